@@ -46,3 +46,4 @@ pub const HIP_MEMCPY_DEVICE_TO_HOST: c_int = 2;
 // own transform, the reference's dataflow (as a real-input transform at W 2048, the application's 2400 / 2205 and every other window but W 8192 and the smallest).
 pub const SGX_FLAG_PAIRED_FRAMES: u32 = 1024;   // opt-in: two frames per transform (half the work; tolerance against the pair's peak)
 pub const SGX_FLAG_COMPLEX_MONO: u32 = 512;     // A/B: the literal (s, s) transform per frame where a real-input kernel would run
+pub const SGX_FLAG_LARGE_TRANSFORM: u32 = 4096; // opt-in: lengths no in-LDS kernel serves, W up to 2^20, as a multi-pass transform through a device scratch

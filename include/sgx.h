@@ -106,6 +106,10 @@ typedef struct sgx_config {
                                       real-input kernel would run (A/B; implies no pairing) */
 #define SGX_FLAG_LUT_WALK 64u      /* fused pixel kernel: walk the dB thresholds from the log2 seed even where the host has shown that one compare pair settles the LUT index (A/B, and the test of the fallback) */
 #define SGX_FLAG_MIXED_GENERIC 256u /* W = 2400: the composite-radix kernel (any 2-3-5-7-smooth length) instead of the tuned 4800-point one (A/B) */
+#define SGX_FLAG_LARGE_TRANSFORM 4096u /* let sgx_create accept lengths that no in-LDS kernel serves: any W from 4 to 2^20 (2W up to 2^21
+                                        points).  Such lengths run a multi-pass transform staged through device memory (stft_kernel 11), and
+                                        the context holds a scratch buffer for it (64 MiB at most).  Lengths an in-LDS kernel serves run that
+                                        kernel whether the flag is set or not. */
 
 typedef struct sgx_info {
     uint32_t struct_size;
@@ -118,7 +122,7 @@ typedef struct sgx_info {
     uint32_t rows;            /* R */
     uint32_t sample_rate_u32; /* SampleRate(sample_rate as u32)      simple_spectrogram.rs:138 */
     uint32_t total_samples_per_column; /* sum over rows of magnitude_in's sample count */
-    uint32_t stft_kernel;     /* 0 = generic power-of-two, 2 = 4096-point workgroup-per-transform (default at W 2048), 4 = Bluestein chirp-z (any 2W), 6 = mixed radix (2W = 2^a 3^b 5^c 7^d <= 20480, e.g. the application's 4800, 4410 and 19200), 9 = 4800-point workgroup-per-transform, 16 x 20 x 15 (default for W = 2400, the application's window at 48 kHz; streams of more than two channels run 6), 10 = 16384-point as 32 x 32 x 16 in one 512-thread workgroup, 32 points per thread (W = 8192; the designs 5, 7 and 8 of rounds 1-5 are gone: profiles/r06_k16.txt) */
+    uint32_t stft_kernel;     /* 0 = generic power-of-two, 2 = 4096-point workgroup-per-transform (default at W 2048), 4 = Bluestein chirp-z (any 2W), 6 = mixed radix (2W = 2^a 3^b 5^c 7^d <= 20480, e.g. the application's 4800, 4410 and 19200), 9 = 4800-point workgroup-per-transform, 16 x 20 x 15 (default for W = 2400, the application's window at 48 kHz; streams of more than two channels run 6), 10 = 16384-point as 32 x 32 x 16 in one 512-thread workgroup, 32 points per thread (W = 8192; the designs 5, 7 and 8 of rounds 1-5 are gone: profiles/r06_k16.txt), 11 = multi-pass four-step transform through a device-memory scratch (SGX_FLAG_LARGE_TRANSFORM only: lengths no other kernel serves; chirp-z over it where 2W has a prime factor above 7; render_path 0) */
                               /* (magnitudes: the tuned kernels -- 2, 6, 9, 10 and the chirp-z plans of 4 -- take |re + i im| through the hardware
                                  square root of fma(re, re, im * im): 1 ulp; the generic kernel (0) and the radix-4 Bluestein ladder use the
                                  correctly rounded sqrtf.  Rows of different kernels for the same input agree within the tolerance, not bit for bit) */
@@ -147,7 +151,9 @@ SGX_API int sgx_config_init(sgx_config *cfg);
 /* Replaces FastFourierTransform::new (fft.rs:18-31: FFTW planning) + AudioStreamTransform::new
  * (audio_transform.rs:22-32) + SimpleSpectrogram's axis/palette construction
  * (simple_spectrogram.rs:88-113).  Builds the Hann table, twiddles, per-row resampling tables,
- * dB thresholds and the default gradient (Magma, simple_spectrogram.rs:95) on the device. */
+ * dB thresholds and the default gradient (Magma, simple_spectrogram.rs:95) on the device.
+ * Lengths: 2W a power of two up to 16384, 2W 2-3-5-7-smooth up to 20480, or any 2W with 3W - 1 <= 16384 (chirp-z); with
+ * SGX_FLAG_LARGE_TRANSFORM also every other W from 4 to 2^20 (stft_kernel 11).  Any other length: SGX_ERR_UNSUPPORTED. */
 SGX_API int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx);
 SGX_API void sgx_destroy(sgx_ctx *ctx);
 

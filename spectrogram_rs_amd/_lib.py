@@ -26,6 +26,7 @@ FLAG_LUT_WALK = 64
 FLAG_MIXED_GENERIC = 256
 FLAG_COMPLEX_MONO = 512
 FLAG_PAIRED_FRAMES = 1024
+FLAG_LARGE_TRANSFORM = 4096
 LIVE_MAGS, LIVE_MAGS_F16, LIVE_RGBA = 0, 1, 2
 LIVE_REFERENCE_SKIP = 1
 

@@ -233,6 +233,8 @@ hipError_t run_stft(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uin
     // W = 8192 (a mono stream whose frames are not paired: as an (s, s) plane through the two-channel instantiation; the 8192-point plan of
     // the mixed-radix kernel's real-input mode measured no faster, round 4)
     if (c->stft_kernel == 10) return sgx::launch_stft_w16384(c, c->d_w16k, d_pcm, channels, pairs, first, n, total, d_mags);
+    // lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM): four-step passes through the context's scratch
+    if (c->stft_kernel == 11) return sgx::launch_stft_large(c, c->d_large, d_pcm, channels, pairs, first, n, total, d_mags);
     // (a mono stream, every frame its own transform: real-input mode of the mixed-radix kernel, 2400 points instead of 4800 on (s, s))
     if (c->stft_kernel == 9 && channels <= 2 && !sgx::mixed_real_serves(c, c->d_mix, channels)) return sgx::launch_stft_w4800(c, c->d_w4800, d_pcm, channels, first, n, total, d_mags, false);
     if (c->stft_kernel == 6 || c->stft_kernel == 9) return sgx::launch_stft_mixed(c, c->d_mix, d_pcm, channels, pairs, first, n, total, d_mags);
@@ -318,10 +320,14 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     if (cfg->lut_index_mode > SGX_LUT_ROUND_NM1) return bail(SGX_ERR_INVALID_ARG, "sgx_create: unknown lut_index_mode");
     if (c->sr_u32 == 0) return bail(SGX_ERR_INVALID_ARG, "sgx_create: sample_rate must be at least 1 Hz");
     const bool pow2 = (c->P & (c->P - 1)) == 0 && c->P <= 16384;
-    if (!pow2 && !sgx::bluestein_supported(c->W) && !sgx::mixed_supported(c->W))
+    const bool in_lds = pow2 || sgx::bluestein_supported(c->W) || sgx::mixed_supported(c->W);
+    const bool large = !in_lds && (cfg->flags & SGX_FLAG_LARGE_TRANSFORM) && sgx::large_supported(c->W);
+    if (!in_lds && !large)
         return bail(SGX_ERR_UNSUPPORTED,
                     "sgx_create: transform length 2W = " + std::to_string(c->P) +
-                        " is not supported by this build (up to 20480 with prime factors 2, 3, 5, 7 only, or any 2W with 3W - 1 <= 16384)");
+                        " is not supported by this build (up to 20480 with prime factors 2, 3, 5, 7 only, or any 2W with 3W - 1 <= 16384" +
+                        (sgx::large_supported(c->W) ? std::string("; SGX_FLAG_LARGE_TRANSFORM serves it as a multi-pass transform)")
+                                                    : std::string(")")));
     c->logP = 0;
     while ((1u << c->logP) < c->P) ++c->logP;
 
@@ -366,7 +372,12 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     // 8 x 16 x 16, 4 x 8 x 16 x 16): same-device A/B against the radix-4 ladder of the generic kernel, mono / stereo:
     // W 512 +29 % / +44 %, W 1024 +48 % / +90 %, W 4096 +83 % / +117 %; W 256: -14 %, W 128: -53 % (run-time geometry)
     const bool pow2_mixed = pow2 && c->W >= SGX_POW2_MIXED_MIN && c->W != 2048 && c->W != 8192 && sgx::mixed_supported(c->W) && !(cfg->flags & SGX_FLAG_FORCE_GENERIC);
-    if (pow2_mixed || (!pow2 && sgx::mixed_supported(c->W) && !((cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::bluestein_supported(c->W)))) {
+    if (large) {
+        // no in-LDS kernel serves this length (SGX_FLAG_LARGE_TRANSFORM): four-step passes through a scratch allocated here
+        e = sgx::large_init(c, &c->d_large);
+        if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: multi-pass transform tables and scratch: ") + hipGetErrorString(e));
+        c->stft_kernel = 11;
+    } else if (pow2_mixed || (!pow2 && sgx::mixed_supported(c->W) && !((cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::bluestein_supported(c->W)))) {
         // a length FFTW would factor: mixed-radix transform of exactly 2W points (SGX_FLAG_FORCE_GENERIC: chirp-z instead)
         e = sgx::mixed_init(c, &c->d_mix);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: mixed-radix tables: ") + hipGetErrorString(e));
@@ -421,6 +432,8 @@ void sgx_destroy(sgx_ctx *c)
     c->d_chz = nullptr;
     sgx::w16384_destroy(c->d_w16k);
     c->d_w16k = nullptr;
+    sgx::large_destroy(c->d_large);
+    c->d_large = nullptr;
     void *ptrs[] = {c->d_window, c->d_twiddle, c->d_rows, c->d_samples, c->d_lut_thr, c->d_alpha_thr,
                     c->d_lut_rgba, c->d_pal_seed, c->d_t_thr, c->d_t_cell, c->d_band_rows, c->d_band_samples, c->d_levels, c->d_ws_mags, c->d_one_in, c->d_one_out, c->d_cksum};
     for (void *p : ptrs)

@@ -129,6 +129,7 @@ struct sgx_ctx {
     void *d_real = nullptr;        // tables of the real-input 4096-point kernel (independent mono frames at W 2048 / H 256)
     void *d_chz = nullptr;         // chirp-z through the mixed-radix kernel's stages (or null: the radix-4 ladder of stft_bluestein.hip)
     void *d_w16k = nullptr;        // tables of the 16384-point kernel, 32 x 32 x 16 (stft16384_w.hip)
+    void *d_large = nullptr;       // plan, tables and scratch of the multi-pass transform (stft_large.hip)
 
     // workspaces (grown on demand, kept)
     float *d_ws_mags = nullptr;
@@ -215,6 +216,13 @@ hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const flo
                                  size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
 hipError_t launch_stft_wg4096_f16(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                                   size_t first_frame, size_t n_frames, size_t total_frames, void *d_mags_f16);
+// stft_large.hip: lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM), W up to 2^20: four-step passes through a scratch the
+// context holds (allocated here, at create time), direct for a 2-3-5-7-smooth 2W, chirp-z otherwise
+bool large_supported(uint32_t W);
+hipError_t large_init(sgx_ctx *c, void **out);
+void large_destroy(void *tables);
+hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
+                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
 hipError_t launch_to_half(const sgx_ctx *c, const float *d_in, void *d_out, size_t n_pairs);
 hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns, uint8_t *d_rgba);
 hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_columns, const RowEntry *d_rows,

@@ -21,7 +21,8 @@ class SpectrogramEngine:
                  interp: int = _lib.INTERP_CUBIC, lut_index_mode: int = _lib.LUT_FLOOR_N,
                  device: Optional[int] = None, force_generic: bool = False, gradient: Optional[str] = None,
                  fused_render: bool = True, lut_walk: bool = False,
-                 mixed_generic: bool = False, complex_mono: bool = False, paired_frames: bool = False):
+                 mixed_generic: bool = False, complex_mono: bool = False, paired_frames: bool = False,
+                 large_transforms: bool = False):
         import torch
 
         self._lib = _lib.load()
@@ -42,7 +43,8 @@ class SpectrogramEngine:
         cfg.device = -1 if device is None else int(device)
         cfg.flags = (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (0 if fused_render else _lib.FLAG_NO_FUSED_RENDER) \
             | (_lib.FLAG_LUT_WALK if lut_walk else 0) | (_lib.FLAG_MIXED_GENERIC if mixed_generic else 0) \
-            | (_lib.FLAG_COMPLEX_MONO if complex_mono else 0) | (_lib.FLAG_PAIRED_FRAMES if paired_frames else 0)
+            | (_lib.FLAG_COMPLEX_MONO if complex_mono else 0) | (_lib.FLAG_PAIRED_FRAMES if paired_frames else 0) \
+            | (_lib.FLAG_LARGE_TRANSFORM if large_transforms else 0)
         if device is not None and torch.cuda.is_available():
             torch.cuda.set_device(int(device))
         rc = self._lib.sgx_create(C.byref(cfg), C.byref(self._ctx))

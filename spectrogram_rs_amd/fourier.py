@@ -80,11 +80,12 @@ class FastFourierTransform(AudioTransform):
     """fft.rs:11-99.  `process` returns Vec<StereoMagnitude> as an [M][2] float32 array."""
 
     def __init__(self, sample_rate: float, period: float, *, device: Optional[int] = None,
-                 force_generic: bool = False):
+                 force_generic: bool = False, large_transforms: bool = False):
         self._sample_rate = _f32(sample_rate)
         self._period = _f32(period)
         self._device = device
         self._force_generic = force_generic
+        self._large_transforms = large_transforms   # lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM)
         self._engines = {}
         self._per_frame = self._engine(1)  # "planning" happens at construction, as FFTW's does (fft.rs:20-24)
 
@@ -94,7 +95,7 @@ class FastFourierTransform(AudioTransform):
         if hop not in self._engines:
             self._engines[hop] = SpectrogramEngine(float(self._sample_rate), window_samples=self.num_input_samples(),
                                                    hop_samples=hop, channels=2, device=self._device,
-                                                   force_generic=self._force_generic)
+                                                   force_generic=self._force_generic, large_transforms=self._large_transforms)
         return self._engines[hop]
 
     def sample_rate(self) -> float:
