@@ -28,6 +28,9 @@ extern "C" {
                             max_frames: usize, d_rgba: *mut u8, n_out: *mut usize) -> c_int;
     pub fn sgx_magnitude_in(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, h_ranges: *const f32,
                             n_ranges: u32, d_out: *mut f32) -> c_int;              // FrequencySample::magnitude_in
+    pub fn sgx_bands_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
+                           max_frames: usize, d_bands: *mut f32, n_out: *mut usize) -> c_int;   // magnitude_in over the context's rows
+    pub fn sgx_bands_fused(ctx: *const SgxCtx) -> c_int;
     pub fn sgx_set_gradient(ctx: *mut SgxCtx, h_rgb: *const u8, n: u32, stereo: c_int) -> c_int;
     pub fn sgx_set_gradient_fn(ctx: *mut SgxCtx, eval: extern "C" fn(f64, *mut u8, *mut c_void), user: *mut c_void,
                                stereo: c_int) -> c_int;
@@ -47,3 +50,4 @@ pub const HIP_MEMCPY_DEVICE_TO_HOST: c_int = 2;
 pub const SGX_FLAG_PAIRED_FRAMES: u32 = 1024;   // opt-in: two frames per transform (half the work; tolerance against the pair's peak)
 pub const SGX_FLAG_COMPLEX_MONO: u32 = 512;     // A/B: the literal (s, s) transform per frame where a real-input kernel would run
 pub const SGX_FLAG_LARGE_TRANSFORM: u32 = 4096; // opt-in: lengths no in-LDS kernel serves, W up to 2^20, as a multi-pass transform through a device scratch
+pub const SGX_LIVE_BANDS: c_int = 3;            // sgx_live_tick: [frames][R][2] f32, the rows of sgx_bands_batch

@@ -88,7 +88,8 @@ typedef struct sgx_config {
 } sgx_config;
 
 #define SGX_FLAG_FORCE_GENERIC 1u /* use the generic power-of-two kernel even where a tuned one exists, the chirp-z kernel even where the mixed-radix one applies (testing) */
-#define SGX_FLAG_NO_FUSED_RENDER 4u /* sgx_render_batch: run STFT and pixel stage as two kernels even where the fused one applies (A/B) */
+#define SGX_FLAG_NO_FUSED_RENDER 4u /* sgx_render_batch: run STFT and pixel stage as two kernels even where the fused one applies (A/B);
+                                       sgx_bands_batch likewise: STFT, then magnitude_in over the context's rows */
 /* Mono streams.  The reference duplicates a mono sample into (s, s) and transforms every frame on its own
  * (audio_input_list_model.rs:67-69, fft.rs:47-99).  DEFAULT here, at every window and hop: exactly that dataflow, one transform per
  * frame -- every frame within north_star's tolerance of its OWN peak on any input.  At W 2048 (any hop, any alignment of the stream)
@@ -221,6 +222,20 @@ SGX_API int sgx_render_mags(sgx_ctx *ctx, const float *d_mags, size_t n_columns,
 SGX_API int sgx_magnitude_in(sgx_ctx *ctx, const float *d_mags, size_t n_columns, const float *h_ranges,
                              uint32_t n_ranges, float *d_out);
 
+/* FrequencySample::magnitude_in (src/fourier/mod.rs:17-21, interpolated_frequency_sample.rs:60-75) over the context's R
+ * log-frequency rows (the ranges [edge[py], edge[py+1]) of sgx_bin_edges), for every frame of the hop loop: the column
+ * sgx_render_batch colours, as floats.
+ *   d_bands [n_out][pairs][R][2] float: (l, r) mean of the interpolated samples; index py = 0 is the LOWEST row (the
+ *   order of sgx_bin_edges and sgx_magnitude_in, NOT the image order of sgx_render_batch).
+ * Bit-identical to sgx_stft_batch followed by sgx_magnitude_in with ranges (edge[py], edge[py+1]).  A mono stream's rows hold
+ * (b, b); with SGX_FLAG_PAIRED_FRAMES as well (frame a of a transform (l, l), frame b (r, r)).
+ * first_frame / max_frames / *n_out as sgx_stft_batch.  Stream-ordered and asynchronous; nothing waits on the host. */
+SGX_API int sgx_bands_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame,
+                            size_t max_frames, float *d_bands, size_t *n_out);
+/* 1: sgx_bands_batch runs one fused kernel from PCM to bands in this context (the palette plays no part); 0: two kernels
+ * (the STFT into a bounded workspace, then magnitude_in over the context's own tables); < 0: error */
+SGX_API int sgx_bands_fused(const sgx_ctx *ctx);
+
 /* SpectrumAnalyzer::push_frequencies (spectrum_analyzer.rs:46-68) for ONE column of magnitudes
  * d_column [M][2] on the device: the n_bars (the widget has 128) adjacent bands of
  * log_space(32, max(sample_rate / 2, 22050), n_bars + 1, 10) (:20-36,52-58; f32 logf / powf on the host),
@@ -245,6 +260,7 @@ typedef struct sgx_live sgx_live;
 #define SGX_LIVE_MAGS 0     /* float [frames][M][2]: what AudioStreamTransform::process yields        */
 #define SGX_LIVE_MAGS_F16 1 /* half  [frames][M][2]: rows of the F16F16 ring (gpu_spectrogram.rs:268) */
 #define SGX_LIVE_RGBA 2     /* uint8 [frames][R][4]: columns of SimpleSpectrogram::snapshot           */
+#define SGX_LIVE_BANDS 3    /* float [frames][R][2]: the columns of magnitude_in over the context's rows */
 
 #define SGX_LIVE_REFERENCE_SKIP 1u /* also skip H samples on the terminating short read, exactly as
                                       audio_transform.rs:37-41 does (it drops up to H samples per tick);

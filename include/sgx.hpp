@@ -113,6 +113,29 @@ public:
         return out;
     }
 
+    // magnitude_in over the context's log-frequency rows (sgx_bin_edges) for every complete frame of `lr`: frames x R (l, r) means,
+    // row 0 the lowest (sgx_bands_batch)
+    std::vector<Output> bands_stream(const StereoMagnitude *lr, std::size_t n)
+    {
+        sgx_info info;
+        int rc = sgx_query(ctx_, &info);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        const std::size_t frames = sgx_num_frames(ctx_, n), r = info.rows;
+        std::vector<Output> out(frames, Output(r));
+        if (!frames) return out;
+        reserve(n * 2 * sizeof(float), frames * r * 2 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        rc = sgx_bands_batch(ctx_, d_in_, n, 0, frames, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(frames * r * 2);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < frames; ++f)
+            for (std::size_t j = 0; j < r; ++j) out[f][j] = {flat[(f * r + j) * 2], flat[(f * r + j) * 2 + 1]};
+        return out;
+    }
+
     sgx_ctx *ctx() { return ctx_; }
 
 private:

@@ -27,7 +27,7 @@ FLAG_MIXED_GENERIC = 256
 FLAG_COMPLEX_MONO = 512
 FLAG_PAIRED_FRAMES = 1024
 FLAG_LARGE_TRANSFORM = 4096
-LIVE_MAGS, LIVE_MAGS_F16, LIVE_RGBA = 0, 1, 2
+LIVE_MAGS, LIVE_MAGS_F16, LIVE_RGBA, LIVE_BANDS = 0, 1, 2, 3
 LIVE_REFERENCE_SKIP = 1
 
 
@@ -96,6 +96,8 @@ SIGNATURES = [
     ("sgx_render_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_render_mags", C.c_int, [_ctx, _vp, _sz, _vp]),
     ("sgx_magnitude_in", C.c_int, [_ctx, _vp, _sz, _vp, C.c_uint32, _vp]),
+    ("sgx_bands_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_bands_fused", C.c_int, [_ctx]),
     ("sgx_spectrum_levels", C.c_int, [_ctx, _vp, C.c_uint32, _vp]),
     ("sgx_live_create", C.c_int, [_ctx, _sz, C.c_uint32, C.POINTER(_vp)]),
     ("sgx_live_destroy", None, [_vp]),

@@ -5,13 +5,15 @@
 //   vbuf        room for p.n_samples float2 behind it
 // P needs: n_samples, samples, interp, rows, R, pairs, n_frames, rgba, pal, guess_a, guess_b.  The caller has a barrier between its
 // last write of m and this call; the function ends without one.
+// BANDS: no colour (sgx_bands_batch) -- p.rgba holds float2 [F][pairs][R], the row's (l, r) mean at py (py = 0 the LOWEST row), the sum and
+// divide of magnitude_in_kernel (sgx_kernels.hip); pal, guess_a and guess_b are not read.
 #pragma once
 
 #include "sgx_internal.hpp"
 
 namespace sgx {
 
-template <uint32_t NT, typename P>
+template <uint32_t NT, bool BANDS = false, typename P>
 __device__ __forceinline__ void pixel_passes(const P &p, const float2 *m, float2 *vbuf, uint32_t M, bool two_columns, uint32_t pair,
                                              long long row_a, long long row_b, uint32_t tid)
 {
@@ -61,6 +63,16 @@ __device__ __forceinline__ void pixel_passes(const P &p, const float2 *m, float2
         if (row.count > 1) {  // x / 1.0 == x: only rows that average several samples divide (:72)
             l = sl / row.count_f;
             r = sr / row.count_f;
+        }
+        if constexpr (BANDS) {  // (x / 1.0 is x: the means of magnitude_in_kernel, which divides every row)
+            float2 *bands = reinterpret_cast<float2 *>(p.rgba);
+            if (two_columns) {
+                if (st_a) bands[((size_t)row_a * p.pairs + pair) * p.R + py] = make_float2(l, l);
+                if (st_b) bands[((size_t)row_b * p.pairs + pair) * p.R + py] = make_float2(r, r);
+            } else if (st_a) {
+                bands[((size_t)row_a * p.pairs + pair) * p.R + py] = make_float2(l, r);
+            }
+            continue;
         }
         const uint32_t y = p.R - 1 - py;  // simple_spectrogram.rs:150
         if (two_columns) {  // mono -> (s, s): both channels carry the same magnitude

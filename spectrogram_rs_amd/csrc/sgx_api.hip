@@ -244,6 +244,20 @@ hipError_t run_stft(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uin
     return sgx::launch_stft_generic(c, d_pcm, channels, pairs, first, n, total, d_mags);
 }
 
+// sgx_bands_batch's route: 1 the fused 4096-point kernels (K1 / real-input K1R), 2 the fused mixed-radix kernels, 0 two kernels.  Only the
+// transform decides it, not the palette: the bands column has no colour.  The fused column must hold the bits of sgx_stft_batch's rows, so
+// a fused kernel serves only contexts whose rows come from the same transform: a W 2400 stream of one or two channels that real-input
+// mode does not take gets its rows from the tuned 4800-point kernel (run_stft), whose last bits differ from the mixed-radix kernel's --
+// those take the two-kernel route (sgx_render_batch's pixels there come from the mixed-radix kernel).
+int bands_route(const sgx_ctx *c)
+{
+    if (c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER) return 0;
+    if (c->stft_kernel == 2 && sgx::wg4096_can_fuse_bands(c, c->d_fast_wg)) return 1;
+    const bool rows_from_w4800 = c->stft_kernel == 9 && c->C <= 2 && !sgx::mixed_real_serves(c, c->d_mix, c->C);
+    if ((c->stft_kernel == 6 || c->stft_kernel == 9) && !rows_from_w4800 && sgx::mixed_can_fuse_bands(c, c->d_mix)) return 2;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -617,6 +631,49 @@ int sgx_render_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fi
     }
     if (n_out) *n_out = n;
     return SGX_OK;
+}
+
+int sgx_bands_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, float *d_bands, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    const size_t total = sgx_num_frames(c, n_samples);
+    if (first_frame >= total || max_frames == 0) return SGX_OK;
+    size_t n = total - first_frame;
+    if (n > max_frames) n = max_frames;
+    if (!d_pcm || !d_bands) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_batch: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const int route = bands_route(c);
+    if (route != 0) {
+        // one kernel from PCM to bands: the magnitudes stay in LDS, 8 B per row leave the kernel
+        const hipError_t e = route == 1 ? sgx::launch_bands_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first_frame, n, total, d_bands)
+                                        : sgx::launch_bands_mixed(c, c->d_mix, d_pcm, c->C, c->pairs, first_frame, n, total, d_bands);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_batch: fused launch");
+        if (n_out) *n_out = n;
+        return SGX_OK;
+    }
+    // two kernels, as sgx_render_batch: the STFT into the bounded workspace, then magnitude_in over the context's own row and sample tables
+    const size_t bytes_per_frame = (size_t)c->pairs * c->M * 2 * sizeof(float);
+    size_t chunk = (size_t)(192u << 20) / bytes_per_frame;
+    if (chunk < 1) chunk = 1;
+    if (chunk > n) chunk = n;
+    int rc = ensure_workspace(c, chunk);
+    if (rc != SGX_OK) return rc;
+    for (size_t done = 0; done < n; done += chunk) {
+        const size_t m = n - done < chunk ? n - done : chunk;
+        hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame + done, m, total, c->d_ws_mags);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_batch: stft launch");
+        e = sgx::launch_magnitude_in(c, c->d_ws_mags, m * c->pairs, c->d_rows, c->d_samples, c->R, d_bands + done * (size_t)c->pairs * c->R * 2);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_batch: magnitude_in launch");
+    }
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+int sgx_bands_fused(const sgx_ctx *c)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    return bands_route(c) != 0 ? 1 : 0;
 }
 
 int sgx_magnitude_in(sgx_ctx *c, const float *d_mags, size_t n_columns, const float *h_ranges, uint32_t n_ranges, float *d_out)

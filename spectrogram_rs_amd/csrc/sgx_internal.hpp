@@ -168,6 +168,9 @@ void wg4096_destroy(void *tables);
 hipError_t launch_stft_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
 bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables);
+bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables);   // the fused column without the colour (sgx_bands_batch): no palette condition
+hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
+                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_bands);   // float2 [F][pairs][R]
 hipError_t launch_deinterleave_pairs(const sgx_ctx *c, const float *d_pcm, float *d_planes, size_t plane_floats, size_t first_sample, size_t n_samples,
                                      uint32_t channels, uint32_t pairs);   // deinterleave.hip
 bool wg4096_seed_is_within_one(const sgx_ctx *c);
@@ -205,6 +208,9 @@ bool chirpz_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels)
 hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
 bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables);   // one kernel from PCM to pixels at this length, palette and row table
+bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables);    // one kernel from PCM to the rows' (l, r) means at this length and row table
+hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
+                              size_t n_frames, size_t total_frames, float *d_bands);
 hipError_t launch_render_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
                                size_t n_frames, size_t total_frames, uint8_t *d_rgba);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
 hipError_t launch_stft_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,

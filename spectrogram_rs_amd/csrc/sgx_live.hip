@@ -154,6 +154,7 @@ static int live_tick(sgx_live *l, int what, void *h_out, sgx_view *view, sgx_ima
     case SGX_LIVE_MAGS: frame_bytes = (size_t)c->M * 2 * sizeof(float); break;
     case SGX_LIVE_MAGS_F16: frame_bytes = (size_t)c->M * 2 * 2; break;
     case SGX_LIVE_RGBA: frame_bytes = (size_t)c->R * 4; break;
+    case SGX_LIVE_BANDS: frame_bytes = (size_t)c->R * 2 * sizeof(float); break;
     default: return live_fail(l, SGX_ERR_INVALID_ARG, "sgx_live_tick: unknown output format");
     }
     LIVE_HIP(l, hipSetDevice(c->device));
@@ -187,6 +188,7 @@ static int live_tick(sgx_live *l, int what, void *h_out, sgx_view *view, sgx_ima
         int rc;
         if (what == SGX_LIVE_MAGS) rc = sgx_stft_batch(c, pcm, n_samples, 0, frames, static_cast<float *>(l->d_out), &got);
         else if (what == SGX_LIVE_MAGS_F16) rc = sgx_stft_batch_f16(c, pcm, n_samples, 0, frames, l->d_out, &got);
+        else if (what == SGX_LIVE_BANDS) rc = sgx_bands_batch(c, pcm, n_samples, 0, frames, static_cast<float *>(l->d_out), &got);
         else rc = sgx_render_batch(c, pcm, n_samples, 0, frames, static_cast<uint8_t *>(l->d_out), &got);
         if (rc != SGX_OK) return rc;
         if (got != frames) return live_fail(l, SGX_ERR_INVALID_ARG, "sgx_live_tick: frame count mismatch");

@@ -103,6 +103,7 @@ __device__ __forceinline__ void fft8_half_zero(const float (&zr)[4], const float
 }
 
 constexpr int kRowsF32 = 0, kRowsF16 = 1, kPixels = 2;   // what a launch writes: float rows, half-pair rows, RGBA columns (fused pixel path)
+constexpr int kBands = 3;   // the fused column's (l, r) row means as float2, no colour (sgx_bands_batch; PIX wg::kPixBandsCubic / kPixBandsCosine)
 
 // PIX (kPixels only): the pixel code of the instantiation, wg::kPixCubic / kPixCosine / kPixGeneric (stft4096_wg.hpp)
 // SLIDE: H = 256, the window slides in registers (above).  Else: any hop (a frame starts on any sample): the eight columns of the
@@ -171,6 +172,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     float2 *tw2 = buf + (TR ? kBufComplexTR : kBufComplex);
     uint2 *pal = reinterpret_cast<uint2 *>(tw2 + 256);          // kPixels only: [256] {threshold, RGBA} (wg::pixel_for)
     constexpr bool F16 = MODE == kRowsF16;
+    constexpr bool FUSED = MODE == kPixels || MODE == kBands;  // the column goes through LDS to the pixel passes
 
     const int tid = threadIdx.x;
     const int t_p1 = TR ? (tid >> 4) + 16 * (tid & 15) : tid;     // pass-1 column of this thread
@@ -181,9 +183,9 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     const float4 *rd4_1 = reinterpret_cast<const float4 *>(plane + 272 * (tid >> 4) + 68 * ((tid & 15) >> 2) + 16 * (tid & 3));
     const float4 *rd4_2 = reinterpret_cast<const float4 *>(plane + 280 * ((tid & 127) >> 3) + 68 * ((8 * (tid >> 7) + (tid & 7)) >> 2) + 16 * (tid & 3));
     tw2[tid] = p.tw2[tid];
-    uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // kPixels: the table words of this thread's rows tid + 256 i
-    if (MODE == kPixels) {
-        pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
+    uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // FUSED: the table words of this thread's rows tid + 256 i
+    if (FUSED) {
+        if (MODE == kPixels) pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if ((uint32_t)tid + 256u * i < p.R) row_words[i] = p.rows[tid + 256 * i];
@@ -363,10 +365,10 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
         // around the loop); past the end of the stream it reads zeros.  (Requested at the TOP of the iteration instead -- a whole
         // iteration to return in -- it sits right behind the previous iteration's sixteen stores: 5-7 % slower, same device.)
         float2 Ln = make_float2(0.0f, 0.0f);
-        if (SLIDE && MODE != kPixels) Ln = column(columns_from(128 * (fa + 2) + 1152), 0);
+        if (SLIDE && !FUSED) Ln = column(columns_from(128 * (fa + 2) + 1152), 0);
         if (!SLIDE) load_pair(fa + 2);     // (R is dead since pass 1; past the end of the stream: zeros, never stored)
 
-        if (MODE == kPixels) __builtin_amdgcn_s_setprio(1);   // the pixel passes are long: 3 only from the row pass (the pixel stores) on
+        if (FUSED) __builtin_amdgcn_s_setprio(1);   // the pixel passes are long: 3 only from the row pass (the pixel stores) on
         else __builtin_amdgcn_s_setprio(3);
         SGX_STAMP(8)    // image-2 reads + FFT16 + next column requested
         lds_barrier();  // everyone has read image 2
@@ -402,9 +404,9 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
         float m1[8], m2[8];
         // rows: every bin pair is stored as soon as it is computed (SGX_K1R_INTERLEAVE; stft4096_wg.hip does the same for (l, r) rows):
         // sixteen stores spread over the untangle instead of one burst behind it
-        constexpr bool kInterleave = MODE != kPixels && SLIDE && SGX_K1R_INTERLEAVE;   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
+        constexpr bool kInterleave = !FUSED && SLIDE && SGX_K1R_INTERLEAVE;   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
         const long long row = (long long)(F == 0 ? la : lb) * (long long)kM * kBin - kBin;      // byte of the (absent) bin 0
-        const __amdgpu_buffer_rsrc_t r = out_rsrc(out, MODE != kPixels ? row : 0, MODE != kPixels && (F == 0 || have_b));
+        const __amdgpu_buffer_rsrc_t r = out_rsrc(out, !FUSED ? row : 0, !FUSED && (F == 0 || have_b));
         const int l1 = kBin * u, l2 = kBin * (1152 - u);                                        // bins u + 128 q3 ; 2048 - u - 128 q3 = (1152 - u) + 128 (7 - q3)
         auto store_pair = [&](const int q3) {
             // bin k at byte kBin (k - 1).  Thread 0's q3 = 0 slot: bin 1024 from m1, and a second copy of it where its m2 would go.
@@ -450,7 +452,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
         }
 
         // ---- store row [M][2] (or half pairs): straight-line code: the wait for the prefetched rows below is then vmcnt(stores issued since)
-        if (MODE != kPixels) {
+        if (!FUSED) {
             if (!kInterleave) {
 #pragma unroll
                 for (int q3 = 0; q3 < 8; ++q3) store_pair(q3);
@@ -500,11 +502,16 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             SGX_STAMP(16)   // (pixels) sample pass
             lds_barrier();
             SGX_STAMP(17)   // (pixels) barrier 8
-            uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
             __builtin_amdgcn_s_setprio(3);
-            wg::row_pass<true, PIX>(p, row_words, vbuf, rgba + la * (size_t)p.R, rgba + lb * (size_t)p.R, true, have_b, pal, tid);
+            if constexpr (MODE == kBands) {
+                float2 *bands = reinterpret_cast<float2 *>(p.rgba);
+                wg::row_pass_bands<true>(p, row_words, vbuf, bands + la * (size_t)p.R, bands + lb * (size_t)p.R, true, have_b, tid);
+            } else {
+                uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
+                wg::row_pass<true, PIX>(p, row_words, vbuf, rgba + la * (size_t)p.R, rgba + lb * (size_t)p.R, true, have_b, pal, tid);
+            }
         }
-        if (SLIDE && MODE != kPixels) {
+        if (SLIDE && !FUSED) {
             // `Ln` is pinned behind the row stores: its copy into L needs the load complete, and scheduled in front of the stores (where
             // the compiler had put it) that is a vmcnt(0) in the middle of the iteration; here it is vmcnt(stores since).  (The load
             // straight into L behind the slide, no second pair: 4 % slower on the same device.)
@@ -599,7 +606,7 @@ namespace wg {
 
 // p: as launch_wg (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
 // transform's own tables and the job split are set here
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render)
+hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands)
 {
     using namespace wgr;
     if (p.n_frames == 0) return hipSuccess;
@@ -618,7 +625,10 @@ hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, 
     auto launch = [&](auto slide_c) {
         constexpr bool S_ = decltype(slide_c)::value;
         constexpr size_t lds_rows = (S_ && SGX_ADDTID_R) ? kLdsBytesR : kLdsBytes, lds_render = (S_ && SGX_ADDTID_R) ? kLdsBytesRenderR : kLdsBytesRender;
-        if (render) {
+        if (render && bands) {   // (no palette: the row-image LDS size)
+            if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCosine, S_>), grid, block, lds_rows, c->stream, p);
+            else hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCubic, S_>), grid, block, lds_rows, c->stream, p);
+        } else if (render) {
             if (!p.seed_pm1) hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixGeneric, S_>), grid, block, lds_render, c->stream, p);
             else if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixCosine, S_>), grid, block, lds_render, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixCubic, S_>), grid, block, lds_render, c->stream, p);

@@ -99,7 +99,8 @@ __device__ __forceinline__ void read_planes(const float4 *rd4, float (&xr)[16], 
 template <bool MONO, int PAIRING, bool C2, int PIX>
 __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
 {
-    constexpr bool RENDER = PIX != kPixNone && PIX != kPixRowsF16;
+    constexpr bool RENDER = PIX != kPixNone && PIX != kPixRowsF16;   // the fused column: pixels, or (BANDS) its float means
+    constexpr bool BANDS = pix_bands(PIX);
     constexpr bool F16 = PIX == kPixRowsF16;    // rows as (l, r) half pairs (compile-time: the row stores are straight-line code)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf = reinterpret_cast<float2 *>(smem_raw);
@@ -123,7 +124,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     tw2[tid] = p.tw2[tid];
     uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // RENDER: the table words of this thread's rows tid + 256 i
     if (RENDER) {
-        pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
+        if (!BANDS) pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if ((uint32_t)tid + 256u * i < p.R) row_words[i] = p.rows[tid + 256 * i];
@@ -518,11 +519,19 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
             // the same wait is a vmcnt(0) again: every pixel store just issued acknowledged by memory, once per column
             if (!(MONO && PAIRING == kPairAdjacentRow && kSlideWindow)) next_samples_are_here();
             lds_barrier();
-            uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
-            uchar4 *dst_a = rgba + ((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * (size_t)p.R;
-            uchar4 *dst_b = rgba + ((size_t)f1 * p.pairs + p.pair) * (size_t)p.R;
-            __builtin_amdgcn_s_setprio(3);
-            row_pass<MONO, PIX>(p, row_words, vbuf, dst_a, dst_b, have_first, have_second, pal, tid);
+            if constexpr (BANDS) {
+                float2 *bands = reinterpret_cast<float2 *>(p.rgba);   // [F][pairs][R] (l, r)
+                float2 *dst_a = bands + ((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * (size_t)p.R;
+                float2 *dst_b = bands + ((size_t)f1 * p.pairs + p.pair) * (size_t)p.R;
+                __builtin_amdgcn_s_setprio(3);
+                row_pass_bands<MONO>(p, row_words, vbuf, dst_a, dst_b, have_first, have_second, tid);
+            } else {
+                uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
+                uchar4 *dst_a = rgba + ((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * (size_t)p.R;
+                uchar4 *dst_b = rgba + ((size_t)f1 * p.pairs + p.pair) * (size_t)p.R;
+                __builtin_amdgcn_s_setprio(3);
+                row_pass<MONO, PIX>(p, row_words, vbuf, dst_a, dst_b, have_first, have_second, pal, tid);
+            }
         }
         SGX_STAMP(13)   // row stores issued (fused pixel path: the pixel passes)
         if (!RENDER && !(MONO && PAIRING == kPairAdjacentRow && kSlideWindow)) next_samples_are_here();   // rows: behind the stores, vmcnt(stores issued since)
@@ -677,6 +686,13 @@ bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables)
     return t && t->fusable && c->pal.n == 256 && !c->pal.stereo && !c->pal.segments;
 }
 
+bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables)
+{
+    (void)c;   // the column without the colour: only the row and sample tables have to fit
+    const auto *t = static_cast<const wg::WgTables *>(tables);
+    return t && t->fusable;
+}
+
 void lut_seed_coefficients(const sgx_ctx *c, float &a, float &b)
 {
     // t * n = (10 log10(x) - min_db) * n / (max_db - min_db) = log2(x) * a + b   (seed only)
@@ -695,9 +711,11 @@ bool wg4096_seed_is_within_one(const sgx_ctx *c)
 
 namespace {
 
+// RENDER: the fused column into d_rgba -- RGBA pixels, or with `bands` the (l, r) means as float2 per row
 template <bool RENDER>
 hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                     size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, uint8_t *d_rgba, bool out_f16 = false)
+                     size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, uint8_t *d_rgba, bool out_f16 = false,
+                     bool bands = false)
 {
     using namespace wg;
     if (n_frames == 0) return hipSuccess;
@@ -754,8 +772,10 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
             p.rgba = d_rgba;
             p.R = c->R;
             p.interp = c->cfg.interp;
-            lut_seed_coefficients(c, p.guess_a, p.guess_b);
-            p.seed_pm1 = wg4096_seed_is_within_one(c) ? 1u : 0u;
+            if (!bands) {
+                lut_seed_coefficients(c, p.guess_a, p.guess_b);
+                p.seed_pm1 = wg4096_seed_is_within_one(c) ? 1u : 0u;
+            }
             p.single_rows = t->single_rows;
             p.block_max_cnt = t->block_max_cnt;
         }
@@ -765,7 +785,7 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         const uint32_t fl = c->cfg.flags;      // (sgx_create: INDEPENDENT is set unless PAIRED was asked for)
         const bool own_transform = !(fl & SGX_FLAG_PAIRED_FRAMES) || (fl & SGX_FLAG_COMPLEX_MONO) != 0;
         if (channels == 1 && own_transform && !(fl & SGX_FLAG_COMPLEX_MONO) && real4096_serves(c, d_pcm, channels))
-            return launch_real4096(c, c->d_real, p, out_f16, RENDER);
+            return launch_real4096(c, c->d_real, p, out_f16, RENDER, bands);
         const bool mono = channels == 1 && (fl & SGX_FLAG_PAIRED_FRAMES) && !(fl & SGX_FLAG_COMPLEX_MONO);
         p.pair_base = mono ? first_frame / 2 : 0;
         p.n_jobs = mono ? (first_frame + n_frames + 1) / 2 - first_frame / 2 : n_frames;
@@ -777,15 +797,18 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         blocks = (p.n_jobs + per - 1) / per;
         p.jobs_per_block = per;
         const dim3 grid((unsigned)blocks), block(256);
-        const size_t lds = RENDER ? kLdsBytesRender : kLdsBytes;
+        const size_t lds = RENDER && !bands ? kLdsBytesRender : kLdsBytes;   // (the bands rows need no palette)
         // the pixel code of the instantiation: the interpolator and the seed-only LUT search are compile-time (kPixCubic / kPixCosine);
         // SGX_FLAG_LUT_WALK and palettes whose seed proof fails run kPixGeneric
-        const int pix = !RENDER ? kPixNone : (!p.seed_pm1 ? kPixGeneric : (p.interp == SGX_INTERP_COSINE ? kPixCosine : kPixCubic));
+        const int pix = !RENDER ? kPixNone : bands ? (p.interp == SGX_INTERP_COSINE ? kPixBandsCosine : kPixBandsCubic)
+                                   : (!p.seed_pm1 ? kPixGeneric : (p.interp == SGX_INTERP_COSINE ? kPixCosine : kPixCubic));
         auto launch = [&](auto mono_c, auto pairing_c, auto c2_c) {
             constexpr bool M_ = decltype(mono_c)::value, C2_ = decltype(c2_c)::value;
             constexpr int P_ = decltype(pairing_c)::value;
             if (!RENDER && out_f16) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixRowsF16>), grid, block, lds, c->stream, p);
             else if (!RENDER) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixNone>), grid, block, lds, c->stream, p);
+            else if (pix == kPixBandsCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCubic : kPixNone>), grid, block, lds, c->stream, p);
+            else if (pix == kPixBandsCosine) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCosine : kPixNone>), grid, block, lds, c->stream, p);
             else if (pix == kPixCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixCubic : kPixNone>), grid, block, lds, c->stream, p);
             else if (pix == kPixCosine) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixCosine : kPixNone>), grid, block, lds, c->stream, p);
             else hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixGeneric : kPixNone>), grid, block, lds, c->stream, p);
@@ -828,6 +851,13 @@ hipError_t launch_render_wg4096(const sgx_ctx *c, const void *tables, const floa
                                 size_t first_frame, size_t n_frames, size_t total_frames, uint8_t *d_rgba)
 {
     return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr, d_rgba);
+}
+
+hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
+                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_bands)
+{
+    return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr,
+                           reinterpret_cast<uint8_t *>(d_bands), false, true);
 }
 
 }  // namespace sgx

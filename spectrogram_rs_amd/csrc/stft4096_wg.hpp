@@ -60,7 +60,7 @@ struct Params {
 };
 
 // stft4096_real.hip
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render);
+hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands = false);
 
 // Which two mono frames share a transform: always (2j, 2j+1).
 //   kPairAdjacentRow : H = 256: frame 2j+1's rows are frame 2j's rows shifted by one (9 rows feed both)
@@ -194,6 +194,9 @@ constexpr int kMaxFusedSamples = kBufComplex - kColSlots;       // float2 per sa
 // which pixel code an instantiation carries: the launch-uniform switches -- the interpolator, the LUT search -- are compile-time,
 // each instantiation holds one path's code and live ranges
 constexpr int kPixNone = 0, kPixCubic = 1, kPixCosine = 2, kPixGeneric = 3, kPixRowsF16 = 4;   // kPixRowsF16: no pixels either -- half-pair rows (stft4096_wg.hip)
+// the fused column without the colour (sgx_bands_batch): the row pass stores the (l, r) means as float2, lowest row first; no palette
+constexpr int kPixBandsCubic = 5, kPixBandsCosine = 6;
+constexpr bool pix_bands(int pix) { return pix == kPixBandsCubic || pix == kPixBandsCosine; }
 //   // kPixGeneric: interpolator at run time, LUT seed + walk (SGX_FLAG_LUT_WALK / proof failed)
 
 // (The repeats are written by the ONE thread that holds bin 1 / bin 2047, in the one unrolled step where it does -- a test of the
@@ -317,7 +320,7 @@ __device__ __forceinline__ void sample_pass_with(const Params &p, const float2 *
     for (int k = 0; k < kSampleSteps; ++k) {
         const uint32_t s = tid + 256 * k;
         if (s < p.n_samples) {
-            if (PIX == kPixCosine || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) vbuf[s] = interp_sample2<true>(P, se[k].i0, se[k].w);
+            if (PIX == kPixCosine || PIX == kPixBandsCosine || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) vbuf[s] = interp_sample2<true>(P, se[k].i0, se[k].w);
             else vbuf[s] = interp_sample2<false>(P, se[k].i0, se[k].w);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -327,7 +330,7 @@ __device__ __forceinline__ void sample_pass_with(const Params &p, const float2 *
 template <int PIX>
 __device__ __forceinline__ void sample_pass(const Params &p, const float2 *P, float2 *vbuf, int tid)
 {
-    if (PIX == kPixCosine || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) sample_pass_for<true>(p, P, vbuf, tid);
+    if (PIX == kPixCosine || PIX == kPixBandsCosine || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) sample_pass_for<true>(p, P, vbuf, tid);
     else sample_pass_for<false>(p, P, vbuf, tid);
 }
 
@@ -432,6 +435,50 @@ __device__ __forceinline__ void row_pass(const Params &p, const uint32_t (&row_w
         // one row at a time: without this fence the scheduler interleaves the four unrolled rows, and the kernels -- at the 128-VGPR cap
         // of four waves per SIMD -- spill 15 to 34 registers
         asm volatile("" ::: "memory");
+    }
+}
+
+// The row pass of the bands instantiations: FrequencySample::magnitude_in (interpolated_frequency_sample.rs:60-75) as magnitude_in_kernel
+// (sgx_kernels.hip) computes it -- the sum from zero in lin_space order, then the divide (x / 1.0 is x) -- stored as one float2 per row at
+// dst[py], py = 0 the LOWEST row: a wave's 64 consecutive rows are one contiguous 512-byte run.  MONO: .x / .y are the two frames of the
+// transform, each stored as (s, s); else (l, r).
+template <bool MONO>
+__device__ __forceinline__ void row_pass_bands(const Params &p, const uint32_t (&row_words)[4], const float2 *vbuf, float2 *dst_a, float2 *dst_b,
+                                               bool have_a, bool have_b, int tid)
+{
+#pragma unroll 1
+    for (int i_row = 0; i_row < 4; ++i_row) {
+        const uint32_t py = tid + 256 * i_row;
+        if (py >= p.R) break;
+        const uint32_t re = i_row == 0 ? row_words[0] : i_row == 1 ? row_words[1] : i_row == 2 ? row_words[2] : row_words[3];
+        const uint32_t first = re & 0xffffu, cnt = re >> 16;
+        float l, r;
+        if (p.single_rows & (1u << i_row)) {          // (launch-uniform) one sample: 0 + x (the sign of a zero as the sum gives it), / 1.0 = x
+            const float2 v = vbuf[first];
+            l = 0.0f + v.x;
+            r = 0.0f + v.y;
+        } else {
+            float sl = 0.0f, sr = 0.0f;
+            for (uint32_t i = 0; i < cnt; ++i) {
+                const float2 v = vbuf[first + i];
+                sl = sl + v.x;
+                sr = sr + v.y;
+            }
+            l = sl;
+            r = sr;
+            if (cnt > 1) {
+                const float nf = (float)cnt;
+                l = sl / nf;
+                r = sr / nf;
+            }
+        }
+        if (MONO) {
+            if (have_a) dst_a[py] = make_float2(l, l);
+            if (have_b) dst_b[py] = make_float2(r, r);
+        } else {
+            dst_a[py] = make_float2(l, r);
+        }
+        asm volatile("" ::: "memory");   // one row at a time (see row_pass)
     }
 }
 

@@ -335,7 +335,7 @@ __device__ __forceinline__ void untangle_store(const Params &p, const float2 *s,
 
 // ... and the pixel stage on it: the column (s, s) of the one frame, then pixel_passes as below (the launch asks for LDS for the column
 // and its samples, which the W-point image alone would not hold).
-template <uint32_t NT, uint32_t WN>
+template <uint32_t NT, uint32_t WN, bool BANDS = false>   // BANDS: the column's float means, no colour (pixel_passes)
 __device__ __forceinline__ void pixel_epilogue_real(const Params &p, float2 *s, long long row, uint32_t tid)
 {
     constexpr uint32_t M = WN - 1, K = WN / 2, kPer = (K + NT - 1) / NT;
@@ -355,7 +355,7 @@ __device__ __forceinline__ void pixel_epilogue_real(const Params &p, float2 *s, 
         }
     }
     __syncthreads();
-    pixel_passes<NT>(p, s, s + M + 1, M, false, 0u, row, -1, tid);
+    pixel_passes<NT, BANDS>(p, s, s + M + 1, M, false, 0u, row, -1, tid);
 }
 
 // The pixel stage on the transform's own LDS image (magnitude_in -> color_for -> put_pixel, simple_spectrogram.rs:141-161), as
@@ -364,7 +364,7 @@ __device__ __forceinline__ void pixel_epilogue_real(const Params &p, float2 *s, 
 // interpolated samples behind it, then one thread per row.  A mono stream carries two frames per transform: .x / .y of a
 // bin are the two columns, each an (s, s) pixel.  256-level palettes without the diverging branch whose thresholds pass
 // the seed proof only (mixed_can_fuse_render); everything else takes the two-kernel route.
-template <uint32_t NT, uint32_t WN>
+template <uint32_t NT, uint32_t WN, bool BANDS = false>
 __device__ __forceinline__ void pixel_epilogue(const Params &p, float2 *s, uint32_t pair, long long row_a, long long row_b, uint32_t tid)
 {
     constexpr uint32_t M = WN - 1, kPer = (M + NT - 1) / NT;
@@ -388,9 +388,10 @@ __device__ __forceinline__ void pixel_epilogue(const Params &p, float2 *s, uint3
         if (j < M) s[j] = mg[i];
     }
     __syncthreads();
-    pixel_passes<NT>(p, s, s + M + 1, M, p.mono_pairs != 0, pair, row_a, row_b, tid);
+    pixel_passes<NT, BANDS>(p, s, s + M + 1, M, p.mono_pairs != 0, pair, row_a, row_b, tid);
 }
 
+#ifndef SGX_MIXED_KERNELS_ONLY
 __global__ void __launch_bounds__(1024) stft_mixed_kernel(Params p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -424,6 +425,7 @@ __global__ void __launch_bounds__(1024) stft_mixed_kernel(Params p)
     if (p.real) untangle_store(p, s, row_a, tid, nt);
     else split_store(p, s, pair, row_a, row_b, tid, nt);
 }
+#endif
 
 // The two lengths the application produces (0.05 s at 48 and 44.1 kHz), three stages each, everything about the plan a
 // compile-time constant.  PAD = R2 (even) -> position(i) = i + i / R2; the host checks that its own plan for the length is
@@ -647,8 +649,14 @@ struct ChirpTables {
 #define MIX_FIXED4_PLANS(X) X(9600, 4, 3, 5, 2, 5, 1, 4, 4, 1024) X(19200, 5, 3, 5, 1, 4, 4, 4, 4, 1024) \
                             X(17640, 5, 3, 7, 2, 4, 3, 7, 1, 1024) X(8192, 4, 1, 4, 2, 4, 4, 4, 4, 512)
 
+// the bands instantiations (stft_mixed_bands.hip): the kernel of the plan `fixed` that launch_mixed would run to pixels (real-input mode,
+// two frames per workgroup, as it chose them), writing the (l, r) means instead; hipErrorNotSupported when no bands kernel has that plan
+hipError_t launch_bands_kernel(const Params &p, int fixed, bool real, bool two_frames, dim3 grid, size_t lds, hipStream_t stream);
+bool bands_kernel_exists(int fixed, bool real, bool two_frames);
+
 }  // namespace mix
 
+#ifndef SGX_MIXED_KERNELS_ONLY
 bool mixed_supported(uint32_t W)
 {
     uint32_t n = 2 * W;
@@ -875,10 +883,27 @@ bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels)
 
 // real-input mode from PCM to pixels: a compile-time W-point plan, the palette conditions of the fused pixel stage, W / 2 bin pairs in
 // registers (ten per thread at most); the launch sizes its LDS for the column and its samples
-static bool real_fuses_render(const sgx_ctx *c, const mix::MixTables *t)
+// (the palette conditions: the bands instantiations have no palette and fuse without them)
+static bool fused_palette(const sgx_ctx *c)
+{
+    return !c->pal.stereo && !c->pal.segments && c->pal.n == 256 && c->d_pal_seed && wg4096_seed_is_within_one(c);
+}
+
+static bool real_two_frames(int fixed)   // real-input mode to pixels or bands: two frames per workgroup at this plan
+{
+#ifndef SGX_KM_REAL1
+#define X(Pn, A0, B0, A1, B1, A2, B2, N) if (fixed == Pn) return true;
+    MIX_REAL2_RENDER_PLANS(X)
+#undef X
+#endif
+    (void)fixed;
+    return false;
+}
+
+static bool real_column_fits(const sgx_ctx *c, const mix::MixTables *t)
 {
     const auto *h = t->half;
-    if (!h || !h->fixed || c->pal.stereo || c->pal.segments || c->pal.n != 256 || !c->d_pal_seed || !wg4096_seed_is_within_one(c)) return false;
+    if (!h || !h->fixed) return false;
     unsigned nt = 0;
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) if (h->fixed == Pn) nt = N;
     MIX_FIXED_PLANS(X)
@@ -890,13 +915,34 @@ static bool real_fuses_render(const sgx_ctx *c, const mix::MixTables *t)
     return nt && c->W / 2 <= nt * 10u && ((size_t)c->M + 1 + c->tab.samples.size()) * sizeof(float2) <= 160 * 1024;
 }
 
+static bool real_fuses_render(const sgx_ctx *c, const mix::MixTables *t) { return fused_palette(c) && real_column_fits(c, t); }
+
+static bool real_fuses_bands(const sgx_ctx *c, const mix::MixTables *t)
+{
+    return real_column_fits(c, t) && mix::bands_kernel_exists(t->half->fixed, true, real_two_frames(t->half->fixed));
+}
+
+static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t);
+
 bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables)
 {
     const auto *t = static_cast<const mix::MixTables *>(tables);
     // (a mono stream that real-input mode cannot take to pixels goes the two-kernel route on real-input ROWS, not through the 2W-point
     // plan as an (s, s) frame: the pixels of a context are those of its rows)
     if (mixed_real_serves(c, tables, c->C)) return real_fuses_render(c, t);
-    if (!t || !t->fixed || c->pal.stereo || c->pal.segments || c->pal.n != 256 || !c->d_pal_seed || !wg4096_seed_is_within_one(c)) return false;
+    return fused_palette(c) && mixed_column_fits(c, t);
+}
+
+bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables)
+{
+    const auto *t = static_cast<const mix::MixTables *>(tables);
+    if (mixed_real_serves(c, tables, c->C)) return real_fuses_bands(c, t);
+    return mixed_column_fits(c, t) && mix::bands_kernel_exists(t->fixed, false, false);
+}
+
+static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t)
+{
+    if (!t || !t->fixed) return false;
     // the column and its interpolated samples on the transform's LDS image; ten bins per thread in registers at most
     unsigned nt = 0;
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) if (t->fixed == Pn) nt = N;
@@ -909,7 +955,8 @@ bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables)
 }
 
 static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba);
+                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
+                               bool bands = false);
 
 hipError_t launch_stft_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16)
@@ -923,14 +970,23 @@ hipError_t launch_render_mixed(const sgx_ctx *c, const void *tables, const float
     return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr, false, d_rgba);
 }
 
+hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
+                              size_t n_frames, size_t total_frames, float *d_bands)
+{
+    return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr, false,
+                        reinterpret_cast<uint8_t *>(d_bands), true);
+}
+
+// d_rgba: the fused column -- RGBA pixels, or with `bands` float2 (l, r) means per row (sgx_bands_batch)
 static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba)
+                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
+                               bool bands)
 {
     using namespace mix;
     if (n_frames == 0) return hipSuccess;
     const auto *t = static_cast<const MixTables *>(tables);
     // a mono stream, every frame its own transform (the default): real-input mode on the W-point plan, where there is one
-    const bool real = mixed_real_serves(c, tables, channels) && (!d_rgba || real_fuses_render(c, t));
+    const bool real = mixed_real_serves(c, tables, channels) && (!d_rgba || (bands ? real_fuses_bands(c, t) : real_fuses_render(c, t)));
     if (real) t = t->half;
     Params p{};
     if (d_rgba) {
@@ -942,7 +998,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         p.rows = c->d_rows;
         p.samples = c->d_samples;
         p.pal = c->d_pal_seed;
-        lut_seed_coefficients(c, p.guess_a, p.guess_b);
+        if (!bands) lut_seed_coefficients(c, p.guess_a, p.guess_b);
     }
     p.pcm = d_pcm;
     p.window = c->d_window;
@@ -976,12 +1032,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
     if (real) p.vec2 = c->W % 2 == 0 ? 1u : 0u;   // sample PAIRS of one channel as 8-byte words (any hop, any alignment: see stage())
     size_t lds = (size_t)t->lds_points * sizeof(float2);
     if (real && d_rgba) lds = std::max(lds, ((size_t)c->M + 1 + c->tab.samples.size()) * sizeof(float2));   // the column and its samples
-    bool two_frames = false;   // real-input mode to pixels at the two application plans: two frames (two images) per workgroup
-#ifndef SGX_KM_REAL1
-#define X(Pn, A0, B0, A1, B1, A2, B2, N) if (real && d_rgba && t->fixed == Pn) two_frames = true;
-    MIX_REAL2_RENDER_PLANS(X)
-#undef X
-#endif
+    const bool two_frames = real && d_rgba && real_two_frames(t->fixed);   // real-input mode to pixels at the application plans: two frames (two images) per workgroup
     if (two_frames) lds = std::max(lds, 2 * (size_t)t->lds_points * sizeof(float2));
     const unsigned threads = t->threads;
     hipError_t attr_err = hipSuccess;
@@ -993,6 +1044,10 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, c->stream, p);
     };
     auto launch = [&](dim3 grid) {
+        if (bands) {
+            attr_err = launch_bands_kernel(p, t->fixed, real, two_frames, grid, lds, c->stream);
+            return;
+        }
         if (two_frames)
             switch (t->fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N)                                                                                                  \
@@ -1048,7 +1103,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         p.first_frame = first_frame + done;
         p.n_frames = chunk;
         p.mags = d_mags ? d_mags + done * (size_t)pairs * c->M * (out_f16 ? 1 : 2) : nullptr;
-        if (d_rgba) p.rgba = d_rgba + done * (size_t)pairs * c->R * 4;
+        if (d_rgba) p.rgba = d_rgba + done * (size_t)pairs * c->R * (bands ? 8 : 4);
         launch(dim3((unsigned)chunk, pairs));
         hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
         if (e != hipSuccess) return e;
@@ -1305,5 +1360,7 @@ hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float 
     }
     return hipSuccess;
 }
+
+#endif  // SGX_MIXED_KERNELS_ONLY
 
 }  // namespace sgx

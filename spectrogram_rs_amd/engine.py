@@ -198,6 +198,29 @@ class SpectrogramEngine:
             assert got.value == n
         return out
 
+    def bands_batch(self, pcm, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [frames][pairs][R][2] float32: magnitude_in over the context's rows for every frame, row 0 = the LOWEST
+        (the order of bin_edges(); bit-identical to stft_batch followed by magnitude_in over those edges)."""
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        out = self._out(out, (n, self.pairs, self.R, 2), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_bands_batch(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n,
+                                                  C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return out
+
+    @property
+    def bands_fused(self) -> int:
+        """1 when bands_batch runs one fused kernel from PCM to bands in this context, 0 when it runs two"""
+        return self._check(self._lib.sgx_bands_fused(self._ctx))
+
     def render_mags(self, mags, out=None):
         """[columns][M][2] float32 magnitudes -> [columns][R][4] uint8."""
         import torch
@@ -333,7 +356,7 @@ class LiveRing:
     AudioStreamTransform::process (audio_transform.rs:34-42), run on the GPU once per tick."""
 
     _FORMATS = {"mags": (_lib.LIVE_MAGS, np.float32), "mags_f16": (_lib.LIVE_MAGS_F16, np.float16),
-                "rgba": (_lib.LIVE_RGBA, np.uint8)}
+                "rgba": (_lib.LIVE_RGBA, np.uint8), "bands": (_lib.LIVE_BANDS, np.float32)}
 
     def __init__(self, engine: SpectrogramEngine, capacity: int = 4096, reference_skip: bool = False):
         self.engine = engine
@@ -371,12 +394,13 @@ class LiveRing:
 
     def tick(self, what: str = "mags", max_frames: Optional[int] = None) -> np.ndarray:
         """One GUI tick: every complete frame of the ring as a host array
-        ("mags": [frames][M][2] f32, "mags_f16": the same in half, "rgba": [frames][R][4] u8)."""
+        ("mags": [frames][M][2] f32, "mags_f16": the same in half, "rgba": [frames][R][4] u8,
+        "bands": [frames][R][2] f32 -- bands_batch's rows, lowest first)."""
         code, dtype = self._FORMATS[what]
         e = self.engine
         if max_frames is None:
             max_frames = e.num_frames(self.capacity)
-        shape = (max_frames, e.R, 4) if what == "rgba" else (max_frames, e.M, 2)
+        shape = {"rgba": (max_frames, e.R, 4), "bands": (max_frames, e.R, 2)}.get(what, (max_frames, e.M, 2))
         out = np.empty(shape, dtype)
         got = C.c_size_t(0)
         e._check(self._lib.sgx_live_tick(self._h, code, out.ctypes.data_as(C.c_void_p), max_frames, C.byref(got)))
