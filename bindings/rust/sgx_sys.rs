@@ -24,6 +24,8 @@ extern "C" {
                           max_frames: usize, d_mags: *mut f32, n_out: *mut usize) -> c_int;
     pub fn sgx_stft_batch_f16(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
                               max_frames: usize, d_mags_f16: *mut c_void, n_out: *mut usize) -> c_int;   // F16F16 ring rows
+    pub fn sgx_stft_batch_complex(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
+                                  max_frames: usize, d_spec: *mut f32, n_out: *mut usize) -> c_int;   // (L, R) complex spectra
     pub fn sgx_render_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
                             max_frames: usize, d_rgba: *mut u8, n_out: *mut usize) -> c_int;
     pub fn sgx_magnitude_in(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, h_ranges: *const f32,

@@ -186,6 +186,17 @@ SGX_API int sgx_sync(sgx_ctx *ctx);
 SGX_API int sgx_stft_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame,
                            size_t max_frames, float *d_mags, size_t *n_out);
 
+/* The transform of sgx_stft_batch without the magnitude: the complex spectra of the (l, r) split (fft.rs:81-98 before `hypot`).
+ *   d_spec [n_out][pairs][M][2][2] float: per bin k = 1..W-1 (L.re, L.im, R.re, R.im) with
+ *     L[k] = (F[k] + conj F[P-k]) / 2 * (2/W),   R[k] = (F[k] - conj F[P-k]) / (2i) * (2/W),
+ *   F = the 2W-point forward DFT (e^{-2 pi i k n / P}) of (l + i r) * Hann, zero-padded; time origin = the frame's first sample.
+ *   So L = DFT(Hann * l) * 2/W and R = DFT(Hann * r) * 2/W, and |L|, |R| are sgx_stft_batch's rows.
+ *   Mono: (X, X) per bin, X = DFT(Hann * s) * 2/W, the same as the (s, s) dataflow gives; with SGX_FLAG_PAIRED_FRAMES
+ *   the frame's own X in both halves.
+ * first_frame / max_frames / *n_out as sgx_stft_batch.  Stream-ordered and asynchronous. */
+SGX_API int sgx_stft_batch_complex(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame,
+                                   size_t max_frames, float *d_spec, size_t *n_out);
+
 /* The same transform with the magnitudes stored as IEEE half (l, r) pairs, 4 bytes per bin
  * (round to nearest even): d_mags_f16 [n_out][pairs][M][2] half.  This is the texel format of the
  * F16F16 ring texture the default widget uploads its frames into (gpu_spectrogram.rs:218-226,

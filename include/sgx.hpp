@@ -15,6 +15,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <array>
+#include <complex>
 #include <cstddef>
 #include <deque>
 #include <optional>
@@ -133,6 +135,29 @@ public:
         check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (std::size_t f = 0; f < frames; ++f)
             for (std::size_t j = 0; j < r; ++j) out[f][j] = {flat[(f * r + j) * 2], flat[(f * r + j) * 2 + 1]};
+        return out;
+    }
+
+    // the complex (L, R) spectra behind process_stream's magnitudes for every complete frame of `lr`: frames x (W-1) bins of
+    // {L, R} (sgx_stft_batch_complex)
+    std::vector<std::vector<std::array<std::complex<float>, 2>>> process_stream_complex(const StereoMagnitude *lr, std::size_t n)
+    {
+        const std::size_t frames = sgx_num_frames(ctx_, n), m = num_output_frequencies();
+        std::vector<std::vector<std::array<std::complex<float>, 2>>> out(frames, std::vector<std::array<std::complex<float>, 2>>(m));
+        if (!frames) return out;
+        reserve(n * 2 * sizeof(float), frames * m * 4 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        int rc = sgx_stft_batch_complex(ctx_, d_in_, n, 0, frames, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(frames * m * 4);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < frames; ++f)
+            for (std::size_t j = 0; j < m; ++j) {
+                const float *b = &flat[(f * m + j) * 4];
+                out[f][j] = {std::complex<float>(b[0], b[1]), std::complex<float>(b[2], b[3])};
+            }
         return out;
     }
 

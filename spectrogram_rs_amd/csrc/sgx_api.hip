@@ -226,22 +226,25 @@ int ensure_workspace(sgx_ctx *c, size_t frames)
     return SGX_OK;
 }
 
-// `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index)
+// `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index).  `out`: magnitude pairs (sgx_stft_batch)
+// or complex rows (sgx_stft_batch_complex) -- one dispatch, so that both outputs of a context come from the same kernel family
+enum class StftOut { kMagnitudes, kComplex };
 hipError_t run_stft(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first, size_t n,
-                    size_t total, float *d_mags)
+                    size_t total, float *d_mags, StftOut out = StftOut::kMagnitudes)
 {
+    const bool cx = out == StftOut::kComplex;
     // W = 8192 (a mono stream whose frames are not paired: as an (s, s) plane through the two-channel instantiation; the 8192-point plan of
     // the mixed-radix kernel's real-input mode measured no faster, round 4)
-    if (c->stft_kernel == 10) return sgx::launch_stft_w16384(c, c->d_w16k, d_pcm, channels, pairs, first, n, total, d_mags);
+    if (c->stft_kernel == 10) return sgx::launch_stft_w16384(c, c->d_w16k, d_pcm, channels, pairs, first, n, total, d_mags, cx);
     // lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM): four-step passes through the context's scratch
-    if (c->stft_kernel == 11) return sgx::launch_stft_large(c, c->d_large, d_pcm, channels, pairs, first, n, total, d_mags);
+    if (c->stft_kernel == 11) return sgx::launch_stft_large(c, c->d_large, d_pcm, channels, pairs, first, n, total, d_mags, cx);
     // (a mono stream, every frame its own transform: real-input mode of the mixed-radix kernel, 2400 points instead of 4800 on (s, s))
-    if (c->stft_kernel == 9 && channels <= 2 && !sgx::mixed_real_serves(c, c->d_mix, channels)) return sgx::launch_stft_w4800(c, c->d_w4800, d_pcm, channels, first, n, total, d_mags, false);
-    if (c->stft_kernel == 6 || c->stft_kernel == 9) return sgx::launch_stft_mixed(c, c->d_mix, d_pcm, channels, pairs, first, n, total, d_mags);
-    if (c->stft_kernel == 4 && c->d_chz) return sgx::launch_stft_chirpz(c, c->d_chz, d_pcm, channels, pairs, first, n, total, d_mags);
-    if (c->stft_kernel == 4) return sgx::launch_stft_bluestein(c, c->d_blu, d_pcm, channels, pairs, first, n, total, d_mags);
-    if (c->stft_kernel == 2) return sgx::launch_stft_wg4096(c, c->d_fast_wg, d_pcm, channels, pairs, first, n, total, d_mags);
-    return sgx::launch_stft_generic(c, d_pcm, channels, pairs, first, n, total, d_mags);
+    if (c->stft_kernel == 9 && channels <= 2 && !sgx::mixed_real_serves(c, c->d_mix, channels)) return sgx::launch_stft_w4800(c, c->d_w4800, d_pcm, channels, first, n, total, d_mags, false, cx);
+    if (c->stft_kernel == 6 || c->stft_kernel == 9) return sgx::launch_stft_mixed(c, c->d_mix, d_pcm, channels, pairs, first, n, total, d_mags, false, cx);
+    if (c->stft_kernel == 4 && c->d_chz) return sgx::launch_stft_chirpz(c, c->d_chz, d_pcm, channels, pairs, first, n, total, d_mags, cx);
+    if (c->stft_kernel == 4) return sgx::launch_stft_bluestein(c, c->d_blu, d_pcm, channels, pairs, first, n, total, d_mags, cx);
+    if (c->stft_kernel == 2) return sgx::launch_stft_wg4096(c, c->d_fast_wg, d_pcm, channels, pairs, first, n, total, d_mags, cx);
+    return sgx::launch_stft_generic(c, d_pcm, channels, pairs, first, n, total, d_mags, cx);
 }
 
 // sgx_bands_batch's route: 1 the fused 4096-point kernels (K1 / real-input K1R), 2 the fused mixed-radix kernels, 0 two kernels.  Only the
@@ -520,6 +523,23 @@ int sgx_stft_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t firs
     SGX_HIP(c, hipSetDevice(c->device));
     hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame, n, total, d_mags);
     if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch: kernel launch");
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+int sgx_stft_batch_complex(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                           float *d_spec, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    const size_t total = sgx_num_frames(c, n_samples);
+    if (first_frame >= total || max_frames == 0) return SGX_OK;
+    size_t n = total - first_frame;
+    if (n > max_frames) n = max_frames;
+    if (!d_pcm || !d_spec) return fail(c, SGX_ERR_INVALID_ARG, "sgx_stft_batch_complex: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame, n, total, d_spec, StftOut::kComplex);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_complex: kernel launch");
     if (n_out) *n_out = n;
     return SGX_OK;
 }

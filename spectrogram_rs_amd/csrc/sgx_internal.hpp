@@ -161,12 +161,13 @@ namespace sgx {
 
 inline bool fast4096_supported(const sgx_ctx *c) { return c->W == 2048; }   // the tuned 4096-point kernels (stft4096_wg.hip)
 // kernel launchers (each returns hipSuccess or the launch error)
+// out_c64 (every STFT launcher): complex rows of sgx_stft_batch_complex, [F][pairs][M][2][2] floats, instead of the magnitude pairs
 hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                               size_t n_frames, size_t total_frames, float *d_mags);
+                               size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 hipError_t wg4096_init(sgx_ctx *c, void **out);
 void wg4096_destroy(void *tables);
 hipError_t launch_stft_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
+                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables);
 bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables);   // the fused column without the colour (sgx_bands_batch): no palette condition
 hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
@@ -183,7 +184,7 @@ bool w16384_supported(const sgx_ctx *c);
 hipError_t w16384_init(sgx_ctx *c, void **out);
 void w16384_destroy(void *tables);
 hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
+                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 // W = 2400 (48 kHz x 0.05 s): persistent 320-thread workgroups, 16 x 20 x 15 (stft4800_wg.hip); rows and half rows of one or two channels -- more
 // channels and the fused PCM-to-pixel path go to the composite-radix kernel, whose tables such a context carries too
 // stft4096_real.hip: independent mono frames at W 2048 / H 256 as 2048-point complex transforms of the real frame
@@ -194,7 +195,7 @@ bool w4800_supported(const sgx_ctx *c);
 hipError_t w4800_init(sgx_ctx *c, void **out);
 void w4800_destroy(void *tables);
 hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, size_t first_frame, size_t n_frames,
-                             size_t total_frames, float *d_mags, bool out_f16);
+                             size_t total_frames, float *d_mags, bool out_f16, bool out_c64 = false);
 bool mixed_supported(uint32_t W);
 hipError_t mixed_init(sgx_ctx *c, void **out);
 void mixed_destroy(void *tables);
@@ -206,7 +207,7 @@ hipError_t chirpz_init(sgx_ctx *c, void **out);
 void chirpz_destroy(void *tables);
 bool chirpz_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode, as mixed_real_serves
 hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
+                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables);   // one kernel from PCM to pixels at this length, palette and row table
 bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables);    // one kernel from PCM to the rows' (l, r) means at this length and row table
 hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
@@ -214,12 +215,13 @@ hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float 
 hipError_t launch_render_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
                                size_t n_frames, size_t total_frames, uint8_t *d_rgba);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
 hipError_t launch_stft_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16 = false);   // out_f16: (l, r) half pairs, 4 B per bin
+                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16 = false,
+                             bool out_c64 = false);   // out_f16: (l, r) half pairs, 4 B per bin
 bool bluestein_supported(uint32_t W);
 hipError_t bluestein_init(sgx_ctx *c, void **out);
 void bluestein_destroy(void *tables);
 hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                 size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
+                                 size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 hipError_t launch_stft_wg4096_f16(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                                   size_t first_frame, size_t n_frames, size_t total_frames, void *d_mags_f16);
 // stft_large.hip: lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM), W up to 2^20: four-step passes through a scratch the
@@ -228,7 +230,7 @@ bool large_supported(uint32_t W);
 hipError_t large_init(sgx_ctx *c, void **out);
 void large_destroy(void *tables);
 hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags);
+                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 hipError_t launch_to_half(const sgx_ctx *c, const float *d_in, void *d_out, size_t n_pairs);
 hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns, uint8_t *d_rgba);
 hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_columns, const RowEntry *d_rows,

@@ -108,9 +108,79 @@ __global__ void __launch_bounds__(1024) stft_generic_kernel(StftGenericParams p)
     }
 }
 
-hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                               size_t n_frames, size_t total_frames, float *d_mags)
+// The same transform for sgx_stft_batch_complex: the (L, R) spectra of the split, [F][pairs][M][2][2] floats, float4 per bin.  (A kernel of
+// its own: stft_generic_kernel's code is to stay exactly what it is.)
+__global__ void __launch_bounds__(1024) stft_generic_complex_kernel(StftGenericParams p)
 {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float2 *s = reinterpret_cast<float2 *>(smem_raw);
+    const uint32_t W = p.W, P = 2 * W, M = W - 1;
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    const uint32_t pair = blockIdx.y;
+    // (l, r) of one frame -- or, for a mono stream, frames 2q and 2q+1 by GLOBAL index: the split that separates left
+    // from right then separates the two frames, each is written as (m, m), and any sub-range writes the same bytes
+    long long row_a, row_b = -1;   // output rows (frames relative to first_frame); < 0 or >= n_frames: not stored
+    const float *src_a, *src_b;
+    uint32_t cl, cr;
+    bool data_b = true;
+    if (p.mono_pairs) {
+        const unsigned long long fa = 2 * (p.pair_base + blockIdx.x), fb = fa + 1;
+        row_a = (long long)fa - (long long)p.first_frame;
+        row_b = row_a + 1;
+        data_b = fb < p.total_frames;
+        src_a = p.pcm + (size_t)(fa * p.H);
+        src_b = data_b ? src_a + p.H : src_a;
+        cl = cr = 0;
+    } else {
+        row_a = (long long)blockIdx.x;
+        src_a = src_b = p.pcm + (size_t)((p.first_frame + blockIdx.x) * p.H) * p.C;
+        cl = p.C == 1 ? 0 : 2 * pair;
+        cr = p.C == 1 ? 0 : 2 * pair + 1;
+    }
+
+    for (uint32_t n = tid; n < W; n += nt) {
+        const float w = p.window[n];
+        const float l = src_a[(size_t)n * p.C + cl];
+        const float r = data_b ? src_b[(size_t)n * p.C + cr] : 0.0f;
+        const float2 z = make_float2(l * w, r * w);  // complex * real, fft.rs:59-63
+        s[n] = z;
+        s[n + W] = cmul(z, p.twiddle[n]);
+    }
+    __syncthreads();
+
+    // the two halves are independent length-W transforms now (even bins / odd bins): radix-4 stages in place
+    // (lds_fft.hpp), each half's result in digit-reversed order
+    if (p.logP >= 2) ldsfft::forward_dif(s, p.logP, p.logP - 1, p.twiddle, p.logP, tid, nt);
+
+    // fft.rs:81-98 before the magnitude: a = F[k], b = F[P - k]; L = (a + conj b) / 2, R = (a - conj b) / (2i) -- the difference rotated
+    // by -90 degrees -- each times 2 / W.  Mono frame pairs: (X, X) rows of frames 2q (L) and 2q+1 (R)
+    const bool st_a = row_a >= 0 && (unsigned long long)row_a < p.n_frames;
+    const bool st_b = p.mono_pairs && row_b >= 0 && (unsigned long long)row_b < p.n_frames;
+    float4 *out_a = reinterpret_cast<float4 *>(p.mags) + ((size_t)(st_a ? row_a : 0) * p.pairs + pair) * M;
+    float4 *out_b = reinterpret_cast<float4 *>(p.mags) + ((size_t)(st_b ? row_b : 0) * p.pairs + pair) * M;
+    // bin k: half k & 1 (the pruned first stage), then the digit-reversed position of k >> 1 inside it
+    const uint32_t logW = p.logP - 1;
+    for (uint32_t j = tid; j < M; j += nt) {
+        const uint32_t k = j + 1, kp = P - k;
+        const float2 a = s[(k & 1u) * W + ldsfft::pos_of(k >> 1, logW)];
+        const float2 b = s[(kp & 1u) * W + ldsfft::pos_of(kp >> 1, logW)];
+        const float sre = a.x + b.x, sim = a.y - b.y;
+        const float dre = a.x - b.x, dim = a.y + b.y;
+        const float lr = sre * 0.5f * p.scale, li = sim * 0.5f * p.scale;
+        const float rr = dim * 0.5f * p.scale, ri = -dre * 0.5f * p.scale;
+        if (p.mono_pairs) {
+            if (st_a) out_a[j] = make_float4(lr, li, lr, li);
+            if (st_b) out_b[j] = make_float4(rr, ri, rr, ri);
+        } else {
+            out_a[j] = make_float4(lr, li, rr, ri);
+        }
+    }
+}
+
+hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
+                               size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
+{
+    const auto kernel = out_c64 ? stft_generic_complex_kernel : stft_generic_kernel;
     if (n_frames == 0) return hipSuccess;
     StftGenericParams p{};
     p.pcm = d_pcm;
@@ -130,7 +200,7 @@ hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t ch
     // stage for short transforms, 16 waves per CU where the LDS image limits residency (2 x 512 at 8192, 1 x 1024 at 16384)
     const unsigned threads = c->P >= 16384 ? 1024u : (c->P >= 8192 ? 512u : (c->P >= 2048 ? 256u : (c->P >= 1024 ? 128u : 64u)));
     if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(stft_generic_kernel),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
@@ -145,7 +215,7 @@ hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t ch
         for (unsigned long long q = q0; q < q1; q += max_chunk) {
             const unsigned long long chunk = q1 - q < max_chunk ? q1 - q : max_chunk;
             p.pair_base = q;
-            hipLaunchKernelGGL(stft_generic_kernel, dim3((unsigned)chunk, 1), dim3(threads), lds, c->stream, p);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)chunk, 1), dim3(threads), lds, c->stream, p);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
@@ -159,8 +229,8 @@ hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t ch
         StftGenericParams q = p;
         q.first_frame = first_frame + done;
         q.n_frames = chunk;
-        q.mags = d_mags + done * (size_t)pairs * c->M * 2;
-        hipLaunchKernelGGL(stft_generic_kernel, dim3((unsigned)chunk, pairs), dim3(threads), lds, c->stream, q);
+        q.mags = d_mags + done * (size_t)pairs * c->M * (out_c64 ? 4 : 2);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunk, pairs), dim3(threads), lds, c->stream, q);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         done += chunk;

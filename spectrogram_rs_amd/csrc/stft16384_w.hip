@@ -37,7 +37,13 @@
 
 namespace sgx {
 
-namespace w16k {
+// SGX_W16K_C64 1: the complex-row instantiations of sgx_stft_batch_complex (stft16384_w_complex.hip takes this file's device code into a
+// namespace of its own: the kernels here are to stay exactly what they are)
+#ifndef SGX_W16K_C64
+#define SGX_W16K_C64 0
+#define SGX_W16K_NS w16k
+#endif
+namespace SGX_W16K_NS {
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float cl_fma(float a, float c, float u) { return fmaf(a, c, u); }
@@ -134,6 +140,7 @@ __device__ unsigned long long g_phase_cycles16w[24];
 #define SGX_STAMP(i)
 #endif
 
+#if !SGX_W16K_C64   // (the complex-row translation unit launches its kernels on this file's plane: no second copy)
 // a mono sample range as one (s, s) plane: what the reference's capture callback does to a mono device (audio_input_list_model.rs:67-69)
 __global__ void __launch_bounds__(256) duplicate_mono_kernel(const float *pcm, float *plane, size_t first, size_t n)
 {
@@ -142,6 +149,7 @@ __global__ void __launch_bounds__(256) duplicate_mono_kernel(const float *pcm, f
         reinterpret_cast<float2 *>(plane)[i] = make_float2(s, s);
     }
 }
+#endif
 
 // MONO: SGX_FLAG_PAIRED_FRAMES -- frames 2j and 2j + 1 of a mono stream in the real and the imaginary part of one transform.
 // DIRECT: more than two interleaved channels, pair p = channels (2 p, 2 p + 1), read where they lie: 8-byte loads at a stride of C floats
@@ -153,6 +161,7 @@ __global__ void __launch_bounds__(256) duplicate_mono_kernel(const float *pcm, f
 template <bool MONO, bool DIRECT = false, bool SLIDE = false>
 __global__ void __launch_bounds__(512, 2) stft16384_w_kernel(Params p)
 {
+    constexpr bool C64 = SGX_W16K_C64 != 0;   // complex rows, (L, R) as 16 bytes per bin, stored by pass 3 itself (no pending row)
     static_assert(!(MONO && SLIDE), "frame pairs of a mono stream do not slide");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf = reinterpret_cast<float2 *>(smem_raw);
@@ -295,7 +304,7 @@ __global__ void __launch_bounds__(512, 2) stft16384_w_kernel(Params p)
     for (int i = 0; i < 32; ++i) pm[i] = 0.0f;
     __amdgpu_buffer_rsrc_t pend0 = uniform_rsrc(p.mags, 0u), pend1 = uniform_rsrc(p.mags, 0u);
     auto store_bin = [&](float ml, float mr, const __amdgpu_buffer_rsrc_t &r0, const __amdgpu_buffer_rsrc_t &r1, int voff, int soff) {
-        if (!W_STORE_OK(ml)) return;
+        if (C64 || !W_STORE_OK(ml)) return;
         if (MONO) {   // (ml, mr) = the bin of frames 2j and 2j + 1: each row holds (s, s) pairs (audio_input_list_model.rs:67-69)
             __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(ml), __float_as_uint(ml)}, r0, voff, soff, W_OUT_AUX);
             __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(mr), __float_as_uint(mr)}, r1, voff, soff, W_OUT_AUX);
@@ -347,6 +356,30 @@ __global__ void __launch_bounds__(512, 2) stft16384_w_kernel(Params p)
         // last at every barrier.  Its u = 0 bins ride one store instruction early (bin q3 + 1 in the slot of q3, lane offset 8184 =
         // 8192 - 8: a lane offset of -8 would be dropped, profiles/r05_bufrange.txt); instruction 7 drops its lane.
         const bool z = tid == 0;
+        if constexpr (C64) {
+            // L = (a + conj b) / 2, R = (a - conj b) / (2i) = (di, -dr) / 2, the scale 2 / W on the window; bin k at byte 16 (k - 1) of the row,
+            // thread 0's u = 0 bins one store early as above (16368 = 16384 - 16), its store of j = 7 dropped
+            const int cA = z ? 16368 : 16 * (uA - 1), cA7 = z ? (int)0x7ffffff0 : 16 * (uA - 1), cB = 16 * (uB - 1);
+            auto cstore = [&](float xr_, float xi_, float yr_, float yi_, int voff, int soff) {
+                const float sr_ = xr_ + yr_, si_ = xi_ - yi_;
+                const float dr_ = xr_ - yr_, di_ = xi_ + yi_;
+                if (MONO) {   // frames 2j (L) and 2j + 1 (R): (X, X) rows
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(sr_), __float_as_uint(si_), __float_as_uint(sr_), __float_as_uint(si_)}, row0, voff + soff, 0, W_OUT_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(di_), __float_as_uint(-dr_), __float_as_uint(di_), __float_as_uint(-dr_)}, row1, voff + soff, 0, W_OUT_AUX);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(sr_), __float_as_uint(si_), __float_as_uint(di_), __float_as_uint(-dr_)}, row0, voff + soff, 0, W_OUT_AUX);
+                }
+            };
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int pa = FFT16_OUT[j], pa1 = FFT16_OUT[j < 7 ? j + 1 : j], pb = FFT16_OUT[15 - j];
+                cstore(z ? ar[pa1] : ar[pa], z ? ai[pa1] : ai[pa], z ? ar[pb] : br[pb], z ? ai[pb] : bi[pb], j == 7 ? cA7 : cA, 16384 * j);
+                cstore(br[pa], bi[pa], z ? br[pb] : ar[pb], z ? bi[pb] : ai[pb], cB, 16384 * j);
+            }
+            pend0 = row0;
+            pend1 = row1;
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int pa = FFT16_OUT[j], pa1 = FFT16_OUT[j < 7 ? j + 1 : j], pb = FFT16_OUT[15 - j];
@@ -514,8 +547,8 @@ __global__ void __launch_bounds__(512, 2) stft16384_w_kernel(Params p)
         SGX_STAMP(6)
 
         // ---- pass 3 (the lambdas in front of the loop): this transform's words; kDefer3: their arithmetic in the next iteration
-        row0 = uniform_rsrc(p.mags + (((size_t)(have_first ? f0 : 0) * p.pairs + pair) * (size_t)kM) * 2, (MONO && !have_first) ? 0u : 0x7fffffffu);
-        row1 = uniform_rsrc(p.mags + (((size_t)f1 * p.pairs + pair) * (size_t)kM) * 2, (MONO && !have_second) ? 0u : 0x7fffffffu);
+        row0 = uniform_rsrc(p.mags + (((size_t)(have_first ? f0 : 0) * p.pairs + pair) * (size_t)kM) * (C64 ? 4 : 2), (MONO && !have_first) ? 0u : 0x7fffffffu);
+        row1 = uniform_rsrc(p.mags + (((size_t)f1 * p.pairs + pair) * (size_t)kM) * (C64 ? 4 : 2), (MONO && !have_second) ? 0u : 0x7fffffffu);
         p3_read();
         if constexpr (!kDefer3) p3_finish();
         SGX_STAMP(8)    // pass 3
@@ -544,7 +577,8 @@ struct TablesW {
     size_t planes_floats = 0;
 };
 
-}  // namespace w16k
+}  // namespace SGX_W16K_NS
+#ifndef SGX_W16K_KERNELS_ONLY
 
 #if SGX_STAMPS
 extern "C" __attribute__((visibility("default"))) int sgx_debug_phase_cycles16w(unsigned long long *h_out, int reset)
@@ -625,8 +659,11 @@ void w16384_destroy(void *tables)
     delete t;
 }
 
+// stft16384_w_complex.hip: the complex-row kernels, launched on this file's parameter block (the same struct there)
+hipError_t launch_w16384_complex(const void *params, size_t params_size, bool mono, bool slide, bool direct, dim3 grid, hipStream_t stream);
+
 hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags)
+                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
 {
     using namespace w16k;
     if (n_frames == 0) return hipSuccess;
@@ -692,6 +729,7 @@ hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm
         p.xcds = blocks % kXcdHint == 0 ? kXcdHint : 1u;
     }
     const dim3 grid((unsigned)blocks), block(512);
+    if (out_c64) return launch_w16384_complex(&p, sizeof p, mono, slide, direct, grid, c->stream);   // stft16384_w_complex.hip
     if (mono) hipLaunchKernelGGL((stft16384_w_kernel<true>), grid, block, kLdsBytes, c->stream, p);
     else if (slide && direct) hipLaunchKernelGGL((stft16384_w_kernel<false, true, true>), grid, block, kLdsBytes, c->stream, p);
     else if (slide) hipLaunchKernelGGL((stft16384_w_kernel<false, false, true>), grid, block, kLdsBytes, c->stream, p);
@@ -699,5 +737,7 @@ hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm
     else hipLaunchKernelGGL((stft16384_w_kernel<false>), grid, block, kLdsBytes, c->stream, p);
     return hipGetLastError();
 }
+
+#endif  // SGX_W16K_KERNELS_ONLY
 
 }  // namespace sgx

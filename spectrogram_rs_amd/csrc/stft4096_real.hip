@@ -57,6 +57,7 @@ using wg::lds_cfloat2;
 using wg::lds_ptr;
 using wg::pcm_rsrc;
 using wg::u32x2;
+using wg::u32x4;
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float cl_fma(float a, float c, float u) { return fmaf(a, c, u); }
@@ -104,6 +105,7 @@ __device__ __forceinline__ void fft8_half_zero(const float (&zr)[4], const float
 
 constexpr int kRowsF32 = 0, kRowsF16 = 1, kPixels = 2;   // what a launch writes: float rows, half-pair rows, RGBA columns (fused pixel path)
 constexpr int kBands = 3;   // the fused column's (l, r) row means as float2, no colour (sgx_bands_batch; PIX wg::kPixBandsCubic / kPixBandsCosine)
+constexpr int kRowsC64 = 4;   // complex rows (sgx_stft_batch_complex): (S, S) per bin, 16 bytes, every bin pair stored as soon as it is untangled
 
 // PIX (kPixels only): the pixel code of the instantiation, wg::kPixCubic / kPixCosine / kPixGeneric (stft4096_wg.hpp)
 // SLIDE: H = 256, the window slides in registers (above).  Else: any hop (a frame starts on any sample): the eight columns of the
@@ -172,6 +174,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     float2 *tw2 = buf + (TR ? kBufComplexTR : kBufComplex);
     uint2 *pal = reinterpret_cast<uint2 *>(tw2 + 256);          // kPixels only: [256] {threshold, RGBA} (wg::pixel_for)
     constexpr bool F16 = MODE == kRowsF16;
+    constexpr bool C64 = MODE == kRowsC64;
     constexpr bool FUSED = MODE == kPixels || MODE == kBands;  // the column goes through LDS to the pixel passes
 
     const int tid = threadIdx.x;
@@ -269,7 +272,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     float2 *xch = buf + 2304;         // [256] the iteration's loads, beside the partner rows (image 2 is dead by then)
 
     char *out = reinterpret_cast<char *>(p.mags);
-    constexpr int kBin = F16 ? 4 : 8;             // bytes per output bin
+    constexpr int kBin = C64 ? 16 : (F16 ? 4 : 8);   // bytes per output bin
 #if SGX_STAMPS
     unsigned long long st_acc[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long st_last = __builtin_readcyclecounter();
@@ -404,7 +407,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
         float m1[8], m2[8];
         // rows: every bin pair is stored as soon as it is computed (SGX_K1R_INTERLEAVE; stft4096_wg.hip does the same for (l, r) rows):
         // sixteen stores spread over the untangle instead of one burst behind it
-        constexpr bool kInterleave = !FUSED && SLIDE && SGX_K1R_INTERLEAVE;   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
+        constexpr bool kInterleave = (!FUSED && SLIDE && SGX_K1R_INTERLEAVE) || C64;   // (C64: at any hop -- four arrays of eight would stay live otherwise)   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
         const long long row = (long long)(F == 0 ? la : lb) * (long long)kM * kBin - kBin;      // byte of the (absent) bin 0
         const __amdgpu_buffer_rsrc_t r = out_rsrc(out, !FUSED ? row : 0, !FUSED && (F == 0 || have_b));
         const int l1 = kBin * u, l2 = kBin * (1152 - u);                                        // bins u + 128 q3 ; 2048 - u - 128 q3 = (1152 - u) + 128 (7 - q3)
@@ -443,6 +446,17 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             const float orr = zi_ + pv.y, oi = pv.x - zr_;    // -i (Z - conj P) = 2 O
             const float wr = fmaf(twu[q3].x, orr, -(twu[q3].y * oi)), wi = fmaf(twu[q3].x, oi, twu[q3].y * orr);
             const float ar = er + wr, ai = ei + wi, br = er - wr, bi = ei - wi;
+            if constexpr (C64) {
+                // S[k] = (ar, ai) and S[2048 - k] = conj(br + i bi), both already times 2 / W; thread 0's q3 = 0 slot: bin 1024 twice
+                const bool self = q3 == 0 && u == 0;
+                const float cr2 = self ? ar : br, ci2 = self ? ai : -bi;
+                const int o1 = self ? kBin * 1024 : l1, o2 = self ? kBin * 128 : l2;
+                const int s1 = kBin * 128 * q3, s2 = kBin * 128 * (7 - q3);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(ar), __float_as_uint(ai), __float_as_uint(ar), __float_as_uint(ai)}, r, o1 + s1, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cr2), __float_as_uint(ci2), __float_as_uint(cr2), __float_as_uint(ci2)}, r, o2 + s2, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                continue;
+            }
             m1[q3] = __builtin_amdgcn_sqrtf(fmaf(ar, ar, ai * ai));   // |S[k]| 2 / W      (the scale rides on the window)
             m2[q3] = __builtin_amdgcn_sqrtf(fmaf(br, br, bi * bi));   // |S[2048 - k]| 2 / W
             if (kInterleave) {
@@ -606,7 +620,7 @@ namespace wg {
 
 // p: as launch_wg (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
 // transform's own tables and the job split are set here
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands)
+hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands, bool out_c64)
 {
     using namespace wgr;
     if (p.n_frames == 0) return hipSuccess;
@@ -632,6 +646,8 @@ hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, 
             if (!p.seed_pm1) hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixGeneric, S_>), grid, block, lds_render, c->stream, p);
             else if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixCosine, S_>), grid, block, lds_render, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixCubic, S_>), grid, block, lds_render, c->stream, p);
+        } else if (out_c64) {
+            hipLaunchKernelGGL((stft4096_real_kernel<kRowsC64, kPixNone, S_>), grid, block, lds_rows, c->stream, p);
         } else if (out_f16) {
             hipLaunchKernelGGL((stft4096_real_kernel<kRowsF16, kPixNone, S_>), grid, block, lds_rows, c->stream, p);
         } else {

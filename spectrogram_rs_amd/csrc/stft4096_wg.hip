@@ -99,7 +99,8 @@ __device__ __forceinline__ void read_planes(const float4 *rd4, float (&xr)[16], 
 template <bool MONO, int PAIRING, bool C2, int PIX>
 __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
 {
-    constexpr bool RENDER = PIX != kPixNone && PIX != kPixRowsF16;   // the fused column: pixels, or (BANDS) its float means
+    constexpr bool C64 = PIX == kPixRowsC64;    // complex rows, (L, R) per bin (sgx_stft_batch_complex), stored inside the split
+    constexpr bool RENDER = PIX != kPixNone && PIX != kPixRowsF16 && !C64;   // the fused column: pixels, or (BANDS) its float means
     constexpr bool BANDS = pix_bands(PIX);
     constexpr bool F16 = PIX == kPixRowsF16;    // rows as (l, r) half pairs (compile-time: the row stores are straight-line code)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -426,7 +427,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         // (l, r) rows: every segment is stored as soon as it is computed -- eight stores spread over the split instead of one burst of eight
         // behind it (a wave stalls at the issue of a store while the CU's vector-memory path drains the previous ones: 1 083 cycles per
         // transform for the burst, profiles/r05_k1_stereo.txt; same device 5.10 -> 4.87 ms per 1e6 frames together with the sliding window)
-        constexpr bool kInterleave = !MONO && !RENDER;
+        constexpr bool kInterleave = (!MONO && !RENDER) || C64;   // (C64: a frame pair's two rows too, sixteen stores as the burst has)
         float2 pb[8] = {};
         if (kInterleave) {
 #pragma unroll
@@ -444,7 +445,14 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
 #else
         const long long f0_il = f0;
 #endif
-        const __amdgpu_buffer_rsrc_t r_il = row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)f0_il * p.pairs + p.pair) * ((size_t)kM * (F16 ? 4 : 8))) - (F16 ? 4 : 8));
+        constexpr int kRowBin = C64 ? 16 : (F16 ? 4 : 8);   // bytes per output bin
+        // (C64 frame pairs: r_il / r_il2 are the rows of frames f0 / f1, each dropped when outside the requested range)
+        const __amdgpu_buffer_rsrc_t r_il = (C64 && MONO)
+            ? row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin, have_first)
+            : row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)f0_il * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin);
+        const __amdgpu_buffer_rsrc_t r_il2 = (C64 && MONO)
+            ? row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)f1 * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin, have_second)
+            : r_il;
 #pragma unroll
         for (int q3 = 0; q3 < 8; ++q3) {
             const int pos = FFT16_OUT[q3];
@@ -453,6 +461,19 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
             const float ar = xr[pos], ai = xi[pos];
             const float pr = ar + b.x, pi = ai - b.y;   // a + conj(b) = 2 L^
             const float qr = ar - b.x, qi = ai + b.y;   // a - conj(b) = 2i R^
+            if constexpr (C64) {
+                // L = (a + conj b) / 2 and R = (a - conj b) / (2i) = (qi, -qr) / 2, times 2 / W: the scale rides on the window.  Bin k =
+                // col + 256 q3 at byte 16 k of the row; k = 0 (DC) is not an output: thread 0's first stores fall outside the records
+                const int off = (q3 == 0 && col == 0) ? (int)0x80000000 : col * 16;
+                if (MONO) {   // frames f0 and f1 of the pair: (X, X) rows
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(pr), __float_as_uint(pi), __float_as_uint(pr), __float_as_uint(pi)}, r_il, off + 4096 * q3, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(qi), __float_as_uint(-qr), __float_as_uint(qi), __float_as_uint(-qr)}, r_il2, off + 4096 * q3, 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(pr), __float_as_uint(pi), __float_as_uint(qi), __float_as_uint(-qr)}, r_il, off + 4096 * q3, 0, kAuxNt);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                continue;
+            }
             ml[q3] = __builtin_amdgcn_sqrtf(fmaf(pr, pr, pi * pi));  // already scaled by 1 / W (see `win`)
             mr[q3] = __builtin_amdgcn_sqrtf(fmaf(qr, qr, qi * qi));
             if (kInterleave) {
@@ -479,7 +500,9 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         // the head of the next transform waited for the pixel stores just issued to be acknowledged by memory)
         issued_since = RENDER ? (p.n_samples >> 8) + (p.R >> 8) * ((have_first ? 1u : 0u) + ((MONO && have_second) ? 1u : 0u))
                               : (MONO ? 16u : 8u);    // rows: eight store instructions per row in every wave, absent rows included (dropped by their descriptor)
-        if (!RENDER) {
+        if (C64) {
+            // (complex rows: stored inside the split)
+        } else if (!RENDER) {
             // ---- store [F][pairs][M][2]: uniform row base (SGPR) + one 32-bit lane offset
             if (F16) {
                 char *base = reinterpret_cast<char *>(p.mags);
@@ -715,7 +738,7 @@ namespace {
 template <bool RENDER>
 hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                      size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, uint8_t *d_rgba, bool out_f16 = false,
-                     bool bands = false)
+                     bool bands = false, bool out_c64 = false)
 {
     using namespace wg;
     if (n_frames == 0) return hipSuccess;
@@ -785,7 +808,7 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         const uint32_t fl = c->cfg.flags;      // (sgx_create: INDEPENDENT is set unless PAIRED was asked for)
         const bool own_transform = !(fl & SGX_FLAG_PAIRED_FRAMES) || (fl & SGX_FLAG_COMPLEX_MONO) != 0;
         if (channels == 1 && own_transform && !(fl & SGX_FLAG_COMPLEX_MONO) && real4096_serves(c, d_pcm, channels))
-            return launch_real4096(c, c->d_real, p, out_f16, RENDER, bands);
+            return launch_real4096(c, c->d_real, p, out_f16, RENDER, bands, out_c64);
         const bool mono = channels == 1 && (fl & SGX_FLAG_PAIRED_FRAMES) && !(fl & SGX_FLAG_COMPLEX_MONO);
         p.pair_base = mono ? first_frame / 2 : 0;
         p.n_jobs = mono ? (first_frame + n_frames + 1) / 2 - first_frame / 2 : n_frames;
@@ -805,7 +828,8 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         auto launch = [&](auto mono_c, auto pairing_c, auto c2_c) {
             constexpr bool M_ = decltype(mono_c)::value, C2_ = decltype(c2_c)::value;
             constexpr int P_ = decltype(pairing_c)::value;
-            if (!RENDER && out_f16) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixRowsF16>), grid, block, lds, c->stream, p);
+            if (!RENDER && out_c64) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixNone : kPixRowsC64>), grid, block, lds, c->stream, p);
+            else if (!RENDER && out_f16) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixRowsF16>), grid, block, lds, c->stream, p);
             else if (!RENDER) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixNone>), grid, block, lds, c->stream, p);
             else if (pix == kPixBandsCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCubic : kPixNone>), grid, block, lds, c->stream, p);
             else if (pix == kPixBandsCosine) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCosine : kPixNone>), grid, block, lds, c->stream, p);
@@ -836,9 +860,9 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
 }  // namespace
 
 hipError_t launch_stft_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags)
+                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
 {
-    return launch_wg<false>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, d_mags, nullptr);
+    return launch_wg<false>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, d_mags, nullptr, false, false, out_c64);
 }
 
 hipError_t launch_stft_wg4096_f16(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,

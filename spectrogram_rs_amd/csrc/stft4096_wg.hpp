@@ -60,7 +60,8 @@ struct Params {
 };
 
 // stft4096_real.hip
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands = false);
+hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands = false,
+                          bool out_c64 = false);   // out_c64: complex rows (sgx_stft_batch_complex)
 
 // Which two mono frames share a transform: always (2j, 2j+1).
 //   kPairAdjacentRow : H = 256: frame 2j+1's rows are frame 2j's rows shifted by one (9 rows feed both)
@@ -119,6 +120,7 @@ __device__ __forceinline__ float2 lds_read_alone(lds_cfloat2 *&base, int idx)
 // one row of [M][2] floats; rowm8 = row base - 8 bytes (bin k lives at byte 8 k of rowm8): a uniform
 // (SGPR) row base plus one 32-bit lane offset, immediate offsets per segment
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // A raw buffer descriptor over one output row: base = the row's bin-0 address (uniform), no stride, no bounds
 // in the way (2 GB window).  Stores through it take an SGPR descriptor + one 32-bit lane offset + a scalar
@@ -197,6 +199,8 @@ constexpr int kPixNone = 0, kPixCubic = 1, kPixCosine = 2, kPixGeneric = 3, kPix
 // the fused column without the colour (sgx_bands_batch): the row pass stores the (l, r) means as float2, lowest row first; no palette
 constexpr int kPixBandsCubic = 5, kPixBandsCosine = 6;
 constexpr bool pix_bands(int pix) { return pix == kPixBandsCubic || pix == kPixBandsCosine; }
+// no pixels: the complex rows of sgx_stft_batch_complex, (L, R) as 16 bytes per bin, stored inside the split (stft4096_wg.hip)
+constexpr int kPixRowsC64 = 7;
 //   // kPixGeneric: interpolator at run time, LUT seed + walk (SGX_FLAG_LUT_WALK / proof failed)
 
 // (The repeats are written by the ONE thread that holds bin 1 / bin 2047, in the one unrolled step where it does -- a test of the

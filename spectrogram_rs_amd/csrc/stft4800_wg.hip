@@ -89,9 +89,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void *base)
 #ifndef W48_ABL
 #define W48_ABL 0   // ablation builds (profiles/r03_app_point.txt): 1 no row stores, 2 no sample loads, 4 / 8 no butterfly in pass 2 / 3
 #endif
-template <int MODE, bool F16>
+// MODE_X 4 + MODE: the complex rows of sgx_stft_batch_complex, (L, R) as float4 per bin (F16 false)
+template <int MODE_X, bool F16>
 __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4))) stft4800_wg_kernel(Params p)
 {
+    constexpr int MODE = MODE_X & 3;
+    constexpr bool C64 = MODE_X >= 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf = reinterpret_cast<float2 *>(smem_raw);
     float2 *tw2 = buf + kBuf;
@@ -262,6 +265,7 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         // eight stores spread over the split instead of a burst of eight behind it -- a wave stalls at the issue of a store while the
         // CU's vector-memory path drains the previous ones (profiles/r05_k1_stereo.txt; W48_BURST restores the burst for A/B).
         float ml[8], mr[8];
+        float cl[8], cr[8];   // C64: the imaginary parts beside ml / mr, which then hold the real parts of L and R
         float2 pb[8];
 #pragma unroll
         for (int q3 = 0; q3 < 8; ++q3) {
@@ -279,7 +283,7 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         //     raw buffer store a negative one is ~4 GiB: dropped by the range check today, a stray write if that ever changed);
         //   * a mono pair whose first or second frame lies outside the requested range stores the other row twice.
         char *base = reinterpret_cast<char *>(p.mags);
-        const int bin_bytes = F16 ? 4 : 8;
+        const int bin_bytes = C64 ? 16 : (F16 ? 4 : 8);
         const bool sa = have_first, sb = MODE == 1 ? have_second : false;
         const long long fa = sa ? f0 : f1, fb = sb ? f1 : f0;            // (row, values) of the two stores of a mono pair
         const __amdgpu_buffer_rsrc_t ra = uniform_rsrc(base + ((long long)((size_t)fa * p.pairs * (size_t)kM) - 1 - kT) * bin_bytes);
@@ -290,10 +294,29 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
             const float ar = y[q3].x, ai = y[q3].y;
             const float sr_ = ar + b.x, si_ = ai - b.y;   // a + conj(b) = 2 L^
             const float dr_ = ar - b.x, di_ = ai + b.y;   // a - conj(b) = 2i R^
+            if constexpr (C64) {   // L = (a + conj b) / 2, R = (a - conj b) / (2i) = (di, -dr) / 2; half_scale is not a power of two: each component once
+                ml[q3] = sr_ * p.half_scale; cl[q3] = si_ * p.half_scale;
+                mr[q3] = di_ * p.half_scale; cr[q3] = -dr_ * p.half_scale;
+                return;
+            }
             ml[q3] = __builtin_amdgcn_sqrtf(fmaf(sr_, sr_, si_ * si_)) * p.half_scale;
             mr[q3] = __builtin_amdgcn_sqrtf(fmaf(dr_, dr_, di_ * di_)) * p.half_scale;
         };
         auto store = [&](const int q3) {
+            if constexpr (C64) {
+                float lr = ml[q3], li = cl[q3], rr = mr[q3], ri = cr[q3];
+                int lane_off = bin_bytes * (tid + kT);
+                if (q3 == 0) { lr = drop0 ? ml[1] : lr; li = drop0 ? cl[1] : li; rr = drop0 ? mr[1] : rr; ri = drop0 ? cr[1] : ri; lane_off = drop0 ? bin_bytes * 2 * kT : lane_off; }
+                if (q3 == 7) { lr = drop7 ? ml[6] : lr; li = drop7 ? cl[6] : li; rr = drop7 ? mr[6] : rr; ri = drop7 ? cr[6] : ri; lane_off = drop7 ? bin_bytes * tid : lane_off; }
+                if (MODE == 1) {   // frame pair: (L, L) to row a, (R, R) to row b; an absent frame's row gets the other one twice
+                    const float ar_ = sa ? lr : rr, ai_ = sa ? li : ri, br_ = sb ? rr : lr, bi_ = sb ? ri : li;
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(ar_), __float_as_uint(ai_), __float_as_uint(ar_), __float_as_uint(ai_)}, ra, lane_off + bin_bytes * kT * q3, 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(br_), __float_as_uint(bi_), __float_as_uint(br_), __float_as_uint(bi_)}, rb, lane_off + bin_bytes * kT * q3, 0, 2);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(lr), __float_as_uint(li), __float_as_uint(rr), __float_as_uint(ri)}, ra, lane_off + bin_bytes * kT * q3, 0, 2);
+                }
+                return;
+            }
             float l = ml[q3], r = mr[q3];
             if ((W48_ABL & 1) && l != -12345.0f) return;
             int lane_off = bin_bytes * (tid + kT);
@@ -381,7 +404,7 @@ void w4800_destroy(void *tables)
 }
 
 hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, size_t first_frame, size_t n_frames,
-                               size_t total_frames, float *d_mags, bool out_f16)
+                               size_t total_frames, float *d_mags, bool out_f16, bool out_c64)
 {
     using namespace w48;
     if (n_frames == 0) return hipSuccess;
@@ -411,7 +434,8 @@ hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *
     const dim3 grid((unsigned)blocks), block(kT);
 #define W48_GO(MODE_) \
     do { \
-        if (out_f16) hipLaunchKernelGGL((stft4800_wg_kernel<MODE_, true>), grid, block, kLdsBytes, c->stream, p); \
+        if (out_c64) hipLaunchKernelGGL((stft4800_wg_kernel<4 + MODE_, false>), grid, block, kLdsBytes, c->stream, p); \
+        else if (out_f16) hipLaunchKernelGGL((stft4800_wg_kernel<MODE_, true>), grid, block, kLdsBytes, c->stream, p); \
         else hipLaunchKernelGGL((stft4800_wg_kernel<MODE_, false>), grid, block, kLdsBytes, c->stream, p); \
     } while (0)
     if (mode == 0) W48_GO(0);

@@ -50,7 +50,9 @@ __device__ __forceinline__ float2 cmul_conj(float2 a, float2 b)  // a * conj(b)
     return make_float2(fmaf(a.x, b.x, a.y * b.y), fmaf(a.y, b.x, -(a.x * b.y)));
 }
 
-__global__ void __launch_bounds__(1024) stft_bluestein_kernel(Params p)
+// C64: the complex rows of sgx_stft_batch_complex, (L, R) as float4 per bin (else the magnitude pairs)
+template <bool C64>
+__device__ __forceinline__ void stft_bluestein_body(Params p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *s = reinterpret_cast<float2 *>(smem_raw);
@@ -111,6 +113,20 @@ __global__ void __launch_bounds__(1024) stft_bluestein_kernel(Params p)
         const float2 b = cmul(s[P - k], p.chirp[P - k]);
         const float sre = a.x + b.x, sim = a.y - b.y;
         const float dre = a.x - b.x, dim = a.y + b.y;
+        if constexpr (C64) {
+            // L = (a + conj b) / 2, R = (a - conj b) / (2i): the difference rotated by -90 degrees, each times 2 / W
+            float4 *cx_a = reinterpret_cast<float4 *>(p.mags) + ((size_t)(st_a ? row_a : 0) * p.pairs + pair) * M;
+            float4 *cx_b = reinterpret_cast<float4 *>(p.mags) + ((size_t)(st_b ? row_b : 0) * p.pairs + pair) * M;
+            const float lr = sre * 0.5f * p.scale, li = sim * 0.5f * p.scale;
+            const float rr = dim * 0.5f * p.scale, ri = -dre * 0.5f * p.scale;
+            if (p.mono_pairs) {
+                if (st_a) cx_a[j] = make_float4(lr, li, lr, li);
+                if (st_b) cx_b[j] = make_float4(rr, ri, rr, ri);
+            } else {
+                cx_a[j] = make_float4(lr, li, rr, ri);
+            }
+            continue;
+        }
         const float left = sqrtf(fmaf(sre, sre, sim * sim)) * 0.5f * p.scale;
         const float right = sqrtf(fmaf(dre, dre, dim * dim)) * 0.5f * p.scale;
         if (p.mono_pairs) {
@@ -121,6 +137,9 @@ __global__ void __launch_bounds__(1024) stft_bluestein_kernel(Params p)
         }
     }
 }
+
+__global__ void __launch_bounds__(1024) stft_bluestein_kernel(Params p) { stft_bluestein_body<false>(p); }
+__global__ void __launch_bounds__(1024) stft_bluestein_complex_kernel(Params p) { stft_bluestein_body<true>(p); }
 
 // host float64 radix-2 FFT (table set-up only)
 static void fft_host(std::vector<double> &re, std::vector<double> &im)
@@ -215,9 +234,10 @@ void bluestein_destroy(void *tables)
 }
 
 hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                 size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags)
+                                 size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
 {
     using namespace blu;
+    const auto kernel = out_c64 ? stft_bluestein_complex_kernel : stft_bluestein_kernel;
     if (n_frames == 0) return hipSuccess;
     const auto *t = static_cast<const BluTables *>(tables);
     Params p{};
@@ -249,7 +269,7 @@ hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const flo
         for (unsigned long long q = q0; q < q1; q += max_chunk) {
             const unsigned long long chunk = q1 - q < max_chunk ? q1 - q : max_chunk;
             p.pair_base = q;
-            hipLaunchKernelGGL(stft_bluestein_kernel, dim3((unsigned)chunk, 1), dim3(threads), lds, c->stream, p);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)chunk, 1), dim3(threads), lds, c->stream, p);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }
@@ -259,8 +279,8 @@ hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const flo
         const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
         p.first_frame = first_frame + done;
         p.n_frames = chunk;
-        p.mags = d_mags + done * (size_t)pairs * c->M * 2;
-        hipLaunchKernelGGL(stft_bluestein_kernel, dim3((unsigned)chunk, pairs), dim3(threads), lds, c->stream, p);
+        p.mags = d_mags + done * (size_t)pairs * c->M * (out_c64 ? 4 : 2);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunk, pairs), dim3(threads), lds, c->stream, p);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -291,6 +291,27 @@ __global__ void __launch_bounds__(kThreads) large_split_kernel(Params p)
     st_stream(reinterpret_cast<float2 *>(p.mags) + ((size_t)(p.t0 + blockIdx.y) * p.M + j), left, right);
 }
 
+// ... the complex rows of sgx_stft_batch_complex: L = (a + conj b) / 2, R = (a - conj b) / (2i), each times 2 / W, as float4 per bin
+__global__ void __launch_bounds__(kThreads) large_split_complex_kernel(Params p)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= p.M) return;
+    const uint32_t k = j + 1, P = p.P;
+    float2 a, b;
+    if (p.chirp) {
+        const float2 *y = p.scr + (size_t)blockIdx.y * p.L;
+        a = cmul(y[k], p.chirp[k]);
+        b = cmul(y[P - k], p.chirp[P - k]);
+    } else {
+        const float2 *X = p.nat + (size_t)blockIdx.y * P;
+        a = X[k];
+        b = X[P - k];
+    }
+    const float sre = a.x + b.x, sim = a.y - b.y;
+    const float dre = a.x - b.x, dim = a.y + b.y;
+    reinterpret_cast<float4 *>(p.mags)[(size_t)(p.t0 + blockIdx.y) * p.M + j] = make_float4(sre * 0.5f * p.scale, sim * 0.5f * p.scale, dim * 0.5f * p.scale, -dre * 0.5f * p.scale);
+}
+
 // host: how many N-point sub-transforms a workgroup runs (B, at most `count` of them) and their LDS stride.  About kBlockPts / 2 points
 // per workgroup (32 KiB of LDS: five workgroups per CU), one transform of up to kBlockPts points where N is longer; the stride is odd
 // (N + 1 for an even N) so that the column gather and the row scatter, whose lanes are one stride apart, hit distinct LDS banks
@@ -428,7 +449,7 @@ void large_destroy(void *tables)
 }
 
 hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags)
+                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
 {
     using namespace large;
     (void)total_frames;   // every frame its own transform: no frame pairing
@@ -469,7 +490,8 @@ hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *
         hipLaunchKernelGGL(large_cols_kernel<true>, dim3(gx_cols, m), dim3(kThreads), lds_cols, c->stream, p);
         hipLaunchKernelGGL(large_rows_kernel, dim3(gx_rows, m), dim3(kThreads), lds_rows, c->stream, p);
         if (pl.chirp) hipLaunchKernelGGL(large_cols_kernel<false>, dim3(gx_cols, m), dim3(kThreads), lds_cols, c->stream, p);
-        hipLaunchKernelGGL(large_split_kernel, dim3(gx_split, m), dim3(kThreads), 0, c->stream, p);
+        if (out_c64) hipLaunchKernelGGL(large_split_complex_kernel, dim3(gx_split, m), dim3(kThreads), 0, c->stream, p);
+        else hipLaunchKernelGGL(large_split_kernel, dim3(gx_split, m), dim3(kThreads), 0, c->stream, p);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -653,6 +653,9 @@ struct ChirpTables {
 // two frames per workgroup, as it chose them), writing the (l, r) means instead; hipErrorNotSupported when no bands kernel has that plan
 hipError_t launch_bands_kernel(const Params &p, int fixed, bool real, bool two_frames, dim3 grid, size_t lds, hipStream_t stream);
 bool bands_kernel_exists(int fixed, bool real, bool two_frames);
+// the complex-row instantiations (stft_mixed_complex.hip, sgx_stft_batch_complex): the row kernel launch_mixed / launch_stft_chirpz would run
+hipError_t launch_complex_kernel(const Params &p, int fixed, bool real, unsigned threads, dim3 grid, size_t lds, hipStream_t stream);
+hipError_t launch_chirpz_complex_kernel(const Params &p, uint32_t L, bool real, dim3 grid, size_t lds, hipStream_t stream);
 
 }  // namespace mix
 
@@ -956,12 +959,12 @@ static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t)
 
 static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                                size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
-                               bool bands = false);
+                               bool bands = false, bool out_c64 = false);
 
 hipError_t launch_stft_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16)
+                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, bool out_c64)
 {
-    return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, d_mags, out_f16, nullptr);
+    return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, d_mags, out_f16, nullptr, false, out_c64);
 }
 
 hipError_t launch_render_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
@@ -980,7 +983,7 @@ hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float 
 // d_rgba: the fused column -- RGBA pixels, or with `bands` float2 (l, r) means per row (sgx_bands_batch)
 static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                                size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
-                               bool bands)
+                               bool bands, bool out_c64)
 {
     using namespace mix;
     if (n_frames == 0) return hipSuccess;
@@ -1048,6 +1051,10 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
             attr_err = launch_bands_kernel(p, t->fixed, real, two_frames, grid, lds, c->stream);
             return;
         }
+        if (out_c64) {   // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
+            attr_err = launch_complex_kernel(p, t->fixed, real, threads, grid, lds, c->stream);
+            return;
+        }
         if (two_frames)
             switch (t->fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N)                                                                                                  \
@@ -1102,7 +1109,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
         p.first_frame = first_frame + done;
         p.n_frames = chunk;
-        p.mags = d_mags ? d_mags + done * (size_t)pairs * c->M * (out_f16 ? 1 : 2) : nullptr;
+        p.mags = d_mags ? d_mags + done * (size_t)pairs * c->M * (out_f16 ? 1 : (out_c64 ? 4 : 2)) : nullptr;
         if (d_rgba) p.rgba = d_rgba + done * (size_t)pairs * c->R * (bands ? 8 : 4);
         launch(dim3((unsigned)chunk, pairs));
         hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
@@ -1281,7 +1288,7 @@ void chirpz_destroy(void *tables)
 }
 
 hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags)
+                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
 {
     using namespace mix;
     if (n_frames == 0) return hipSuccess;
@@ -1317,6 +1324,10 @@ hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float 
         hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, c->stream, p);
     };
     auto launch = [&](dim3 grid) {
+        if (out_c64) {   // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
+            attr_err = launch_chirpz_complex_kernel(p, t->L, real, grid, lds, c->stream);
+            return;
+        }
         switch (t->L) {
 #define X(Ln, A0, B0, A1, B1, A2, B2, N)                                                                             \
     case Ln:                                                                                                         \
@@ -1353,7 +1364,7 @@ hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float 
         const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
         p.first_frame = first_frame + done;
         p.n_frames = chunk;
-        p.mags = d_mags + done * (size_t)pairs * c->M * 2;
+        p.mags = d_mags + done * (size_t)pairs * c->M * (out_c64 ? 4 : 2);
         launch(dim3((unsigned)chunk, pairs));
         const hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
         if (e != hipSuccess) return e;

@@ -172,6 +172,28 @@ class SpectrogramEngine:
             assert got.value == n
         return out
 
+    def stft_batch_complex(self, pcm, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """The complex spectra behind stft_batch's magnitudes: [frames][pairs][M][2] torch.complex64, (L, R) of bins k = 1..W-1,
+        L = DFT(Hann * l) * 2/W and R = DFT(Hann * r) * 2/W, time origin = the frame's first sample (include/sgx.h).  `out`:
+        complex64 of that shape, or float32 [frames][pairs][M][2][2] (its view_as_real); the result is a complex64 view of it."""
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        if out is not None and out.dtype == torch.float32:
+            buf = self._out(out, (n, self.pairs, self.M, 2, 2), torch.float32)
+        else:
+            buf = torch.view_as_real(self._out(out, (n, self.pairs, self.M, 2), torch.complex64))
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_stft_batch_complex(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n,
+                                                         C.c_void_p(buf.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return torch.view_as_complex(buf.reshape(-1)[:n * self.pairs * self.M * 4].view(n, self.pairs, self.M, 2, 2))
+
     def process_one(self, lr: np.ndarray) -> Optional[np.ndarray]:
         """AudioTransform::process on host (l, r) pairs: [n][2] -> [M][2] or None."""
         lr = np.ascontiguousarray(lr, np.float32).reshape(-1, 2)
