@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py -- STFT frames/s (4096-point, hop 256) on N MI355X, with roofline and CPU baseline.
+"""bench.py -- STFT frames/s (4096-point, hop 256) on N MI355X, with roofline; --full adds the side legs and the CPU baseline.
 
 Contract (one JSON line on rank 0):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   N > 1: either launched by the driver as
       python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
   or BARE (`python bench.py --gpus N`): this process then touches no GPU at all, starts exactly that command as a
@@ -24,7 +24,13 @@ whenever the first allocation was kept, and always with --placements 1.  Every s
 independent mono frames, the application's operating point) is timed the same way: 5 burst launches, then back-to-back
 launches for --leg-sustain-s seconds; its figure is the mean of the last two thirds of that window.
 
-Extra objects on the same line:
+A plain run stops after the timed steps (and --dump-outputs, if given): it prints the headline, its `roofline` from the launches above and
+`checksum_first_4096_frames`.  Everything that takes runs of its own comes with --full, after the headline is final:
+`roofline.first_allocation` (when another candidate was kept) and `roofline.measured_device`, every object below, and
+`cpu_baseline`.  The placement study, the burst and the sustain window run either way: they set the device and the buffer the
+K timed steps see.
+
+Extra objects on the same line (`roofline` always, the others with --full):
   roofline     -- dominant kernel (the STFT kernel): algorithmic bytes per launch / launch duration (HIP events on the
                   launch stream) against the 8 TB/s HBM peak; frac (timed region), frac_burst, frac_sustained
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference's algorithm; the reference itself is Rust + FFTW and
@@ -111,6 +117,8 @@ def parse(argv=None):
     ap.add_argument("--leg-timeout", type=float, default=600.0, help="seconds after which a stalled collective leg is given up (exit 3)")
     ap.add_argument("--cpu-frames", type=int, default=262_144, help="frames of the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--generic", action="store_true", help="force the generic power-of-two kernel")
+    ap.add_argument("--full", action="store_true", help="after the headline: the side legs (N = 1) or config 5 (N > 1), the CPU baseline, the first "
+                                                        "allocation's own timed steps and the device's fill / copy rates (off: the headline alone)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (a fixed, seeded sample of frames)")
     args = ap.parse_args(argv)
@@ -604,13 +612,15 @@ def main_rank(args):
     steady = sustained[len(sustained) // 3:]     # the first third of the window is still heating up
     sustained_ms = (sum(steady) / len(steady)) if steady else kernel_ms
     burst_ms = sum(burst) / max(len(burst), 1)
-    # the first allocation under the same protocol, on the same hot device: K timed steps right behind the K that count
-    if mags_first is not None:
+    # the first allocation under the same protocol, on the same hot device: K timed steps right behind the K that count (--full)
+    if mags_first is None:
+        first, first_ms = timed, kernel_ms
+    elif args.full:
         first = timed_launches(args.steps, mags_first)
         first_ms = sum(first) / max(len(first), 1)
-        del mags_first
     else:
-        first, first_ms = timed, kernel_ms
+        first, first_ms = None, kernel_ms      # not measured (first_allocation: None); kernel_ms only fills its slot in the reduction
+    del mags_first
     elapsed, kernel_ms, sustained_ms, burst_ms, first_ms = max_over_ranks([elapsed, kernel_ms, sustained_ms, burst_ms, first_ms])
     checksum = eng.checksum(mags[:4096])
     if args.dump_outputs:
@@ -625,7 +635,7 @@ def main_rank(args):
 
     # the fraction of a MEASURED streaming rate next to the fraction of the vendor peak -- the same 16 GB
     # output buffer filled (write only) and copied half to half (read + write) by the runtime's own kernels, hot device
-    probe = device_streaming_rates(torch, mags) if rank == 0 else None
+    probe = device_streaming_rates(torch, mags) if rank == 0 and args.full else None
 
     def build_line(extra):
         total_frames = world * F * args.steps
@@ -668,7 +678,7 @@ def main_rank(args):
                 "first_allocation": {"launch_ms": first_ms, "frac": frac_of(first_ms), "frames_per_s": F / (first_ms * 1e-3),
                                      "launch_ms_stats": stats_ms(first), "is_value": placement["chosen"] == 0,
                                      "what": "the FIRST allocation of the output buffer, K timed steps on the same hot device "
-                                             "(the K steps of `value` themselves when the first allocation was kept)"},
+                                             "(the K steps of `value` themselves when the first allocation was kept)"} if first is not None else None,
                 "placement": placement,
                 "sustain_s": sustain_wall, "sclk_mhz_after_run": sclk,
                 "measured_device": None if probe is None else dict(
@@ -680,6 +690,13 @@ def main_rank(args):
         }
         line.update(extra)
         return line
+
+    if not args.full:       # a plain run: the headline alone
+        if rank == 0:
+            emit_line(build_line({}))
+        if grouped:
+            dist.destroy_process_group()
+        return 0
 
     # ---- everything below is reported beside the headline, which is final ------------------------------------
     import threading

@@ -1,6 +1,7 @@
 """bench.py's N = 1 run on the GPU, at reduced sizes, inside the suite the driver runs: ONE stdout line that parses, is at most 4 096 bytes
-(the 21 KB line of that round was not parsed) and carries the contract keys with `roofline` and `cpu_baseline`; the full
-record on stderr and in bench_legs.json.  A fresh child process (this pytest process has touched the GPU and is never replaced)."""
+(the 21 KB line of that round was not parsed) and carries the contract keys -- with `roofline` and `cpu_baseline` under
+--full, the headline alone without it; the full record on stderr and in bench_legs.json.  A fresh child process (this pytest process has
+touched the GPU and is never replaced)."""
 import json
 import os
 import subprocess
@@ -12,11 +13,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def test_the_default_run_prints_one_parsable_line_within_its_budget(tmp_path):
+def test_the_full_run_prints_one_parsable_line_within_its_budget(tmp_path):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "BENCH_LAUNCH_ONLY", "BENCH_BACKEND", "BENCH_SINGLE_DEVICE", "BENCH_TEST_HOOKS"):
         env.pop(k, None)
-    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "65536", "--placements", "2", "--sustain-s", "0.2", "--leg-sustain-s", "0.1",
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--frames", "65536", "--placements", "2", "--sustain-s", "0.2", "--leg-sustain-s", "0.1",
             "--pixel-frames", "65536", "--config4-hops", "2048", "--stereo-frames", "65536", "--paired-frames", "65536", "--complex-frames", "65536",
             "--app-frames", "16384", "--cpu-frames", "8192"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=600)
@@ -45,6 +46,35 @@ def test_the_default_run_prints_one_parsable_line_within_its_budget(tmp_path):
     full = json.loads(legs[0][len("bench_legs "):])
     assert full["value"] == line["value"] and "config4" in full and "placement" in full["roofline"]
     assert json.load(open(os.path.join(ROOT, "bench_legs.json")))["value"] == line["value"]
+
+
+def test_a_plain_run_prints_the_headline_alone():
+    # what is run for every change, several times: set-up, warm-up, the timed steps and the line -- no side leg, no CPU baseline,
+    # no timed run of its own beside the headline
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "BENCH_LAUNCH_ONLY", "BENCH_BACKEND", "BENCH_SINGLE_DEVICE", "BENCH_TEST_HOOKS"):
+        env.pop(k, None)
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "65536", "--placements", "2", "--sustain-s", "0.2"]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0].encode()) <= 4096, p.stdout[-3000:]
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+              "roofline"):
+        assert k in line, k
+    assert line["metric"].startswith("STFT frames/sec") and line["unit"] == "frames/s" and line["steps"] == 3 and line["warmup"] == 1
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["value"] > 0 and line["ms_per_step"] > 0
+    rf = line["roofline"]
+    assert 0 < rf["frac"] < 1 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-5 and "measured_device" not in rf
+    legs = [ln for ln in p.stderr.splitlines() if ln.startswith("bench_legs ")]
+    assert len(legs) == 1
+    full = json.loads(legs[0][len("bench_legs "):])
+    for k in ("cpu_baseline", "config3", "config4", "stereo4096", "mono_paired_frames", "mono_complex_frames", "app_point", "config5"):
+        assert k not in full, k
+    assert full["value"] == line["value"] and full["roofline"]["measured_device"] is None and full["roofline"]["placement"]["candidates"] == 2
+    # the first allocation is reported only where it costs no run of its own: when it is the buffer the timed steps wrote
+    assert (full["roofline"]["first_allocation"] is None) == (full["roofline"]["placement"]["chosen"] != 0)
 
 
 def test_dump_outputs_writes_the_last_timed_step(tmp_path, mags_err):

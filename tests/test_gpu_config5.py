@@ -28,7 +28,7 @@ def run_bench(extra_env, timeout=900):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "BENCH_LAUNCH_ONLY"):
         env.pop(k, None)
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "65536", "--placements", "1", "--sustain-s", "0",
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--frames", "65536", "--placements", "1", "--sustain-s", "0",
             "--config5-frames", str(TOTAL), "--config5-chunk", str(CHUNK), "--leg-timeout", "120"]
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=timeout)
 
@@ -85,7 +85,7 @@ def one_rank_over_rccl(total, extra_argv=(), timeout=900):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     for k in ("BENCH_BACKEND", "BENCH_SINGLE_DEVICE", "BENCH_LAUNCH_ONLY"):
         env.pop(k, None)
-    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "65536", "--placements", "1", "--sustain-s", "0",
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--frames", "65536", "--placements", "1", "--sustain-s", "0",
             "--config5-frames", str(total), "--leg-timeout", "600", *extra_argv]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])

@@ -41,7 +41,7 @@ def pick(acc, name_part, counter):
 
 fb, fm, wb, wm, s1, s2 = [load(d) for d in (fb_d, fm_d, wb_d, wm_d, s1_d, s2_d)]
 KIB = 1024.0
-out = {"how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes over `bench.py --steps 3 --warmup 1 --sustain-s 0 "
+out = {"how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes over `bench.py --full --steps 3 --warmup 1 --sustain-s 0 "
               "--cpu-frames 0` (tools/pmc_bench.sh); counters are KiB; FETCH_SIZE x 2 (gfx950 tallies 128-B requests at 64 B), WRITE_SIZE x 1",
        "calibration": {}, "csrc_sha16": csrc_sha16()}
 f = pick(fm, "copy_kernel", "FETCH_SIZE")

@@ -6,7 +6,7 @@
 n=${1:-5}; total=${2:-1000003}
 [ "$n" -le 5 ] || { echo "at most 5 ranks on one card (the launcher's agent process counts as the sixth)"; exit 2; }
 mkdir -p gpurun_out
-BENCH_BACKEND=gloo BENCH_SINGLE_DEVICE=1 timeout -k 10 600 python bench.py --gpus $n --steps 2 --warmup 1 --frames 65536 --placements 1 --sustain-s 0 \
+BENCH_BACKEND=gloo BENCH_SINGLE_DEVICE=1 timeout -k 10 600 python bench.py --gpus $n --steps 2 --warmup 1 --full --frames 65536 --placements 1 --sustain-s 0 \
     --config5-frames $total --config5-chunk 32768 --leg-timeout 300 > gpurun_out/rehearsal_n$n.json 2> gpurun_out/rehearsal_n$n.err || { tail -5 gpurun_out/rehearsal_n$n.err; exit 1; }
 single=$(timeout -k 10 300 python tools/config5_single.py $total 50000 | tail -1) || exit 1
 python3 - "$n" "$total" "$single" <<'PY'
