@@ -26,6 +26,9 @@ extern "C" {
                               max_frames: usize, d_mags_f16: *mut c_void, n_out: *mut usize) -> c_int;   // F16F16 ring rows
     pub fn sgx_stft_batch_complex(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
                                   max_frames: usize, d_spec: *mut f32, n_out: *mut usize) -> c_int;   // (L, R) complex spectra
+    pub fn sgx_istft_batch(ctx: *mut SgxCtx, d_spec: *const f32, n_frames: usize, first_sample: usize,
+                           max_samples: usize, d_pcm: *mut f32, n_out: *mut usize) -> c_int;   // PCM from (L, R) spectra
+    pub fn sgx_istft_supported(ctx: *const SgxCtx) -> c_int;
     pub fn sgx_render_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
                             max_frames: usize, d_rgba: *mut u8, n_out: *mut usize) -> c_int;
     pub fn sgx_magnitude_in(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, h_ranges: *const f32,

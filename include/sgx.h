@@ -17,6 +17,8 @@
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
  *     stream; no call waits for another context's stream (tests/test_gpu_streams.py).
+ *     sgx_istft_batch builds its tables on a context's first call (sgx_create does not); that first call may wait for the
+ *     context's own stream, as a grown workspace does.  Later calls only enqueue.
  *   - Every function returns SGX_OK (0) or a negative sgx_status; the text of the last error is
  *     available from sgx_last_error().  The library never aborts the host process (the
  *     reference unwrap()s: fft.rs:24,77).
@@ -196,6 +198,27 @@ SGX_API int sgx_stft_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, s
  * first_frame / max_frames / *n_out as sgx_stft_batch.  Stream-ordered and asynchronous. */
 SGX_API int sgx_stft_batch_complex(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame,
                                    size_t max_frames, float *d_spec, size_t *n_out);
+
+/* The inverse of sgx_stft_batch_complex: PCM from complex (L, R) spectra by weighted overlap-add.
+ *   d_spec [n_frames][pairs][M][2][2] float, exactly what sgx_stft_batch_complex writes; frame t has its time origin at sample t*H.
+ *   d_pcm  [n_out][channels] float, interleaved (the layout of the forward's input): samples [first_sample, first_sample + max_samples)
+ *          that exist, n < (n_frames - 1) * H + W.  Sample n is stream sample f0 * H + n when the spectra came from a forward call at
+ *          first_frame = f0.  (l, r): 2 channels; 2k channels: pair j writes channels 2j and 2j+1; mono: 1 channel from the L half.
+ * Definition, per frame and channel, with L[k] given for k = 1 .. W-1 and P = 2W:
+ *   1. g[n] = 1/2 Re sum_{k=1}^{W-1} L[k] e^{+i pi k n / W}, n in [0, 2W)  (numpy: A = zeros(P); A[1:W] = L; g = W * ifft(A).real).
+ *   2. The forward drops DC and Nyquist; the zero padding pins them down: c_e = minus the mean of g over the even n in [W, 2W), c_o the
+ *      same over the odd n, and the frame is f[m] = g[m] + c_{m mod 2}, m in [0, W).  For spectra the forward produced this is Hann * x;
+ *      for edited spectra it is the least-squares choice of the two missing real bins.
+ *   3. x[n] = sum_t w[m] f_t[m] / sum_t w[m]^2, m = n - t*H, over the frames t of d_spec that cover n, w = sgx_window (w[0] = 0);
+ *      exactly 0.0f where the envelope sum_t w[m]^2 is 0 (sample 0, and the gaps when H > W).
+ * Each sample's sum runs over its frames in ascending order: the output is bit-identical however the range is split across calls.
+ * n_frames == 0 or first_sample past the end: *n_out = 0, not an error.  n_out may be NULL.  Stream-ordered and asynchronous; the first
+ * call builds the context's inverse tables (see the conventions above).  SGX_ERR_UNSUPPORTED where sgx_istft_supported is 0. */
+SGX_API int sgx_istft_batch(sgx_ctx *ctx, const float *d_spec, size_t n_frames, size_t first_sample,
+                            size_t max_samples, float *d_pcm, size_t *n_out);
+/* 1: this context's W is served by sgx_istft_batch; 0: it is not (SGX_ERR_UNSUPPORTED: the lengths only SGX_FLAG_LARGE_TRANSFORM
+ * serves); < 0: error */
+SGX_API int sgx_istft_supported(const sgx_ctx *ctx);
 
 /* The same transform with the magnitudes stored as IEEE half (l, r) pairs, 4 bytes per bin
  * (round to nearest even): d_mags_f16 [n_out][pairs][M][2] half.  This is the texel format of the

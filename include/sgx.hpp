@@ -161,6 +161,38 @@ public:
         return out;
     }
 
+    // PCM back from complex (L, R) spectra laid out as process_stream_complex returns them: the samples [0, (frames - 1) H + W) of the
+    // signal, `channels` interleaved per sample (sgx_istft_batch)
+    std::vector<float> istft(const std::vector<std::vector<std::array<std::complex<float>, 2>>> &spec)
+    {
+        sgx_info inf{};
+        int rc = sgx_query(ctx_, &inf);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        const std::size_t frames = spec.size(), m = num_output_frequencies(), ch = inf.channels;
+        if (!frames) return {};
+        const std::size_t n = (frames - 1) * inf.hop_samples + inf.window_samples;
+        for (std::size_t f = 0; f < frames; ++f)
+            if (spec[f].size() != m)
+                throw Error(SGX_ERR_INVALID_ARG, "istft: frame " + std::to_string(f) + " holds " + std::to_string(spec[f].size()) +
+                                                     " bins, the context has " + std::to_string(m));
+        std::vector<float> flat(frames * m * 4);
+        for (std::size_t f = 0; f < frames; ++f)
+            for (std::size_t j = 0; j < m; ++j) {
+                float *b = &flat[(f * m + j) * 4];
+                b[0] = spec[f][j][0].real(); b[1] = spec[f][j][0].imag(); b[2] = spec[f][j][1].real(); b[3] = spec[f][j][1].imag();
+            }
+        reserve(flat.size() * sizeof(float), n * ch * sizeof(float));
+        check_hip(hipMemcpy(d_in_, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        rc = sgx_istft_batch(ctx_, d_in_, frames, 0, n, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> out(got * ch);
+        check_hip(hipMemcpy(out.data(), d_out_, out.size() * sizeof(float), hipMemcpyDeviceToHost));
+        return out;
+    }
+    bool istft_supported() const { return sgx_istft_supported(ctx_) == 1; }
+
     sgx_ctx *ctx() { return ctx_; }
 
 private:

@@ -451,6 +451,8 @@ void sgx_destroy(sgx_ctx *c)
     c->d_w16k = nullptr;
     sgx::large_destroy(c->d_large);
     c->d_large = nullptr;
+    sgx::istft_destroy(c->d_istft);
+    c->d_istft = nullptr;
     void *ptrs[] = {c->d_window, c->d_twiddle, c->d_rows, c->d_samples, c->d_lut_thr, c->d_alpha_thr,
                     c->d_lut_rgba, c->d_pal_seed, c->d_t_thr, c->d_t_cell, c->d_band_rows, c->d_band_samples, c->d_levels, c->d_ws_mags, c->d_one_in, c->d_one_out, c->d_cksum};
     for (void *p : ptrs)
@@ -540,6 +542,36 @@ int sgx_stft_batch_complex(sgx_ctx *c, const float *d_pcm, size_t n_samples, siz
     SGX_HIP(c, hipSetDevice(c->device));
     hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame, n, total, d_spec, StftOut::kComplex);
     if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_complex: kernel launch");
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+int sgx_istft_supported(const sgx_ctx *c)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    return sgx::istft_route(c) ? 1 : 0;
+}
+
+int sgx_istft_batch(sgx_ctx *c, const float *d_spec, size_t n_frames, size_t first_sample, size_t max_samples, float *d_pcm,
+                    size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (!sgx::istft_route(c))
+        return fail(c, SGX_ERR_UNSUPPORTED, "sgx_istft_batch: no inverse for transform length 2W = " + std::to_string(c->P) +
+                                                " (the multi-pass lengths of SGX_FLAG_LARGE_TRANSFORM are not served)");
+    if (n_frames == 0 || max_samples == 0) return SGX_OK;
+    if (n_frames - 1 > (SIZE_MAX - c->W) / c->H) return fail(c, SGX_ERR_INVALID_ARG, "sgx_istft_batch: n_frames out of range");
+    const size_t total = (n_frames - 1) * (size_t)c->H + c->W;   // samples n < (n_frames - 1) H + W exist
+    if (first_sample >= total) return SGX_OK;
+    size_t n = total - first_sample;
+    if (n > max_samples) n = max_samples;
+    if (!d_spec || !d_pcm) return fail(c, SGX_ERR_INVALID_ARG, "sgx_istft_batch: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    hipError_t e;
+    if (!c->d_istft && (e = sgx::istft_init(c, &c->d_istft)) != hipSuccess) return fail_hip(c, e, "sgx_istft_batch: tables");
+    e = sgx::launch_istft(c, c->d_istft, d_spec, n_frames, first_sample, first_sample + n, d_pcm);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_istft_batch: kernel launch");
     if (n_out) *n_out = n;
     return SGX_OK;
 }

@@ -130,6 +130,7 @@ struct sgx_ctx {
     void *d_chz = nullptr;         // chirp-z through the mixed-radix kernel's stages (or null: the radix-4 ladder of stft_bluestein.hip)
     void *d_w16k = nullptr;        // tables of the 16384-point kernel, 32 x 32 x 16 (stft16384_w.hip)
     void *d_large = nullptr;       // plan, tables and scratch of the multi-pass transform (stft_large.hip)
+    void *d_istft = nullptr;       // tables of the inverse STFT (stft_istft.hip): built by the first sgx_istft_batch, not by sgx_create
 
     // workspaces (grown on demand, kept)
     float *d_ws_mags = nullptr;
@@ -198,6 +199,7 @@ hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *
                              size_t total_frames, float *d_mags, bool out_f16, bool out_c64 = false);
 bool mixed_supported(uint32_t W);
 hipError_t mixed_init(sgx_ctx *c, void **out);
+hipError_t mixed_length_tables(uint32_t n, void **out);   // the stage plan and tables of an n-point transform alone (mixed_destroy frees them)
 void mixed_destroy(void *tables);
 uint32_t mixed_fixed_plan(const void *tables);
 bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode: a mono stream, every frame its own W-point transform
@@ -231,6 +233,12 @@ hipError_t large_init(sgx_ctx *c, void **out);
 void large_destroy(void *tables);
 hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
+// stft_istft.hip: the inverse of sgx_stft_batch_complex by weighted overlap-add; route 1 = the composite stages of 2W points,
+// 2 = chirp-z through a power-of-two plan, 0 = none (the lengths only kernel 11 serves)
+int istft_route(const sgx_ctx *c);
+hipError_t istft_init(sgx_ctx *c, void **out);
+void istft_destroy(void *tables);
+hipError_t launch_istft(const sgx_ctx *c, const void *tables, const float *d_spec, size_t n_frames, size_t s0, size_t s1, float *d_pcm);
 hipError_t launch_to_half(const sgx_ctx *c, const float *d_in, void *d_out, size_t n_pairs);
 hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns, uint8_t *d_rgba);
 hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_columns, const RowEntry *d_rows,

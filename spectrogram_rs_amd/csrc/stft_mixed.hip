@@ -864,6 +864,14 @@ hipError_t mixed_init(sgx_ctx *c, void **out)
     return hipSuccess;
 }
 
+hipError_t mixed_length_tables(uint32_t n, void **out)
+{
+    mix::MixTables *t = nullptr;
+    const hipError_t e = build_tables(n, false, &t);
+    if (e == hipSuccess) *out = t;
+    return e;
+}
+
 uint32_t mixed_fixed_plan(const void *tables) { return tables ? (uint32_t)static_cast<const mix::MixTables *>(tables)->fixed : 0u; }
 
 void mixed_destroy(void *tables)

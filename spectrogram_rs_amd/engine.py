@@ -194,6 +194,34 @@ class SpectrogramEngine:
             assert got.value == n
         return torch.view_as_complex(buf.reshape(-1)[:n * self.pairs * self.M * 4].view(n, self.pairs, self.M, 2, 2))
 
+    def istft_batch(self, spec, first_sample: int = 0, max_samples: Optional[int] = None, out=None):
+        """The inverse of stft_batch_complex: PCM from complex (L, R) spectra by weighted overlap-add (include/sgx.h states the
+        definition).  `spec`: the complex64 [frames][pairs][M][2] that stft_batch_complex returns, or its float32
+        [frames][pairs][M][2][2] view.  Returns float32 [n][channels], the samples [first_sample, first_sample + max_samples) that
+        exist (n < (frames - 1) * H + W); sample n is stream sample first_frame * H + n of the forward call."""
+        import torch
+
+        if spec.dtype == torch.complex64:
+            spec = torch.view_as_real(spec)
+        per_frame = self.pairs * self.M * 4
+        assert spec.dtype == torch.float32 and spec.numel() % per_frame == 0, \
+            "expected complex64 [frames][pairs][M][2] or float32 [frames][pairs][M][2][2]"
+        n_frames = spec.numel() // per_frame
+        total = (n_frames - 1) * self.H + self.W if n_frames else 0
+        n = max(total - first_sample, 0)
+        if max_samples is not None:
+            n = min(n, max_samples)
+        buf = self._out(out, (n, self.channels), torch.float32)
+        got = C.c_size_t(0)
+        self._check(self._lib.sgx_istft_batch(self._ctx, self._dev_f32(spec.contiguous()), n_frames, first_sample, n,
+                                              C.c_void_p(buf.data_ptr()), C.byref(got)))
+        assert got.value == n
+        return buf.reshape(-1)[:n * self.channels].view(n, self.channels)
+
+    def istft_supported(self) -> int:
+        """1 when istft_batch serves this context's window, 0 when it does not (the SGX_FLAG_LARGE_TRANSFORM-only lengths)"""
+        return self._check(self._lib.sgx_istft_supported(self._ctx))
+
     def process_one(self, lr: np.ndarray) -> Optional[np.ndarray]:
         """AudioTransform::process on host (l, r) pairs: [n][2] -> [M][2] or None."""
         lr = np.ascontiguousarray(lr, np.float32).reshape(-1, 2)
