@@ -36,6 +36,10 @@ extern "C" {
     pub fn sgx_bands_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize,
                            max_frames: usize, d_bands: *mut f32, n_out: *mut usize) -> c_int;   // magnitude_in over the context's rows
     pub fn sgx_bands_fused(ctx: *const SgxCtx) -> c_int;
+    pub fn sgx_bands_peak_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                                group: usize, d_peak: *mut f32, n_out: *mut usize) -> c_int;   // peak-hold of the bands over groups of frames
+    pub fn sgx_bands_peak_fused(ctx: *const SgxCtx) -> c_int;
+    pub fn sgx_render_bands(ctx: *mut SgxCtx, d_bands: *const f32, n_columns: usize, d_rgba: *mut u8) -> c_int;   // color_for over band columns
     pub fn sgx_set_gradient(ctx: *mut SgxCtx, h_rgb: *const u8, n: u32, stereo: c_int) -> c_int;
     pub fn sgx_set_gradient_fn(ctx: *mut SgxCtx, eval: extern "C" fn(f64, *mut u8, *mut c_void), user: *mut c_void,
                                stereo: c_int) -> c_int;

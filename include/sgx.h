@@ -12,7 +12,7 @@
  *   - All `d_*` pointers are DEVICE pointers (hipMalloc'ed, or a torch tensor's data_ptr()).
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
- *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_magnitude_in,
+ *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
  *     sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise, sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -269,6 +269,23 @@ SGX_API int sgx_bands_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, 
 /* 1: sgx_bands_batch runs one fused kernel from PCM to bands in this context (the palette plays no part); 0: two kernels
  * (the STFT into a bounded workspace, then magnitude_in over the context's own tables); < 0: error */
 SGX_API int sgx_bands_fused(const sgx_ctx *ctx);
+
+/* Peak-hold of sgx_bands_batch over groups of `group` consecutive frames: the overview of a long stream, no transient lost.
+ *   Frames [first_frame, first_frame + max_frames) that exist: F of them. Column j = 0 .. ceil(F / group) - 1 covers frames
+ *   first_frame + [j * group, min((j + 1) * group, F)); the last column may cover fewer.
+ *   d_peak [n_out][pairs][R][2] float: per pair, row py (0 = LOWEST, as sgx_bands_batch) and side, the maximum over the column's
+ *   frames of the value sgx_bands_batch stores for that frame.  *n_out = number of COLUMNS.
+ * group = 1 is sgx_bands_batch.  group = 0: SGX_ERR_INVALID_ARG.  Any group up to SIZE_MAX (one column).
+ * The comparison is on float values: which of +0 and -0 is stored is unspecified, as is the output for non-finite PCM.
+ * Stream-ordered and asynchronous; device memory beyond the caller's buffers is bounded (the 192 MiB workspace of the
+ * two-kernel routes, or 16 KiB * R / 1024 per persistent workgroup) whatever the number of frames. */
+SGX_API int sgx_bands_peak_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                                 size_t group, float *d_peak, size_t *n_out);
+/* 1: one kernel from PCM to peak columns (plus at most one combine pass over partial columns); 0: the workspace route; < 0: error */
+SGX_API int sgx_bands_peak_fused(const sgx_ctx *ctx);
+/* ColorScheme::color_for (colorscheme.rs:55-71) + put_pixel's row order over columns of bands: d_bands [n_columns][R][2] (py = 0 lowest)
+ * -> d_rgba [n_columns][R][4], image order (row 0 = highest frequency), the context's current colour scheme (mono or diverging). */
+SGX_API int sgx_render_bands(sgx_ctx *ctx, const float *d_bands, size_t n_columns, uint8_t *d_rgba);
 
 /* SpectrumAnalyzer::push_frequencies (spectrum_analyzer.rs:46-68) for ONE column of magnitudes
  * d_column [M][2] on the device: the n_bars (the widget has 128) adjacent bands of

@@ -138,6 +138,30 @@ public:
         return out;
     }
 
+    // the overview of a long stream: bands_stream's columns as maxima over groups of `group` consecutive frames, ceil(frames / group)
+    // columns x R (sgx_bands_peak_batch)
+    std::vector<Output> bands_peak_stream(const StereoMagnitude *lr, std::size_t n, std::size_t group)
+    {
+        sgx_info info;
+        int rc = sgx_query(ctx_, &info);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if (group == 0) throw Error(SGX_ERR_INVALID_ARG, "bands_peak_stream: group is 0");
+        const std::size_t frames = sgx_num_frames(ctx_, n), r = info.rows, cols = frames ? (frames - 1) / group + 1 : 0;
+        std::vector<Output> out(cols, Output(r));
+        if (!cols) return out;
+        reserve(n * 2 * sizeof(float), cols * r * 2 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        rc = sgx_bands_peak_batch(ctx_, d_in_, n, 0, frames, group, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(cols * r * 2);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < cols; ++f)
+            for (std::size_t j = 0; j < r; ++j) out[f][j] = {flat[(f * r + j) * 2], flat[(f * r + j) * 2 + 1]};
+        return out;
+    }
+
     // the complex (L, R) spectra behind process_stream's magnitudes for every complete frame of `lr`: frames x (W-1) bins of
     // {L, R} (sgx_stft_batch_complex)
     std::vector<std::vector<std::array<std::complex<float>, 2>>> process_stream_complex(const StereoMagnitude *lr, std::size_t n)

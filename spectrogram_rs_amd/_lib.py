@@ -101,6 +101,9 @@ SIGNATURES = [
     ("sgx_magnitude_in", C.c_int, [_ctx, _vp, _sz, _vp, C.c_uint32, _vp]),
     ("sgx_bands_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_bands_fused", C.c_int, [_ctx]),
+    ("sgx_bands_peak_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_bands_peak_fused", C.c_int, [_ctx]),
+    ("sgx_render_bands", C.c_int, [_ctx, _vp, _sz, _vp]),
     ("sgx_spectrum_levels", C.c_int, [_ctx, _vp, C.c_uint32, _vp]),
     ("sgx_live_create", C.c_int, [_ctx, _sz, C.c_uint32, C.POINTER(_vp)]),
     ("sgx_live_destroy", None, [_vp]),

@@ -261,6 +261,32 @@ int bands_route(const sgx_ctx *c)
     return 0;
 }
 
+// What sgx_bands_batch runs on frames [first, first + n): the fused kernel of its route, or the STFT into the first `mags_chunk` frames
+// of the workspace (the caller has grown it) and magnitude_in over the context's own row and sample tables, chunk by chunk.
+int run_bands(sgx_ctx *c, const char *who, const float *d_pcm, size_t first, size_t n, size_t total, float *d_bands, size_t mags_chunk)
+{
+    const int route = bands_route(c);
+    if (route != 0) {
+        // one kernel from PCM to bands: the magnitudes stay in LDS, 8 B per row leave the kernel
+        const hipError_t e = route == 1 ? sgx::launch_bands_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first, n, total, d_bands)
+                                        : sgx::launch_bands_mixed(c, c->d_mix, d_pcm, c->C, c->pairs, first, n, total, d_bands);
+        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": fused launch").c_str());
+        return SGX_OK;
+    }
+    // two kernels, as sgx_render_batch
+    for (size_t done = 0; done < n; done += mags_chunk) {
+        const size_t m = n - done < mags_chunk ? n - done : mags_chunk;
+        hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first + done, m, total, c->d_ws_mags);
+        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": stft launch").c_str());
+        e = sgx::launch_magnitude_in(c, c->d_ws_mags, m * c->pairs, c->d_rows, c->d_samples, c->R, d_bands + done * (size_t)c->pairs * c->R * 2);
+        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": magnitude_in launch").c_str());
+    }
+    return SGX_OK;
+}
+
+// sgx_bands_peak_batch in one kernel: where sgx_bands_batch runs the 4096-point kernels and the frames are not paired
+bool peak_fused(const sgx_ctx *c) { return bands_route(c) == 1 && sgx::wg4096_can_fuse_peak(c, c->d_fast_wg); }
+
 }  // namespace
 
 extern "C" {
@@ -695,30 +721,106 @@ int sgx_bands_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fir
     if (n > max_frames) n = max_frames;
     if (!d_pcm || !d_bands) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_batch: null buffer");
     SGX_HIP(c, hipSetDevice(c->device));
-    const int route = bands_route(c);
-    if (route != 0) {
-        // one kernel from PCM to bands: the magnitudes stay in LDS, 8 B per row leave the kernel
-        const hipError_t e = route == 1 ? sgx::launch_bands_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first_frame, n, total, d_bands)
-                                        : sgx::launch_bands_mixed(c, c->d_mix, d_pcm, c->C, c->pairs, first_frame, n, total, d_bands);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_batch: fused launch");
-        if (n_out) *n_out = n;
+    size_t chunk = 0;
+    if (bands_route(c) == 0) {   // two kernels: the magnitudes of a chunk of frames in the bounded workspace
+        chunk = (size_t)(192u << 20) / ((size_t)c->pairs * c->M * 2 * sizeof(float));
+        if (chunk < 1) chunk = 1;
+        if (chunk > n) chunk = n;
+        int rc = ensure_workspace(c, chunk);
+        if (rc != SGX_OK) return rc;
+    }
+    int rc = run_bands(c, "sgx_bands_batch", d_pcm, first_frame, n, total, d_bands, chunk);
+    if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+int sgx_bands_peak_fused(const sgx_ctx *c)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    return peak_fused(c) ? 1 : 0;
+}
+
+int sgx_bands_peak_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, size_t group,
+                         float *d_peak, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (group == 0) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_peak_batch: group is 0");
+    const size_t total = sgx_num_frames(c, n_samples);
+    if (first_frame >= total || max_frames == 0) return SGX_OK;
+    size_t n = total - first_frame;
+    if (n > max_frames) n = max_frames;
+    if (!d_pcm || !d_peak) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_peak_batch: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const size_t g = group < n ? group : n;              // (one column: any group from n on)
+    const size_t n_cols = (n - 1) / g + 1;
+    if (peak_fused(c)) {
+        // one kernel from PCM to peak columns: every persistent workgroup keeps the running maximum of its current column (in L2),
+        // the columns that span several workgroups are finished by one combine launch
+        const hipError_t e = sgx::launch_bands_peak_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first_frame, n, total, g, d_peak);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_peak_batch: fused launch");
+        if (n_out) *n_out = n_cols;
         return SGX_OK;
     }
-    // two kernels, as sgx_render_batch: the STFT into the bounded workspace, then magnitude_in over the context's own row and sample tables
-    const size_t bytes_per_frame = (size_t)c->pairs * c->M * 2 * sizeof(float);
-    size_t chunk = (size_t)(192u << 20) / bytes_per_frame;
+    // The workspace route: chunks of frames through sgx_bands_batch's own route into the bounded workspace, bands_peak_kernel reduces
+    // each chunk.  The 192 MiB hold, per frame of a chunk: its band column; on the two-kernel bands route its magnitudes in front;
+    // and behind the columns the sub-columns of a two-level reduction (kSubNum / kSubDen of a column and two more: below).
+    const size_t col = (size_t)c->pairs * c->R * 2, col_bytes = col * sizeof(float);
+    const int route = bands_route(c);
+    const size_t mags_bytes = route == 0 ? (size_t)c->pairs * c->M * 2 * sizeof(float) : 0;
+    constexpr size_t kBudget = (size_t)192u << 20, kSubNum = 9, kSubDen = 64, kTwoLevelMin = 64;
+    const size_t per_frame = col_bytes + mags_bytes + (col_bytes * kSubNum + kSubDen - 1) / kSubDen;
+    size_t chunk = kBudget > 2 * col_bytes ? (kBudget - 2 * col_bytes) / per_frame : 0;
     if (chunk < 1) chunk = 1;
     if (chunk > n) chunk = n;
-    int rc = ensure_workspace(c, chunk);
+    if (g <= chunk) chunk -= chunk % g;                  // whole columns per chunk; else a column accumulates over several chunks
+    const size_t sub_cap = chunk * kSubNum / kSubDen + 2;
+    const size_t ws_bytes = chunk * (col_bytes + mags_bytes) + sub_cap * col_bytes;
+    const size_t ws_unit = (size_t)c->pairs * c->M * 2 * sizeof(float);   // (ensure_workspace counts frames of magnitudes)
+    int rc = ensure_workspace(c, (ws_bytes + ws_unit - 1) / ws_unit);
     if (rc != SGX_OK) return rc;
-    for (size_t done = 0; done < n; done += chunk) {
-        const size_t m = n - done < chunk ? n - done : chunk;
-        hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame + done, m, total, c->d_ws_mags);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_batch: stft launch");
-        e = sgx::launch_magnitude_in(c, c->d_ws_mags, m * c->pairs, c->d_rows, c->d_samples, c->R, d_bands + done * (size_t)c->pairs * c->R * 2);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_batch: magnitude_in launch");
+    float *ws_bands = c->d_ws_mags + chunk * (mags_bytes / sizeof(float)), *ws_sub = ws_bands + chunk * col;
+    for (size_t done = 0; done < n;) {
+        const size_t j = done / g;                       // the column this chunk starts in: at its first frame unless g > chunk
+        size_t m = n - done < chunk ? n - done : chunk;
+        if (g > chunk && m > (j + 1) * g - done) m = (j + 1) * g - done;
+        rc = run_bands(c, "sgx_bands_peak_batch", d_pcm, first_frame + done, m, total, ws_bands, chunk);
+        if (rc != SGX_OK) return rc;
+        const size_t ge = g < m ? g : m;                 // frames per column inside this chunk
+        const bool accumulate = done != j * g;
+        float *dst = d_peak + j * col;
+        // long columns in two levels, about sqrt(ge) sub-columns of sqrt(ge) frames each: one thread per row and column would read
+        // thousands of frames in sequence on a handful of threads.  Sub-columns: m / sub + m / ge + 1 at most, with
+        // sub >= 8 and ge >= 64 that is 9 m / 64 + 1 -- what the workspace reserves; checked all the same.
+        size_t sub = ge;
+        if (ge >= kTwoLevelMin) {
+            sub = (size_t)std::ceil(std::sqrt((double)ge));
+            if (sgx::peak_columns(m, ge, sub) > sub_cap) sub = ge;
+        }
+        hipError_t e;
+        if (sub < ge) {
+            e = sgx::launch_bands_peak(c, ws_bands, m, ge, sub, ws_sub, false);
+            const size_t spc = (ge + sub - 1) / sub;
+            if (e == hipSuccess) e = sgx::launch_bands_peak(c, ws_sub, sgx::peak_columns(m, ge, sub), spc, spc, dst, accumulate);
+        } else {
+            e = sgx::launch_bands_peak(c, ws_bands, m, ge, ge, dst, accumulate);
+        }
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_peak_batch: bands_peak launch");
+        done += m;
     }
-    if (n_out) *n_out = n;
+    if (n_out) *n_out = n_cols;
+    return SGX_OK;
+}
+
+int sgx_render_bands(sgx_ctx *c, const float *d_bands, size_t n_columns, uint8_t *d_rgba)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (n_columns == 0) return SGX_OK;
+    if (!d_bands || !d_rgba) return fail(c, SGX_ERR_INVALID_ARG, "sgx_render_bands: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    hipError_t e = sgx::launch_render_bands(c, d_bands, n_columns, d_rgba);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_render_bands: kernel launch");
     return SGX_OK;
 }
 

@@ -173,6 +173,9 @@ bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables);
 bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables);   // the fused column without the colour (sgx_bands_batch): no palette condition
 hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                                size_t first_frame, size_t n_frames, size_t total_frames, float *d_bands);   // float2 [F][pairs][R]
+bool wg4096_can_fuse_peak(const sgx_ctx *c, const void *tables);    // sgx_bands_peak_batch in one kernel (plus the combine pass)
+hipError_t launch_bands_peak_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
+                                    size_t first_frame, size_t n_frames, size_t total_frames, size_t group, float *d_peak);   // group <= n_frames
 hipError_t launch_deinterleave_pairs(const sgx_ctx *c, const float *d_pcm, float *d_planes, size_t plane_floats, size_t first_sample, size_t n_samples,
                                      uint32_t channels, uint32_t pairs);   // deinterleave.hip
 bool wg4096_seed_is_within_one(const sgx_ctx *c);
@@ -243,6 +246,14 @@ hipError_t launch_to_half(const sgx_ctx *c, const float *d_in, void *d_out, size
 hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns, uint8_t *d_rgba);
 hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_columns, const RowEntry *d_rows,
                                const SampleEntry *d_samples, uint32_t n_ranges, float *d_out);
+// sgx_bands_peak_batch, the workspace route: output column k = the maximum of the source columns it covers (sgx_kernels.hip: PeakParams)
+inline size_t peak_columns(size_t n_src, size_t group, size_t sub)
+{
+    const size_t spc = (group + sub - 1) / sub, full = n_src / group, rem = n_src - full * group;
+    return full * spc + (rem + sub - 1) / sub;
+}
+hipError_t launch_bands_peak(const sgx_ctx *c, const float *d_src, size_t n_src, size_t group, size_t sub, float *d_dst, bool accumulate);
+hipError_t launch_render_bands(const sgx_ctx *c, const float *d_bands, size_t n_columns, uint8_t *d_rgba);
 void detach_views(sgx_ctx *c);   // sgx_view.hip: every live view of the context forgets it
 void detach_images(sgx_ctx *c);   // sgx_image.hip
 sgx_ctx *image_context(const struct sgx_image *im);

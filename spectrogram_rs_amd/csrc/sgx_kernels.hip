@@ -795,6 +795,128 @@ hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_c
 }
 
 // ------------------------------------------------------------------------------------------------
+// peak-hold over groups of band columns (sgx_bands_peak_batch) and the colour of a band column (sgx_render_bands)
+// ------------------------------------------------------------------------------------------------
+
+// Output column k is the maximum of the source columns [start, end), start = (k / spc) * group + (k % spc) * sub,
+// end = min(start + sub, (k / spc + 1) * group, n_src): with spc = 1 and sub = group, whole groups; with spc = ceil(group / sub), every
+// group as spc sub-columns, which a second launch (group = sub = spc over them) reduces -- a group of thousands of frames is then read
+// by thousands of threads instead of one per row.  A column is `col` float2 (pairs * R); a thread holds one (l, r) of one output column.
+// `accumulate`: the maximum with what dst holds (a group that spans several workspace chunks: launches on one stream, in order).
+// The comparison keeps the first of two equal values and drops a NaN that is not the first: a maximum is order-independent on
+// everything but the sign of a zero and NaN payloads, neither of which the bands code produces from finite PCM.
+struct PeakParams {
+    const float2 *src;
+    float2 *dst;
+    unsigned long long n_src, n_dst, group, sub, spc;
+    uint32_t col, accumulate;
+};
+
+__device__ __forceinline__ float2 max2(float2 a, float2 b) { return make_float2(b.x > a.x ? b.x : a.x, b.y > a.y ? b.y : a.y); }
+
+__global__ void __launch_bounds__(256) bands_peak_kernel(PeakParams p)
+{
+    const unsigned long long total = p.n_dst * p.col;
+    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (unsigned long long)gridDim.x * 256) {
+        const unsigned long long k = e / p.col;
+        const uint32_t i = (uint32_t)(e - k * p.col);
+        const unsigned long long g = k / p.spc, start = g * p.group + (k - g * p.spc) * p.sub;
+        unsigned long long end = start + p.sub;
+        if (end > (g + 1) * p.group) end = (g + 1) * p.group;
+        if (end > p.n_src) end = p.n_src;
+        const float2 *s = p.src + start * p.col + i;
+        float2 m = s[0];                       // (start < n_src: the host counts only columns that hold a frame)
+        unsigned long long f = start + 1;
+        for (; f + 4 <= end; f += 4) {         // four independent loads in flight
+            const float2 a = s[(f - start) * p.col], b = s[(f - start + 1) * p.col], c = s[(f - start + 2) * p.col], d = s[(f - start + 3) * p.col];
+            m = max2(max2(max2(max2(m, a), b), c), d);
+        }
+        for (; f < end; ++f) m = max2(m, s[(f - start) * p.col]);
+        if (p.accumulate) m = max2(p.dst[e], m);
+        p.dst[e] = m;
+    }
+}
+
+hipError_t launch_bands_peak(const sgx_ctx *c, const float *d_src, size_t n_src, size_t group, size_t sub, float *d_dst, bool accumulate)
+{
+    if (n_src == 0) return hipSuccess;
+    PeakParams p;
+    p.src = reinterpret_cast<const float2 *>(d_src);
+    p.dst = reinterpret_cast<float2 *>(d_dst);
+    p.n_src = n_src;
+    p.group = group;
+    p.sub = sub < group ? sub : group;
+    p.spc = (p.group + p.sub - 1) / p.sub;
+    p.n_dst = peak_columns(n_src, group, p.sub);
+    p.col = c->pairs * c->R;
+    p.accumulate = accumulate ? 1u : 0u;
+    size_t blocks = ((size_t)p.n_dst * p.col + 255) / 256;
+    const size_t cap = (size_t)c->n_cu * 32;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(bands_peak_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, p);
+    return hipGetLastError();
+}
+
+// ColorScheme::color_for + put_pixel over columns of bands: the pixel stage of render_kernel behind magnitude_in, whose (l, r) the
+// caller already holds.  The threshold tables sit in LDS where they fit (`in_lds`), else color_for reads them where they are.
+__global__ void __launch_bounds__(256) render_bands_kernel(RenderParams p, unsigned long long n_columns, uint32_t in_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float *thr_s = reinterpret_cast<float *>(smem_raw);               // [n_lut - 1]
+    float *athr_s = thr_s + p.n_lut;                                  // [255]
+    const float *thr = p.lut_thr, *athr = p.alpha_thr;
+    if (in_lds) {
+        for (uint32_t i = threadIdx.x; i + 1 < p.n_lut; i += 256) thr_s[i] = p.lut_thr[i];
+        for (uint32_t i = threadIdx.x; i < 255; i += 256) athr_s[i] = p.alpha_thr[i];
+        __syncthreads();
+        thr = thr_s;
+        athr = athr_s;
+    }
+    const float2 *bands = reinterpret_cast<const float2 *>(p.mags);   // [n_columns][R] (l, r), py = 0 the lowest row
+    uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
+    for (unsigned long long col = blockIdx.x; col < n_columns; col += gridDim.x) {
+        const float2 *src = bands + col * p.R;
+        uchar4 *dst = rgba + col * p.R;
+        for (uint32_t py = threadIdx.x; py < p.R; py += 256) {
+            const float2 v = src[py];
+            dst[p.R - 1 - py] = color_for(p, thr, athr, p.t_thr, p.lut_rgba, p.t_cell, v.x, v.y);   // simple_spectrogram.rs:150
+        }
+    }
+}
+
+hipError_t launch_render_bands(const sgx_ctx *c, const float *d_bands, size_t n_columns, uint8_t *d_rgba)
+{
+    if (n_columns == 0) return hipSuccess;
+    RenderParams p;
+    p.mags = d_bands;
+    p.rows = nullptr;
+    p.samples = nullptr;
+    p.lut_thr = c->d_lut_thr;
+    p.alpha_thr = c->d_alpha_thr;
+    p.lut_rgba = c->d_lut_rgba;
+    p.rgba = d_rgba;
+    p.M = c->M;
+    p.R = c->R;
+    p.n_lut = c->pal.n;
+    p.interp = c->cfg.interp;
+    p.stereo = (uint32_t)c->pal.stereo;
+    p.lut_mode = c->cfg.lut_index_mode;
+    p.t_thr = c->d_t_thr;
+    p.t_cell = (c->pal.segments && c->pal.stereo && !(c->cfg.flags & SGX_FLAG_LUT_WALK)) ? c->d_t_cell : nullptr;
+    p.segments = c->pal.segments ? 1u : 0u;
+    p.nan_rgba = make_uchar4(c->pal.nan_rgb[0], c->pal.nan_rgb[1], c->pal.nan_rgb[2], 255);
+    p.guess_a = p.guess_b = 0.0f;
+    p.alpha_seed = 0;       // the thresholds counted by bisection: the tables' own definition
+    const size_t lds = (size_t)(c->pal.n + 255) * sizeof(float);
+    const bool in_lds = lds <= 48 * 1024;
+    size_t blocks = (size_t)c->n_cu * 8;
+    if (blocks > n_columns) blocks = n_columns;
+    hipLaunchKernelGGL(render_bands_kernel, dim3((unsigned)blocks), dim3(256), in_lds ? lds : 0, c->stream, p, (unsigned long long)n_columns,
+                       in_lds ? 1u : 0u);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // f32 -> f16 magnitudes (only for STFT kernels that have no native half store)
 // ------------------------------------------------------------------------------------------------
 

@@ -105,6 +105,7 @@ __device__ __forceinline__ void fft8_half_zero(const float (&zr)[4], const float
 
 constexpr int kRowsF32 = 0, kRowsF16 = 1, kPixels = 2;   // what a launch writes: float rows, half-pair rows, RGBA columns (fused pixel path)
 constexpr int kBands = 3;   // the fused column's (l, r) row means as float2, no colour (sgx_bands_batch; PIX wg::kPixBandsCubic / kPixBandsCosine)
+constexpr int kPeak = 5;    // kBands held as a running maximum over groups of frames (sgx_bands_peak_batch; PIX wg::kPixPeakCubic / kPixPeakCosine)
 constexpr int kRowsC64 = 4;   // complex rows (sgx_stft_batch_complex): (S, S) per bin, 16 bytes, every bin pair stored as soon as it is untangled
 
 // PIX (kPixels only): the pixel code of the instantiation, wg::kPixCubic / kPixCosine / kPixGeneric (stft4096_wg.hpp)
@@ -175,7 +176,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     uint2 *pal = reinterpret_cast<uint2 *>(tw2 + 256);          // kPixels only: [256] {threshold, RGBA} (wg::pixel_for)
     constexpr bool F16 = MODE == kRowsF16;
     constexpr bool C64 = MODE == kRowsC64;
-    constexpr bool FUSED = MODE == kPixels || MODE == kBands;  // the column goes through LDS to the pixel passes
+    constexpr bool FUSED = MODE == kPixels || MODE == kBands || MODE == kPeak;  // the column goes through LDS to the pixel passes
 
     const int tid = threadIdx.x;
     const int t_p1 = TR ? (tid >> 4) + 16 * (tid & 15) : tid;     // pass-1 column of this thread
@@ -512,12 +513,23 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             // the fused pixel path requests the next iteration's load HERE, straight into L (dead since the slide): requested in front
             // of the exchange like the rows' it is two more live registers through the sample pass -- two spills, and a spill reload
             // is a vector-memory load the compiler waits for with vmcnt(0), this load included (same device: 3.79 -> 3.68 ms)
+            [[maybe_unused]] wg::PeakDst peak_a{}, peak_b{};
+            [[maybe_unused]] wg::PeakOld<true> peak_old{};
+            if constexpr (MODE == kPeak) {
+                // the column's rows as they are, requested in front of the barrier -- and in front of the next transform's load, which comes
+                // from HBM: the counter retires in order, and behind that load the row pass would wait for it too
+                peak_a = wg::peak_dst(p, la);
+                peak_b = have_b ? wg::peak_dst_next(p, peak_a, lb) : peak_a;
+                peak_old = wg::peak_prefetch<true>(p, peak_a, tid);
+            }
             if (SLIDE) L = column(columns_from(128 * (fa + 2) + 1152), 0);
             SGX_STAMP(16)   // (pixels) sample pass
             lds_barrier();
             SGX_STAMP(17)   // (pixels) barrier 8
             __builtin_amdgcn_s_setprio(3);
-            if constexpr (MODE == kBands) {
+            if constexpr (MODE == kPeak) {
+                wg::row_pass_peak<true>(p, row_words, vbuf, peak_a, peak_b, peak_old, have_b, tid);
+            } else if constexpr (MODE == kBands) {
                 float2 *bands = reinterpret_cast<float2 *>(p.rgba);
                 wg::row_pass_bands<true>(p, row_words, vbuf, bands + la * (size_t)p.R, bands + lb * (size_t)p.R, true, have_b, tid);
             } else {
@@ -620,7 +632,7 @@ namespace wg {
 
 // p: as launch_wg (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
 // transform's own tables and the job split are set here
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands, bool out_c64)
+hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands, bool out_c64, bool peak)
 {
     using namespace wgr;
     if (p.n_frames == 0) return hipSuccess;
@@ -633,13 +645,20 @@ hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, 
     unsigned long long blocks = (unsigned long long)c->n_cu * 4;   // persistent workgroups, four per CU, each a contiguous run of frame pairs
     unsigned long long per = (p.n_jobs + blocks - 1) / blocks;
     if (per < 1) per = 1;
+    if (peak) {   // sgx_bands_peak_batch: a run is 2 per frames
+        per = peak_align_run(per, 2, p.peak_group);
+        p.peak_run = 2 * per;
+    }
     blocks = (p.n_jobs + per - 1) / per;
     p.jobs_per_block = per;
     const dim3 grid((unsigned)blocks), block(256);
     auto launch = [&](auto slide_c) {
         constexpr bool S_ = decltype(slide_c)::value;
         constexpr size_t lds_rows = (S_ && SGX_ADDTID_R) ? kLdsBytesR : kLdsBytes, lds_render = (S_ && SGX_ADDTID_R) ? kLdsBytesRenderR : kLdsBytesRender;
-        if (render && bands) {   // (no palette: the row-image LDS size)
+        if (render && bands && peak) {
+            if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCosine, S_>), grid, block, lds_rows, c->stream, p);
+            else hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCubic, S_>), grid, block, lds_rows, c->stream, p);
+        } else if (render && bands) {   // (no palette: the row-image LDS size)
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCubic, S_>), grid, block, lds_rows, c->stream, p);
         } else if (render) {
@@ -656,7 +675,8 @@ hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, 
     };
     if (c->H == 256) launch(std::true_type{});
     else launch(std::false_type{});
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess && peak ? launch_peak_combine(c, p, blocks) : e;
 }
 
 }  // namespace wg

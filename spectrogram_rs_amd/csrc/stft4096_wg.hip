@@ -540,15 +540,27 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
             // the fused pixel path waits for the next transform's samples HERE: the sample pass has just waited for its table words with
             // vmcnt(0), so they are there -- behind the row pass, whose pixel stores sit in a loop the compiler cannot count through,
             // the same wait is a vmcnt(0) again: every pixel store just issued acknowledged by memory, once per column
+            [[maybe_unused]] PeakDst peak_d{};
+            [[maybe_unused]] PeakOld<false> peak_old{};
+            if constexpr (pix_peak(PIX)) {   // the column's rows as they are: requested in front of the wait for the next samples and the barrier
+                static_assert(!MONO, "paired mono frames take the workspace route of sgx_bands_peak_batch");
+                peak_d = peak_dst(p, (unsigned long long)f0);
+                peak_old = peak_prefetch<false>(p, peak_d, tid);
+            }
             if (!(MONO && PAIRING == kPairAdjacentRow && kSlideWindow)) next_samples_are_here();
-            lds_barrier();
-            if constexpr (BANDS) {
+            if constexpr (pix_peak(PIX)) {
+                lds_barrier();
+                __builtin_amdgcn_s_setprio(3);
+                row_pass_peak<false>(p, row_words, vbuf, peak_d, peak_d, peak_old, false, tid);
+            } else if constexpr (BANDS) {
+                lds_barrier();
                 float2 *bands = reinterpret_cast<float2 *>(p.rgba);   // [F][pairs][R] (l, r)
                 float2 *dst_a = bands + ((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * (size_t)p.R;
                 float2 *dst_b = bands + ((size_t)f1 * p.pairs + p.pair) * (size_t)p.R;
                 __builtin_amdgcn_s_setprio(3);
                 row_pass_bands<MONO>(p, row_words, vbuf, dst_a, dst_b, have_first, have_second, tid);
             } else {
+                lds_barrier();
                 uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
                 uchar4 *dst_a = rgba + ((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * (size_t)p.R;
                 uchar4 *dst_b = rgba + ((size_t)f1 * p.pairs + p.pair) * (size_t)p.R;
@@ -575,6 +587,39 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         atomicAdd(&g_phase_cycles[16], (unsigned long long)(job_end > job_begin ? job_end - job_begin : 0));   // wave-iterations
     }
 #endif
+}
+
+// sgx_bands_peak_batch: the columns that span several workgroups' runs (stft4096_wg.hpp: peak_dst).  Workgroup (b - 1, y) looks at the
+// boundary in front of run b: the column that crosses it, if one does, is finished HERE if this is the first boundary it crosses --
+// the maximum of slot 1 of the run it starts in and slot 0 of every later run it reaches, rows 256 y .. 256 y + 255.
+__global__ void __launch_bounds__(256) peak_combine_kernel(const float2 *partial, float2 *out, unsigned long long n_frames, unsigned long long group,
+                                                           unsigned long long run, uint32_t R, uint32_t pairs, uint32_t pair)
+{
+    const unsigned long long b = (unsigned long long)blockIdx.x + 1, fb = b * run;
+    const unsigned long long j = fb / group, c0 = j * group;
+    if (c0 == fb) return;                        // a column starts with the run
+    const unsigned long long b_lo = c0 / run;
+    if (b_lo + 1 != b) return;                   // finished at an earlier boundary
+    unsigned long long c1 = c0 + group;
+    if (c1 > n_frames) c1 = n_frames;
+    const unsigned long long b_hi = (c1 - 1) / run;
+    const uint32_t py = blockIdx.y * 256 + threadIdx.x;
+    if (py >= R) return;
+    float2 m = partial[(b_lo * 2 + 1) * R + py];
+    for (unsigned long long bb = b; bb <= b_hi; ++bb) {
+        const float2 v = partial[(bb * 2) * R + py];
+        m.x = v.x > m.x ? v.x : m.x;
+        m.y = v.y > m.y ? v.y : m.y;
+    }
+    out[(j * pairs + pair) * (size_t)R + py] = m;
+}
+
+hipError_t launch_peak_combine(const sgx_ctx *c, const Params &p, unsigned long long blocks)
+{
+    if (blocks < 2 || p.peak_run % p.peak_group == 0) return hipSuccess;   // one run, or every run whole columns
+    hipLaunchKernelGGL(peak_combine_kernel, dim3((unsigned)(blocks - 1), (p.R + 255) / 256), dim3(256), 0, c->stream, p.peak_partial,
+                       reinterpret_cast<float2 *>(p.rgba), p.n_frames, p.peak_group, p.peak_run, p.R, p.pairs, p.pair);
+    return hipGetLastError();
 }
 
 // Is the kernel's LUT-index seed floor(log2(power + 1e-7) a + b) (pixel_for) within one of the exact threshold count
@@ -699,6 +744,7 @@ void wg4096_destroy(void *tables)
     if (t->d_rows) (void)hipFree(t->d_rows);
     if (t->d_samples) (void)hipFree(t->d_samples);
     if (t->d_planes) (void)hipFree(t->d_planes);
+    if (t->d_peak_partial) (void)hipFree(t->d_peak_partial);
     delete t;
 }
 
@@ -738,13 +784,23 @@ namespace {
 template <bool RENDER>
 hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                      size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, uint8_t *d_rgba, bool out_f16 = false,
-                     bool bands = false, bool out_c64 = false)
+                     bool bands = false, bool out_c64 = false, size_t peak_group = 0)
 {
     using namespace wg;
     if (n_frames == 0) return hipSuccess;
     const auto *t = static_cast<const WgTables *>(tables);
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
+    // peak_group (with `bands`): sgx_bands_peak_batch, d_rgba the columns; the partial columns of every persistent workgroup
+    const size_t partial_floats = (size_t)(n_cu > c->n_cu ? n_cu : c->n_cu) * 4 * 2 * c->R * 2;
+    if (peak_group && partial_floats > t->peak_partial_floats) {
+        hipError_t e = hipStreamSynchronize(c->stream);  // a previous launch may still use the old buffer
+        if (e != hipSuccess) return e;
+        if (t->d_peak_partial) { (void)hipFree(t->d_peak_partial); t->d_peak_partial = nullptr; t->peak_partial_floats = 0; }
+        e = hipMalloc(reinterpret_cast<void **>(&t->d_peak_partial), partial_floats * sizeof(float));
+        if (e != hipSuccess) return e;
+        t->peak_partial_floats = partial_floats;
+    }
     // More than two channels: the (l, r) pairs are split into planes first and every pair runs the two-channel kernel on its
     // own plane.  (Reading a pair at a stride of C floats kept the strided variant at the register cap with 60-68 bytes of
     // scratch: 8 channels ran at 80 M transforms/s against 145-180 M for a stereo stream.)
@@ -801,6 +857,10 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
             }
             p.single_rows = t->single_rows;
             p.block_max_cnt = t->block_max_cnt;
+            if (peak_group) {   // (in the words of the palette and the row pointer: see Params)
+                p.peak_group = peak_group;
+                p.peak_partial = t->d_peak_partial;
+            }
         }
         // A one-channel stream (include/sgx.h, "Mono streams"): by default every frame its own real-input transform
         // (stft4096_real.hip); SGX_FLAG_PAIRED_FRAMES: two frames per transform; SGX_FLAG_COMPLEX_MONO: every frame as its own (s, s)
@@ -808,7 +868,7 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         const uint32_t fl = c->cfg.flags;      // (sgx_create: INDEPENDENT is set unless PAIRED was asked for)
         const bool own_transform = !(fl & SGX_FLAG_PAIRED_FRAMES) || (fl & SGX_FLAG_COMPLEX_MONO) != 0;
         if (channels == 1 && own_transform && !(fl & SGX_FLAG_COMPLEX_MONO) && real4096_serves(c, d_pcm, channels))
-            return launch_real4096(c, c->d_real, p, out_f16, RENDER, bands, out_c64);
+            return launch_real4096(c, c->d_real, p, out_f16, RENDER, bands, out_c64, peak_group != 0);
         const bool mono = channels == 1 && (fl & SGX_FLAG_PAIRED_FRAMES) && !(fl & SGX_FLAG_COMPLEX_MONO);
         p.pair_base = mono ? first_frame / 2 : 0;
         p.n_jobs = mono ? (first_frame + n_frames + 1) / 2 - first_frame / 2 : n_frames;
@@ -817,13 +877,19 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         unsigned long long blocks = (unsigned long long)n_cu * 4;
         unsigned long long per = (p.n_jobs + blocks - 1) / blocks;
         if (per < 1) per = 1;
+        if (peak_group) {
+            if (mono) return hipErrorInvalidValue;   // (paired frames: the workspace route, wg4096_can_fuse_peak)
+            per = peak_align_run(per, 1, peak_group);
+            p.peak_run = per;
+        }
         blocks = (p.n_jobs + per - 1) / per;
         p.jobs_per_block = per;
         const dim3 grid((unsigned)blocks), block(256);
         const size_t lds = RENDER && !bands ? kLdsBytesRender : kLdsBytes;   // (the bands rows need no palette)
         // the pixel code of the instantiation: the interpolator and the seed-only LUT search are compile-time (kPixCubic / kPixCosine);
         // SGX_FLAG_LUT_WALK and palettes whose seed proof fails run kPixGeneric
-        const int pix = !RENDER ? kPixNone : bands ? (p.interp == SGX_INTERP_COSINE ? kPixBandsCosine : kPixBandsCubic)
+        const int pix = !RENDER ? kPixNone : peak_group ? (p.interp == SGX_INTERP_COSINE ? kPixPeakCosine : kPixPeakCubic)
+                                   : bands ? (p.interp == SGX_INTERP_COSINE ? kPixBandsCosine : kPixBandsCubic)
                                    : (!p.seed_pm1 ? kPixGeneric : (p.interp == SGX_INTERP_COSINE ? kPixCosine : kPixCubic));
         auto launch = [&](auto mono_c, auto pairing_c, auto c2_c) {
             constexpr bool M_ = decltype(mono_c)::value, C2_ = decltype(c2_c)::value;
@@ -831,6 +897,12 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
             if (!RENDER && out_c64) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixNone : kPixRowsC64>), grid, block, lds, c->stream, p);
             else if (!RENDER && out_f16) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixRowsF16>), grid, block, lds, c->stream, p);
             else if (!RENDER) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixNone>), grid, block, lds, c->stream, p);
+            else if (pix_peak(pix)) {
+                if constexpr (RENDER && !M_) {
+                    if (pix == kPixPeakCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixPeakCubic>), grid, block, lds, c->stream, p);
+                    else hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixPeakCosine>), grid, block, lds, c->stream, p);
+                }
+            }
             else if (pix == kPixBandsCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCubic : kPixNone>), grid, block, lds, c->stream, p);
             else if (pix == kPixBandsCosine) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCosine : kPixNone>), grid, block, lds, c->stream, p);
             else if (pix == kPixCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixCubic : kPixNone>), grid, block, lds, c->stream, p);
@@ -852,6 +924,7 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
             launch(F{}, std::integral_constant<int, kPairAdjacent>{}, T{});
         }
         hipError_t e = hipGetLastError();
+        if (e == hipSuccess && peak_group) e = launch_peak_combine(c, p, blocks);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -882,6 +955,23 @@ hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float
 {
     return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr,
                            reinterpret_cast<uint8_t *>(d_bands), false, true);
+}
+
+// sgx_bands_peak_batch in one kernel: every stream launch_bands_wg4096 serves but paired mono frames (two frames of one transform may
+// fall into different columns of different workgroups' bookkeeping: those contexts take the workspace route)
+bool wg4096_can_fuse_peak(const sgx_ctx *c, const void *tables)
+{
+    const uint32_t fl = c->cfg.flags;
+    const bool paired = c->C == 1 && (fl & SGX_FLAG_PAIRED_FRAMES) && !(fl & SGX_FLAG_COMPLEX_MONO);
+    return wg4096_can_fuse_bands(c, tables) && !paired;
+}
+
+// group: 1 .. n_frames.  d_peak: float2 [ceil(n_frames / group)][pairs][R]
+hipError_t launch_bands_peak_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
+                                    size_t first_frame, size_t n_frames, size_t total_frames, size_t group, float *d_peak)
+{
+    return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr,
+                           reinterpret_cast<uint8_t *>(d_peak), false, true, false, group);
 }
 
 }  // namespace sgx

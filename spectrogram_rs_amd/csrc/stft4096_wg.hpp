@@ -36,7 +36,13 @@ struct Params {
     const float2 *tw1;   // [16][256]  w_4096^{t q1}
     const float2 *tw2;   // [16][16]   w_256^{t0 q2} at [q2][t0]
     const float *window; // [2048]
-    float *mags;
+    // Peak-hold columns (sgx_bands_peak_batch, the kPixPeak* instantiations; `rgba` is then float2 [columns][pairs][R]) write no rows
+    // and carry no palette: their three values ride in those words, so that the argument block of every other instantiation -- and
+    // with it their code objects -- stays as it is.
+    union {
+        float *mags;
+        float2 *peak_partial;            // [workgroups][2][R]: columns that leave a workgroup's run at its front (slot 0) or at its back (slot 1)
+    };
     unsigned long long first_frame, n_frames, n_jobs, jobs_per_block;
     unsigned long long pair_base;  // mono: global index of the first frame PAIR (first_frame / 2)
     unsigned long long total_frames;  // frames the stream holds (a pair's second frame is transformed whenever it exists)
@@ -46,8 +52,14 @@ struct Params {
     const uint32_t *rows;      // [R]  first slot | count << 16
     const PackedSample *samples;   // one entry per LDS slot: the rows' samples in lin_space order, plus pad slots (see wg4096_init)
     uint32_t n_samples;        // slots per column (sum of the rows' counts + pads)
-    const float *lut_thr;      // [255]
-    const uchar4 *lut_rgba;    // [256]
+    union {
+        const float *lut_thr;            // [255]
+        unsigned long long peak_group;   // frames per column, at most n_frames
+    };
+    union {
+        const uchar4 *lut_rgba;          // [256]
+        unsigned long long peak_run;     // frames per workgroup: its run is [blockIdx.x * peak_run, + peak_run) of the call's frames
+    };
     uint8_t *rgba;             // [F][pairs][R][4]
     uint32_t R, interp;
     float guess_a, guess_b;    // LUT index ~ floor(log2(power + 1e-7) * a + b), then exact fix-up
@@ -58,10 +70,22 @@ struct Params {
     const float2 *twu;         // [8][128] w_4096^{u + 128 q3} at [q3][u]; [0][0] holds w_4096^{1024} = -i
     unsigned long long stream_samples;   // samples the frames of the stream cover: columns past them read as zero
 };
+static_assert(sizeof(Params) == 216, "the kernel argument of every instantiation: its size is part of their code objects");
+
+// sgx_bands_peak_batch: the jobs of a workgroup's run, `per` of `fpj` (1 or 2) frames each, rounded up to whole columns of `group` frames
+// where that lengthens the run by at most 1/32 -- the runs are resident side by side, so a longer run is a longer launch, and finishing
+// the columns that cross a boundary (peak_combine_kernel) costs far less than that for all but the smallest groups
+inline unsigned long long peak_align_run(unsigned long long per, unsigned fpj, unsigned long long group)
+{
+    const unsigned long long unit = group % fpj == 0 ? group : group * fpj, run = per * fpj;
+    if (unit > run / 32) return per;
+    return (run + unit - 1) / unit * unit / fpj;
+}
+hipError_t launch_peak_combine(const sgx_ctx *c, const Params &p, unsigned long long blocks);   // stft4096_wg.hip
 
 // stft4096_real.hip
 hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands = false,
-                          bool out_c64 = false);   // out_c64: complex rows (sgx_stft_batch_complex)
+                          bool out_c64 = false, bool peak = false);   // out_c64: complex rows (sgx_stft_batch_complex); peak: p.peak_group, p.peak_partial
 
 // Which two mono frames share a transform: always (2j, 2j+1).
 //   kPairAdjacentRow : H = 256: frame 2j+1's rows are frame 2j's rows shifted by one (9 rows feed both)
@@ -83,6 +107,8 @@ struct WgTables {
     bool fusable = false;
     mutable float *d_planes = nullptr;   // more than two channels: (l, r) pair planes of the sample range of a call, grown on demand
     mutable size_t planes_floats = 0;
+    mutable float2 *d_peak_partial = nullptr;   // sgx_bands_peak_batch: [workgroups][2][R] partial columns (peak_dst), grown on demand
+    mutable size_t peak_partial_floats = 0;
 };
 
 __device__ __forceinline__ void lds_barrier()
@@ -198,7 +224,12 @@ constexpr int kMaxFusedSamples = kBufComplex - kColSlots;       // float2 per sa
 constexpr int kPixNone = 0, kPixCubic = 1, kPixCosine = 2, kPixGeneric = 3, kPixRowsF16 = 4;   // kPixRowsF16: no pixels either -- half-pair rows (stft4096_wg.hip)
 // the fused column without the colour (sgx_bands_batch): the row pass stores the (l, r) means as float2, lowest row first; no palette
 constexpr int kPixBandsCubic = 5, kPixBandsCosine = 6;
-constexpr bool pix_bands(int pix) { return pix == kPixBandsCubic || pix == kPixBandsCosine; }
+// the bands column held as a running maximum over groups of frames (sgx_bands_peak_batch): the row pass of the bands instantiations,
+// its store a load / max / store on a column that only this workgroup writes
+constexpr int kPixPeakCubic = 8, kPixPeakCosine = 9;
+constexpr bool pix_peak(int pix) { return pix == kPixPeakCubic || pix == kPixPeakCosine; }
+constexpr bool pix_bands(int pix) { return pix == kPixBandsCubic || pix == kPixBandsCosine || pix_peak(pix); }
+constexpr bool pix_cosine(int pix) { return pix == kPixCosine || pix == kPixBandsCosine || pix == kPixPeakCosine; }   // the interpolator is compile-time
 // no pixels: the complex rows of sgx_stft_batch_complex, (L, R) as 16 bytes per bin, stored inside the split (stft4096_wg.hip)
 constexpr int kPixRowsC64 = 7;
 //   // kPixGeneric: interpolator at run time, LUT seed + walk (SGX_FLAG_LUT_WALK / proof failed)
@@ -324,7 +355,7 @@ __device__ __forceinline__ void sample_pass_with(const Params &p, const float2 *
     for (int k = 0; k < kSampleSteps; ++k) {
         const uint32_t s = tid + 256 * k;
         if (s < p.n_samples) {
-            if (PIX == kPixCosine || PIX == kPixBandsCosine || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) vbuf[s] = interp_sample2<true>(P, se[k].i0, se[k].w);
+            if (pix_cosine(PIX) || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) vbuf[s] = interp_sample2<true>(P, se[k].i0, se[k].w);
             else vbuf[s] = interp_sample2<false>(P, se[k].i0, se[k].w);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -334,7 +365,7 @@ __device__ __forceinline__ void sample_pass_with(const Params &p, const float2 *
 template <int PIX>
 __device__ __forceinline__ void sample_pass(const Params &p, const float2 *P, float2 *vbuf, int tid)
 {
-    if (PIX == kPixCosine || PIX == kPixBandsCosine || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) sample_pass_for<true>(p, P, vbuf, tid);
+    if (pix_cosine(PIX) || (PIX == kPixGeneric && p.interp == SGX_INTERP_COSINE)) sample_pass_for<true>(p, P, vbuf, tid);
     else sample_pass_for<false>(p, P, vbuf, tid);
 }
 
@@ -482,6 +513,143 @@ __device__ __forceinline__ void row_pass_bands(const Params &p, const uint32_t (
         } else {
             dst_a[py] = make_float2(l, r);
         }
+        asm volatile("" ::: "memory");   // one row at a time (see row_pass)
+    }
+}
+
+// Peak-hold columns (sgx_bands_peak_batch).  A workgroup's frames are the contiguous run [run0, run1) of the call's frames; frame f
+// belongs to column f / peak_group.  A column that lies inside the run is accumulated in place in the output; one that leaves the run
+// at its front or at its back is accumulated in this workgroup's slot 0 or 1 of p.peak_partial, and peak_combine_kernel takes the
+// maximum over the workgroups it spans.  Either way the column is written by this workgroup alone, a row always by the same thread:
+// the first frame stores, every later one loads, takes the maximum and stores -- program order of one thread, no atomics.  (The
+// running column does not fit in LDS beside the transform at four workgroups per CU -- 4 x (kLdsBytes + 8 KB) > 160 KB -- nor in
+// registers across the transform; it lives in L2: 8 KB per workgroup.)
+struct PeakDst {
+    float2 *col;   // the (pair's) column this frame accumulates into
+    bool first;    // no frame of this run has been stored there yet
+    unsigned long long end;   // the column's frames end here
+};
+// (workgroup-uniform: scalar code.  The column of a frame by division -- a 64-bit one is a hundred scalar instructions in every wave
+// and every transform, so the 32-bit one wherever frame and group fit; a state carried across the frames instead costs these kernels,
+// at the 128-VGPR cap, a spilled register)
+__device__ __forceinline__ PeakDst peak_dst(const Params &p, unsigned long long f)
+{
+    const unsigned long long run0 = (unsigned long long)blockIdx.x * p.peak_run;
+    unsigned long long run1 = run0 + p.peak_run;
+    if (run1 > p.n_frames) run1 = p.n_frames;
+    const unsigned long long j = ((f | p.peak_group) >> 32) == 0 ? (unsigned long long)((uint32_t)f / (uint32_t)p.peak_group) : f / p.peak_group;
+    const unsigned long long c0 = j * p.peak_group;
+    unsigned long long c1 = c0 + p.peak_group;
+    if (c1 > p.n_frames) c1 = p.n_frames;
+    PeakDst d;
+    if (c0 >= run0 && c1 <= run1) d.col = reinterpret_cast<float2 *>(p.rgba) + (j * p.pairs + p.pair) * (size_t)p.R;
+    else d.col = p.peak_partial + ((size_t)blockIdx.x * 2 + (c0 >= run0 ? 1 : 0)) * (size_t)p.R;
+    d.first = f == (c0 > run0 ? c0 : run0);
+    d.end = c1;
+    return d;
+}
+// the frame behind the one `a` was found for: in the same column where that goes on (no second division), else found on its own
+__device__ __forceinline__ PeakDst peak_dst_next(const Params &p, const PeakDst &a, unsigned long long f)
+{
+    if (f >= a.end) return peak_dst(p, f);
+    PeakDst d = a;
+    d.first = false;
+    return d;
+}
+
+// What column `d` holds in this thread's four rows, requested in front of the barrier that precedes the row pass: four L2 round trips
+// side by side under the barrier instead of one after the other inside the pass.  MONO: a row holds (m, m), one word is enough.
+template <bool MONO>
+struct PeakOld {   // (named words, not arrays: the row pass picks one by a run-time row number, and an indexed array is a stack object)
+    float x0, x1, x2, x3, y0, y1, y2, y3;   // y: (l, r) streams only
+};
+template <bool MONO>
+__device__ __forceinline__ void peak_prefetch_row(const Params &p, const PeakDst &d, uint32_t py, float &x, float &y)
+{
+    x = y = 0.0f;
+    if (!d.first && py < p.R) {   // (d.first: workgroup-uniform)
+        if (MONO) {
+            x = reinterpret_cast<const float *>(d.col + py)[0];
+        } else {
+            const float2 v = d.col[py];
+            x = v.x;
+            y = v.y;
+        }
+    }
+}
+template <bool MONO>
+__device__ __forceinline__ PeakOld<MONO> peak_prefetch(const Params &p, const PeakDst &d, int tid)
+{
+    PeakOld<MONO> o;
+    asm volatile("" : "+v"(tid));   // (opaque: the four row addresses are not to be hoisted out of the transform loop -- they spill)
+    peak_prefetch_row<MONO>(p, d, tid, o.x0, o.y0);
+    peak_prefetch_row<MONO>(p, d, tid + 256, o.x1, o.y1);
+    peak_prefetch_row<MONO>(p, d, tid + 512, o.x2, o.y2);
+    peak_prefetch_row<MONO>(p, d, tid + 768, o.x3, o.y3);
+    return o;
+}
+
+__device__ __forceinline__ void peak_update(float2 *col, uint32_t py, bool first, float l, float r)
+{
+    if (!first) {   // (workgroup-uniform)
+        const float2 old = col[py];
+        l = l > old.x ? l : old.x;
+        r = r > old.y ? r : old.y;
+    }
+    col[py] = make_float2(l, r);
+}
+
+// row_pass_bands with the peak-hold store; `old`: peak_prefetch of column a.  MONO: .x / .y are frames a and b of the transform;
+// where both accumulate into the same column their maximum is taken in registers and the column is updated once, else b's column
+// (another one: a run's columns follow each other) is read here.
+template <bool MONO>
+__device__ __forceinline__ void row_pass_peak(const Params &p, const uint32_t (&row_words)[4], const float2 *vbuf, PeakDst a, PeakDst b,
+                                              const PeakOld<MONO> &old, bool have_b, int tid)
+{
+    const bool same = MONO && have_b && a.col == b.col;
+    // (the prefetched words move down one row per trip: picked by the row number they became an indexed stack object)
+    float ox = old.x0, ox1 = old.x1, ox2 = old.x2, ox3 = old.x3;
+    [[maybe_unused]] float oy = old.y0, oy1 = old.y1, oy2 = old.y2, oy3 = old.y3;
+#pragma unroll 1
+    for (int i_row = 0; i_row < 4; ++i_row) {
+        const uint32_t py = tid + 256 * i_row;
+        if (py >= p.R) break;
+        const uint32_t re = i_row == 0 ? row_words[0] : i_row == 1 ? row_words[1] : i_row == 2 ? row_words[2] : row_words[3];
+        const uint32_t first = re & 0xffffu, cnt = re >> 16;
+        float l, r;
+        if (p.single_rows & (1u << i_row)) {          // (launch-uniform) one sample: 0 + x (the sign of a zero as the sum gives it), / 1.0 = x
+            const float2 v = vbuf[first];
+            l = 0.0f + v.x;
+            r = 0.0f + v.y;
+        } else {
+            float sl = 0.0f, sr = 0.0f;
+            for (uint32_t i = 0; i < cnt; ++i) {
+                const float2 v = vbuf[first + i];
+                sl = sl + v.x;
+                sr = sr + v.y;
+            }
+            l = sl;
+            r = sr;
+            if (cnt > 1) {
+                const float nf = (float)cnt;
+                l = sl / nf;
+                r = sr / nf;
+            }
+        }
+        if constexpr (MONO) {
+            float m = same && r > l ? r : l;          // frame a, or both frames
+            if (!a.first) m = m > ox ? m : ox;
+            a.col[py] = make_float2(m, m);
+            if (have_b && !same) peak_update(b.col, py, b.first, r, r);
+        } else {
+            if (!a.first) {
+                l = l > ox ? l : ox;
+                r = r > oy ? r : oy;
+            }
+            a.col[py] = make_float2(l, r);
+            oy = oy1; oy1 = oy2; oy2 = oy3;
+        }
+        ox = ox1; ox1 = ox2; ox2 = ox3;
         asm volatile("" ::: "memory");   // one row at a time (see row_pass)
     }
 }

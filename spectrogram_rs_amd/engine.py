@@ -271,6 +271,41 @@ class SpectrogramEngine:
         """1 when bands_batch runs one fused kernel from PCM to bands in this context, 0 when it runs two"""
         return self._check(self._lib.sgx_bands_fused(self._ctx))
 
+    def bands_peak_batch(self, pcm, group: int, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [ceil(frames / group)][pairs][R][2] float32: the maximum of bands_batch's columns over groups of `group`
+        consecutive frames (the last group may be shorter), row 0 = the LOWEST.  group = 1 is bands_batch."""
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        group = int(group)
+        cols = -(-n // group) if group > 0 else 0
+        out = self._out(out, (cols, self.pairs, self.R, 2), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_bands_peak_batch(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n,
+                                                       min(group, 2 ** 64 - 1), C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == cols
+        return out
+
+    @property
+    def bands_peak_fused(self) -> int:
+        """1 when bands_peak_batch runs one kernel from PCM to peak columns (plus a combine pass), 0 on the workspace route"""
+        return self._check(self._lib.sgx_bands_peak_fused(self._ctx))
+
+    def render_bands(self, bands, out=None):
+        """[columns][R][2] float32 band columns (row 0 lowest: bands_batch, bands_peak_batch) -> [columns][R][4] uint8, image order."""
+        import torch
+
+        n = bands.numel() // (self.R * 2)
+        out = self._out(out, (n, self.R, 4), torch.uint8)
+        if n:
+            self._check(self._lib.sgx_render_bands(self._ctx, self._dev_f32(bands), n, C.c_void_p(out.data_ptr())))
+        return out
+
     def render_mags(self, mags, out=None):
         """[columns][M][2] float32 magnitudes -> [columns][R][4] uint8."""
         import torch
