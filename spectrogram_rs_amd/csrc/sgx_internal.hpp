@@ -105,7 +105,10 @@ struct sgx_ctx {
     uint32_t W = 0, P = 0, M = 0, H = 0, C = 0, pairs = 0, R = 0, sr_u32 = 0, logP = 0;
     int device = 0;
     hipStream_t stream = nullptr;
-    int stft_kernel = 0;  // 0 generic, 1 tuned 4096 wave-per-transform, 2 tuned 4096 workgroup-per-transform (scalar codelets), 3 the same with packed (re, im) arithmetic, 4 Bluestein (2W not a power of two), 5 tuned 16384, second design (four 4096-point residues), 6 mixed radix (2W = 2^a 3^b 5^c 7^d), 7 tuned 16384, first design (whole transform in LDS), 8 tuned 16384, third design (four time-decimated 4096-point transforms per quad of lanes; removed in round 6), 9 tuned 4800 (W = 2400; more than two channels: 6), 10 tuned 16384, fourth design (32 x 32 x 16, 512 threads: stft16384_w.hip)
+    // sgx_info.stft_kernel (ABI: the numbers stay): 0 generic, 2 tuned 4096 workgroup-per-transform, 4 Bluestein / chirp-z (2W with a prime
+    // factor above 7), 6 mixed radix (2W = 2^a 3^b 5^c 7^d), 9 tuned 4800 (W = 2400; more than two channels run 6's kernels), 10 tuned 16384
+    // (32 x 32 x 16: stft16384_w.hip), 11 multi-pass (stft_large.hip).  Retired numbers: docs/history/stft_kernel_numbers.md
+    int stft_kernel = 0;
 
     sgx::Tables tab;
     sgx::Palette pal;
@@ -121,7 +124,6 @@ struct sgx_ctx {
     uint2 *d_pal_seed = nullptr;   // [256] {threshold to leave level i (NaN for 255), RGBA of level i}: 256-level palettes, mono branch
     double *d_t_thr = nullptr;     // [n-1], segment palettes with a diverging scheme only
     uint16_t *d_t_cell = nullptr;  // [kTCells + 1] (or null)
-    void *d_fast = nullptr;        // tables of the wave-per-transform kernel (opaque here)
     void *d_fast_wg = nullptr;     // tables of the workgroup-per-transform kernel
     void *d_blu = nullptr;         // tables of the Bluestein (non-power-of-two) kernel
     void *d_mix = nullptr;         // tables of the mixed-radix (2, 3, 5, 7-smooth lengths) kernel

@@ -108,8 +108,8 @@ __global__ void __launch_bounds__(1024) stft_generic_kernel(StftGenericParams p)
     }
 }
 
-// The same transform for sgx_stft_batch_complex: the (L, R) spectra of the split, [F][pairs][M][2][2] floats, float4 per bin.  (A kernel of
-// its own: stft_generic_kernel's code is to stay exactly what it is.)
+// The same transform for sgx_stft_batch_complex: the (L, R) spectra of the split, [F][pairs][M][2][2] floats, float4 per bin.  (A copy up to
+// the store loop: behind one shared body both kernels compile to other code -- DESIGN.md, "Complex rows".)
 __global__ void __launch_bounds__(1024) stft_generic_complex_kernel(StftGenericParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];

@@ -452,8 +452,27 @@ struct Fixed4 {
     static_assert(M2 == R3 && M1 % R3 == 0 && M0 % R3 == 0 && R0 * R1 * R2 * R3 == P, "plan shape");
 };
 
-template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, bool REAL>
-__global__ void __launch_bounds__(F::NT, F::NT <= 256 ? 4 : 8) stft_mixed_fixed_kernel(Params p)
+// The kernels of a compile-time plan -- these, the bands ones (stft_mixed_bands.hip) and the complex-row ones (stft_mixed_complex.hip) -- are
+// wrappers around their shape's body (fixed3_body, fixed4_body) with an epilogue E: what becomes of the finished transform.  A wrapper
+// keeps its name, template parameters and launch bounds, and tools/isa_unchanged.py holds its code to what it was, by symbol.  That check
+// is also why the other shapes (run-time geometry, two frames per workgroup, chirp-z) are still copies: DESIGN.md, "Complex rows".
+struct RowsOrPixels {   // rows of magnitudes, or with p.render the fused pixel column
+    template <typename F, bool REAL>
+    static __device__ __forceinline__ void run(const Params &p, float2 *s, uint32_t pair, long long row_a, long long row_b, uint32_t tid)
+    {
+        if constexpr (REAL) {   // P is the WINDOW here
+            if (p.render) pixel_epilogue_real<F::NT, F::P>(p, s, row_a, tid);
+            else untangle_store(p, s, row_a, tid, F::NT);
+        } else if (p.render) {
+            pixel_epilogue<F::NT, F::W>(p, s, pair, row_a, row_b, tid);
+        } else {
+            split_store(p, s, pair, row_a, row_b, tid, F::NT);
+        }
+    }
+};
+
+template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, bool REAL, typename E>
+__device__ __forceinline__ void fixed3_body(const Params &p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *s = reinterpret_cast<float2 *>(smem_raw);
@@ -466,13 +485,39 @@ __global__ void __launch_bounds__(F::NT, F::NT <= 256 ? 4 : 8) stft_mixed_fixed_
     stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
     stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
     stage<R2A, R2B>(s, p, p.tw, FixGeo<1, F::P / F::R2, 1, F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
-    if constexpr (REAL) {   // P is the WINDOW here
-        if (p.render) pixel_epilogue_real<F::NT, F::P>(p, s, row_a, tid);
-        else untangle_store(p, s, row_a, tid, F::NT);
-    } else if (p.render) {
-        pixel_epilogue<F::NT, F::W>(p, s, pair, row_a, row_b, tid);
+    E::template run<F, REAL>(p, s, pair, row_a, row_b, tid);
+}
+
+// The one plan whose kernels keep the body's text in themselves: through fixed3_body the 2205-point kernels at 192 threads come out with
+// two instructions of their last stage in another order (profiles/r08_shared_bodies.txt), and every kernel is to compile to what it was.
+template <typename F>
+constexpr bool kOwnText = F::P == 2205 && F::NT == 192;
+
+template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, bool REAL>
+__global__ void __launch_bounds__(F::NT, F::NT <= 256 ? 4 : 8) stft_mixed_fixed_kernel(Params p)
+{
+    if constexpr (!kOwnText<F>) {
+        fixed3_body<F, R0A, R0B, R1A, R1B, R2A, R2B, REAL, RowsOrPixels>(p);
     } else {
-        split_store(p, s, pair, row_a, row_b, tid, F::NT);
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+        float2 *s = reinterpret_cast<float2 *>(smem_raw);
+        const uint32_t tid = threadIdx.x;
+        const uint32_t pair = blockIdx.y;
+        long long row_a, row_b;
+        Source src;
+        frame_source(p, pair, src, row_a, row_b);
+        using G0 = FixGeo<F::M0, F::P / F::R0, F::pp(F::M0), F::pp(F::P), F::W, F::PAD, F::NT, true>;
+        stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
+        stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
+        stage<R2A, R2B>(s, p, p.tw, FixGeo<1, F::P / F::R2, 1, F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
+        if constexpr (REAL) {   // the epilogue too: RowsOrPixels' text
+            if (p.render) pixel_epilogue_real<F::NT, F::P>(p, s, row_a, tid);
+            else untangle_store(p, s, row_a, tid, F::NT);
+        } else if (p.render) {
+            pixel_epilogue<F::NT, F::W>(p, s, pair, row_a, row_b, tid);
+        } else {
+            split_store(p, s, pair, row_a, row_b, tid, F::NT);
+        }
     }
 }
 
@@ -528,8 +573,8 @@ __global__ void __launch_bounds__(2 * F::NT, real2_waves_per_simd<F>()) stft_mix
     pixel_passes<2 * NT>(p, s, s + M + 1, M, true, 0u, (long long)fa, (long long)fa + 1, tid);
 }
 
-template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, int R3A, int R3B, bool REAL>
-__global__ void __launch_bounds__(F::NT, F::NT == 256 ? 4 : (F::NT == 512 ? 8 : 4)) stft_mixed_fixed4_kernel(Params p)
+template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, int R3A, int R3B, bool REAL, typename E>
+__device__ __forceinline__ void fixed4_body(const Params &p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *s = reinterpret_cast<float2 *>(smem_raw);
@@ -543,14 +588,13 @@ __global__ void __launch_bounds__(F::NT, F::NT == 256 ? 4 : (F::NT == 512 ? 8 : 
     stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
     stage<R2A, R2B>(s, p, p.tw + F::TW2, FixGeo<F::M2, F::P / F::R2, F::pp(F::M2), F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
     stage<R3A, R3B>(s, p, p.tw, FixGeo<1, F::P / F::R3, 1, F::pp(F::M2), F::W, F::PAD, F::NT, false>{}, src, tid);
-    if constexpr (REAL) {
-        if (p.render) pixel_epilogue_real<F::NT, F::P>(p, s, row_a, tid);
-        else untangle_store(p, s, row_a, tid, F::NT);
-    } else if (p.render) {
-        pixel_epilogue<F::NT, F::W>(p, s, pair, row_a, row_b, tid);
-    } else {
-        split_store(p, s, pair, row_a, row_b, tid, F::NT);
-    }
+    E::template run<F, REAL>(p, s, pair, row_a, row_b, tid);
+}
+
+template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, int R3A, int R3B, bool REAL>
+__global__ void __launch_bounds__(F::NT, F::NT == 256 ? 4 : (F::NT == 512 ? 8 : 4)) stft_mixed_fixed4_kernel(Params p)
+{
+    fixed4_body<F, R0A, R0B, R1A, R1B, R2A, R2B, R3A, R3B, REAL, RowsOrPixels>(p);
 }
 
 // ---- chirp-z (Bluestein) through the same stages: F[k] = c[k] sum_{n<W} (z[n] c[n]) conj(c)[k - n], c[n] = exp(-i pi n^2 / P), as a
@@ -648,6 +692,20 @@ struct ChirpTables {
 // four stages: 0.05 s at 96 / 192 / 176.4 kHz, and the 8192-point power of two
 #define MIX_FIXED4_PLANS(X) X(9600, 4, 3, 5, 2, 5, 1, 4, 4, 1024) X(19200, 5, 3, 5, 1, 4, 4, 4, 4, 1024) \
                             X(17640, 5, 3, 7, 2, 4, 3, 7, 1, 1024) X(8192, 4, 1, 4, 2, 4, 4, 4, 4, 512)
+
+// Every launch of the family goes through here: `lds` bytes of dynamic LDS for the transform's image, nt threads.  An image above the
+// 64 KiB a kernel may have by default (a CU has 160) has to be asked for as a function attribute first.  Returns that call's error, else
+// hipSuccess; an error of the launch itself is left for the caller's hipGetLastError.
+template <typename K>
+hipError_t launch_kernel(K kernel, const Params &p, unsigned nt, dim3 grid, size_t lds, hipStream_t stream)
+{
+    if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, stream, p);
+    return hipSuccess;
+}
 
 // the bands instantiations (stft_mixed_bands.hip): the kernel of the plan `fixed` that launch_mixed would run to pixels (real-input mode,
 // two frames per workgroup, as it chose them), writing the (l, r) means instead; hipErrorNotSupported when no bands kernel has that plan
@@ -965,6 +1023,42 @@ static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t)
     return nt && (size_t)c->M + 1 + c->tab.samples.size() <= t->lds_points && c->M <= nt * 10u;
 }
 
+// The frames p.first_frame .. + p.n_frames in launches of at most 2^30 workgroups (gridDim.x is limited to 2^31 - 1).  launch(grid) starts
+// one with p as this leaves it and returns the error of setting it up.  A mono stream under SGX_FLAG_PAIRED_FRAMES: one workgroup per frame
+// PAIR (2q, 2q+1) by global index, every launch addressing the whole range's rows.  Otherwise one per frame and channel pair, every launch
+// on its own rows: mags_stride floats and rgba_stride bytes per frame (either pointer may be null).
+// p is the caller's, changed in place before every launch (mono_pairs, pair_base and mags, or first_frame, n_frames, mags and rgba), so
+// `launch` must hold p by reference; c is read for the paired-frames flag only.
+template <typename Launch>
+static hipError_t launch_chunks(const sgx_ctx *c, mix::Params &p, float *d_mags, size_t mags_stride, uint8_t *d_rgba, size_t rgba_stride, Launch launch)
+{
+    const size_t first_frame = p.first_frame, n_frames = p.n_frames, max_chunk = 1u << 30;
+    if (p.C == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) {
+        p.mono_pairs = 1;
+        p.mags = d_mags;
+        const unsigned long long q0 = first_frame / 2, q1 = (first_frame + n_frames + 1) / 2;
+        for (unsigned long long q = q0; q < q1; q += max_chunk) {
+            const unsigned long long chunk = q1 - q < max_chunk ? q1 - q : max_chunk;
+            p.pair_base = q;
+            hipError_t e = launch(dim3((unsigned)chunk, 1));
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    for (size_t done = 0; done < n_frames; done += max_chunk) {
+        const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
+        p.first_frame = first_frame + done;
+        p.n_frames = chunk;
+        p.mags = d_mags ? d_mags + done * mags_stride : nullptr;
+        if (d_rgba) p.rgba = d_rgba + done * rgba_stride;
+        hipError_t e = launch(dim3((unsigned)chunk, p.pairs));
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
                                size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
                                bool bands = false, bool out_c64 = false);
@@ -1046,29 +1140,16 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
     const bool two_frames = real && d_rgba && real_two_frames(t->fixed);   // real-input mode to pixels at the application plans: two frames (two images) per workgroup
     if (two_frames) lds = std::max(lds, 2 * (size_t)t->lds_points * sizeof(float2));
     const unsigned threads = t->threads;
-    hipError_t attr_err = hipSuccess;
-    auto go = [&](auto kernel, unsigned nt, dim3 grid) {
-        if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { attr_err = e; return; }
-        }
-        hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, c->stream, p);
-    };
-    auto launch = [&](dim3 grid) {
-        if (bands) {
-            attr_err = launch_bands_kernel(p, t->fixed, real, two_frames, grid, lds, c->stream);
-            return;
-        }
-        if (out_c64) {   // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
-            attr_err = launch_complex_kernel(p, t->fixed, real, threads, grid, lds, c->stream);
-            return;
-        }
+    auto go = [&](auto kernel, unsigned nt, dim3 grid) { return launch_kernel(kernel, p, nt, grid, lds, c->stream); };
+    auto launch = [&](dim3 grid) -> hipError_t {
+        if (bands) return launch_bands_kernel(p, t->fixed, real, two_frames, grid, lds, c->stream);
+        // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
+        if (out_c64) return launch_complex_kernel(p, t->fixed, real, threads, grid, lds, c->stream);
         if (two_frames)
             switch (t->fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N)                                                                                                  \
     case Pn:                                                                                                                              \
-        go(stft_mixed_real2_render_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2>, 2 * N, dim3((grid.x + 1) / 2, 1)); \
-        return;
+        return go(stft_mixed_real2_render_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2>, 2 * N, dim3((grid.x + 1) / 2, 1));
                 MIX_REAL2_RENDER_PLANS(X)
 #undef X
             default: break;
@@ -1076,7 +1157,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         if (real && d_rgba)
             switch (t->fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) \
-    case Pn: go(stft_mixed_fixed_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, N, grid); return;
+    case Pn: return go(stft_mixed_fixed_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, N, grid);
                 MIX_REAL_RENDER_PLANS(X)
 #undef X
             default: break;
@@ -1084,46 +1165,20 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         switch (t->fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N)                                                                                      \
     case Pn:                                                                                                                  \
-        if (real) go(stft_mixed_fixed_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, N, grid);   \
-        else go(stft_mixed_fixed_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, N, grid);      \
-        break;
+        if (real) return go(stft_mixed_fixed_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, N, grid); \
+        return go(stft_mixed_fixed_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, N, grid);
             MIX_FIXED_PLANS(X)
 #undef X
 #define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N)                                                                                               \
     case Pn:                                                                                                                                   \
-        if (real) go(stft_mixed_fixed4_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, N, grid);   \
-        else go(stft_mixed_fixed4_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, N, grid);      \
-        break;
+        if (real) return go(stft_mixed_fixed4_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, N, grid); \
+        return go(stft_mixed_fixed4_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, N, grid);
             MIX_FIXED4_PLANS(X)
 #undef X
-        default: go(stft_mixed_kernel, threads, grid); break;
+        default: return go(stft_mixed_kernel, threads, grid);
         }
     };
-    const size_t max_chunk = 1u << 30;
-    if (channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) {
-        p.mono_pairs = 1;
-        p.mags = d_mags;
-        const unsigned long long q0 = first_frame / 2, q1 = (first_frame + n_frames + 1) / 2;
-        for (unsigned long long q = q0; q < q1; q += max_chunk) {
-            const unsigned long long chunk = q1 - q < max_chunk ? q1 - q : max_chunk;
-            p.pair_base = q;
-            launch(dim3((unsigned)chunk, 1));
-            hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    for (size_t done = 0; done < n_frames; done += max_chunk) {
-        const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
-        p.first_frame = first_frame + done;
-        p.n_frames = chunk;
-        p.mags = d_mags ? d_mags + done * (size_t)pairs * c->M * (out_f16 ? 1 : (out_c64 ? 4 : 2)) : nullptr;
-        if (d_rgba) p.rgba = d_rgba + done * (size_t)pairs * c->R * (bands ? 8 : 4);
-        launch(dim3((unsigned)chunk, pairs));
-        hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_chunks(c, p, d_mags, (size_t)pairs * c->M * (out_f16 ? 1 : (out_c64 ? 4 : 2)), d_rgba, (size_t)pairs * c->R * (bands ? 8 : 4), launch);
 }
 
 // ---- chirp-z through the composite stages (see chirpz3_kernel) --------------------------------------------------------
@@ -1323,61 +1378,27 @@ hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float 
     p.vec2 = (channels >= 2 && channels % 2 == 0 && reinterpret_cast<uintptr_t>(d_pcm) % 8 == 0) ? 1u : 0u;
     if (real) p.vec2 = c->W % 2 == 0 ? 1u : 0u;   // sample PAIRS of one channel as 8-byte words
     const size_t lds = (size_t)t->lds_points * sizeof(float2);
-    hipError_t attr_err = hipSuccess;
-    auto go = [&](auto kernel, unsigned nt, dim3 grid) {
-        if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { attr_err = e; return; }
-        }
-        hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, c->stream, p);
-    };
-    auto launch = [&](dim3 grid) {
-        if (out_c64) {   // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
-            attr_err = launch_chirpz_complex_kernel(p, t->L, real, grid, lds, c->stream);
-            return;
-        }
+    auto go = [&](auto kernel, unsigned nt, dim3 grid) { return launch_kernel(kernel, p, nt, grid, lds, c->stream); };
+    auto launch = [&](dim3 grid) -> hipError_t {
+        // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
+        if (out_c64) return launch_chirpz_complex_kernel(p, t->L, real, grid, lds, c->stream);
         switch (t->L) {
 #define X(Ln, A0, B0, A1, B1, A2, B2, N)                                                                             \
     case Ln:                                                                                                         \
-        if (real) go(chirpz3_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, N, grid);   \
-        else go(chirpz3_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, N, grid);      \
-        break;
+        if (real) return go(chirpz3_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, N, grid); \
+        return go(chirpz3_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, N, grid);
             CHIRP_PLANS3(X)
 #undef X
 #define X(Ln, A0, B0, A1, B1, A2, B2, A3, B3, N)                                                                                      \
     case Ln:                                                                                                                          \
-        if (real) go(chirpz4_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, N, grid);    \
-        else go(chirpz4_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, N, grid);       \
-        break;
+        if (real) return go(chirpz4_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, N, grid); \
+        return go(chirpz4_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, N, grid);
             CHIRP_PLANS4(X)
 #undef X
-        default: attr_err = hipErrorInvalidValue; break;
+        default: return hipErrorInvalidValue;
         }
     };
-    const size_t max_chunk = 1u << 30;
-    if (channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) {
-        p.mono_pairs = 1;
-        p.mags = d_mags;
-        const unsigned long long q0 = first_frame / 2, q1 = (first_frame + n_frames + 1) / 2;
-        for (unsigned long long q = q0; q < q1; q += max_chunk) {
-            const unsigned long long chunk = q1 - q < max_chunk ? q1 - q : max_chunk;
-            p.pair_base = q;
-            launch(dim3((unsigned)chunk, 1));
-            const hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    for (size_t done = 0; done < n_frames; done += max_chunk) {
-        const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
-        p.first_frame = first_frame + done;
-        p.n_frames = chunk;
-        p.mags = d_mags + done * (size_t)pairs * c->M * (out_c64 ? 4 : 2);
-        launch(dim3((unsigned)chunk, pairs));
-        const hipError_t e = attr_err != hipSuccess ? attr_err : hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_chunks(c, p, d_mags, (size_t)pairs * c->M * (out_c64 ? 4 : 2), nullptr, 0, launch);
 }
 
 #endif  // SGX_MIXED_KERNELS_ONLY

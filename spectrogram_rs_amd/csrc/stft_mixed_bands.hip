@@ -8,45 +8,44 @@
 namespace sgx {
 namespace mix {
 
-// The bodies of stft_mixed_fixed_kernel, stft_mixed_fixed4_kernel and stft_mixed_real2_render_kernel (stft_mixed.hip) with their pixel
-// epilogue in its BANDS form.  (Copied rather than shared: the pixel kernels' code is to stay exactly what it is.)
+// stft_mixed_fixed_kernel and stft_mixed_fixed4_kernel (stft_mixed.hip) with the column in its BANDS form
+struct BandsColumn {
+    template <typename F, bool REAL>
+    static __device__ __forceinline__ void run(const Params &p, float2 *s, uint32_t pair, long long row_a, long long row_b, uint32_t tid)
+    {
+        if constexpr (REAL) pixel_epilogue_real<F::NT, F::P, true>(p, s, row_a, tid);   // P is the WINDOW here
+        else pixel_epilogue<F::NT, F::W, true>(p, s, pair, row_a, row_b, tid);
+    }
+};
+
 template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, bool REAL>
 __global__ void __launch_bounds__(F::NT, F::NT <= 256 ? 4 : 8) stft_mixed_fixed_bands_kernel(Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float2 *s = reinterpret_cast<float2 *>(smem_raw);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t pair = blockIdx.y;
-    long long row_a, row_b;
-    Source src;
-    frame_source(p, pair, src, row_a, row_b);
-    using G0 = FixGeo<F::M0, F::P / F::R0, F::pp(F::M0), F::pp(F::P), F::W, F::PAD, F::NT, true>;
-    stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
-    stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
-    stage<R2A, R2B>(s, p, p.tw, FixGeo<1, F::P / F::R2, 1, F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
-    if constexpr (REAL) pixel_epilogue_real<F::NT, F::P, true>(p, s, row_a, tid);   // P is the WINDOW here
-    else pixel_epilogue<F::NT, F::W, true>(p, s, pair, row_a, row_b, tid);
+    if constexpr (!kOwnText<F>) {
+        fixed3_body<F, R0A, R0B, R1A, R1B, R2A, R2B, REAL, BandsColumn>(p);
+    } else {   // fixed3_body's text: see kOwnText in stft_mixed.hip
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+        float2 *s = reinterpret_cast<float2 *>(smem_raw);
+        const uint32_t tid = threadIdx.x;
+        const uint32_t pair = blockIdx.y;
+        long long row_a, row_b;
+        Source src;
+        frame_source(p, pair, src, row_a, row_b);
+        using G0 = FixGeo<F::M0, F::P / F::R0, F::pp(F::M0), F::pp(F::P), F::W, F::PAD, F::NT, true>;
+        stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
+        stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
+        stage<R2A, R2B>(s, p, p.tw, FixGeo<1, F::P / F::R2, 1, F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
+        BandsColumn::run<F, REAL>(p, s, pair, row_a, row_b, tid);
+    }
 }
 
 template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, int R3A, int R3B, bool REAL>
 __global__ void __launch_bounds__(F::NT, F::NT == 256 ? 4 : (F::NT == 512 ? 8 : 4)) stft_mixed_fixed4_bands_kernel(Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float2 *s = reinterpret_cast<float2 *>(smem_raw);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t pair = blockIdx.y;
-    long long row_a, row_b;
-    Source src;
-    frame_source(p, pair, src, row_a, row_b);
-    using G0 = FixGeo<F::M0, F::P / F::R0, F::pp(F::M0), F::pp(F::P), F::W, F::PAD, F::NT, true>;
-    stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
-    stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
-    stage<R2A, R2B>(s, p, p.tw + F::TW2, FixGeo<F::M2, F::P / F::R2, F::pp(F::M2), F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
-    stage<R3A, R3B>(s, p, p.tw, FixGeo<1, F::P / F::R3, 1, F::pp(F::M2), F::W, F::PAD, F::NT, false>{}, src, tid);
-    if constexpr (REAL) pixel_epilogue_real<F::NT, F::P, true>(p, s, row_a, tid);
-    else pixel_epilogue<F::NT, F::W, true>(p, s, pair, row_a, row_b, tid);
+    fixed4_body<F, R0A, R0B, R1A, R1B, R2A, R2B, R3A, R3B, REAL, BandsColumn>(p);
 }
 
+// The body of stft_mixed_real2_render_kernel (stft_mixed.hip) with pixel_passes in its BANDS form.  (A copy: see fixed3_body there.)
 template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B>
 __global__ void __launch_bounds__(2 * F::NT, real2_waves_per_simd<F>()) stft_mixed_real2_bands_kernel(Params p)
 {
@@ -110,46 +109,37 @@ bool bands_kernel_exists(int fixed, bool real, bool two_frames)
 
 hipError_t launch_bands_kernel(const Params &p, int fixed, bool real, bool two_frames, dim3 grid, size_t lds, hipStream_t stream)
 {
-    hipError_t err = hipErrorNotSupported;
-    auto go = [&](auto kernel, unsigned nt, dim3 g) {
-        if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (err != hipSuccess) return;
-        }
-        hipLaunchKernelGGL(kernel, g, dim3(nt), lds, stream, p);
-        err = hipSuccess;
-    };
+    auto go = [&](auto kernel, unsigned nt, dim3 g) { return launch_kernel(kernel, p, nt, g, lds, stream); };
     if (real && two_frames) {
 #ifndef SGX_KM_REAL1
         switch (fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) \
-    case Pn: go(stft_mixed_real2_bands_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2>, 2 * N, dim3((grid.x + 1) / 2, 1)); break;
+    case Pn: return go(stft_mixed_real2_bands_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2>, 2 * N, dim3((grid.x + 1) / 2, 1));
             MIX_REAL2_RENDER_PLANS(X)
 #undef X
         default: break;
         }
 #endif
-        return err;
+        return hipErrorNotSupported;
     }
     switch (fixed) {
-#define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N)                                                                                                   \
-    case Pn:                                                                                                                                       \
-        if (real) go(stft_mixed_fixed4_bands_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, N, grid);   \
-        else go(stft_mixed_fixed4_bands_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, N, grid);      \
-        break;
+#define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N)                                                                                                          \
+    case Pn:                                                                                                                                              \
+        if (real) return go(stft_mixed_fixed4_bands_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, N, grid);   \
+        return go(stft_mixed_fixed4_bands_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, N, grid);
         MIX_FIXED4_PLANS(X)
 #undef X
     default: break;
     }
-    if (real || err != hipErrorNotSupported) return err;
+    if (real) return hipErrorNotSupported;
     switch (fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) \
-    case Pn: go(stft_mixed_fixed_bands_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, N, grid); break;
+    case Pn: return go(stft_mixed_fixed_bands_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, N, grid);
         MIX_FIXED_PLANS(X)
 #undef X
     default: break;
     }
-    return err;
+    return hipErrorNotSupported;
 }
 
 }  // namespace mix

@@ -1,7 +1,7 @@
 // stft_mixed_complex.hip -- the complex-row instantiations of the mixed-radix and chirp-z kernels (sgx_stft_batch_complex): the same
 // transforms as stft_mixed.hip's row kernels, then the (l, r) split -- or real-input mode's untangle -- stored as complex spectra, (L, R) as
 // float4 per bin.  A translation unit of its own that takes stft_mixed.hip's device code and none of its host code, as
-// stft_mixed_bands.hip does: the magnitude kernels there are to stay exactly what they are.
+// stft_mixed_bands.hip does.
 #define SGX_MIXED_KERNELS_ONLY 1
 #include "stft_mixed.hip"
 
@@ -68,7 +68,7 @@ __device__ __forceinline__ void untangle_store_c64(const Params &p, const float2
     }
 }
 
-// stft_mixed_kernel (run-time geometry) with the complex store
+// stft_mixed_kernel (run-time geometry) with the complex store.  (A copy, as the chirp-z kernels below: see fixed3_body in stft_mixed.hip.)
 __global__ void __launch_bounds__(1024) stft_mixed_complex_kernel(Params p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -104,41 +104,25 @@ __global__ void __launch_bounds__(1024) stft_mixed_complex_kernel(Params p)
 }
 
 // stft_mixed_fixed_kernel / stft_mixed_fixed4_kernel (compile-time plans) without the pixel epilogue, with the complex store
+struct ComplexRows {
+    template <typename F, bool REAL>
+    static __device__ __forceinline__ void run(const Params &p, float2 *s, uint32_t pair, long long row_a, long long row_b, uint32_t tid)
+    {
+        if constexpr (REAL) untangle_store_c64(p, s, row_a, tid, F::NT);   // P is the WINDOW here
+        else split_store_c64(p, s, pair, row_a, row_b, tid, F::NT);
+    }
+};
+
 template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, bool REAL>
 __global__ void __launch_bounds__(F::NT, F::NT <= 256 ? 4 : 8) stft_mixed_fixed_complex_kernel(Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float2 *s = reinterpret_cast<float2 *>(smem_raw);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t pair = blockIdx.y;
-    long long row_a, row_b;
-    Source src;
-    frame_source(p, pair, src, row_a, row_b);
-    using G0 = FixGeo<F::M0, F::P / F::R0, F::pp(F::M0), F::pp(F::P), F::W, F::PAD, F::NT, true>;
-    stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
-    stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
-    stage<R2A, R2B>(s, p, p.tw, FixGeo<1, F::P / F::R2, 1, F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
-    if constexpr (REAL) untangle_store_c64(p, s, row_a, tid, F::NT);   // P is the WINDOW here
-    else split_store_c64(p, s, pair, row_a, row_b, tid, F::NT);
+    fixed3_body<F, R0A, R0B, R1A, R1B, R2A, R2B, REAL, ComplexRows>(p);
 }
 
 template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B, int R3A, int R3B, bool REAL>
 __global__ void __launch_bounds__(F::NT, F::NT == 256 ? 4 : (F::NT == 512 ? 8 : 4)) stft_mixed_fixed4_complex_kernel(Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float2 *s = reinterpret_cast<float2 *>(smem_raw);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t pair = blockIdx.y;
-    long long row_a, row_b;
-    Source src;
-    frame_source(p, pair, src, row_a, row_b);
-    using G0 = FixGeo<F::M0, F::P / F::R0, F::pp(F::M0), F::pp(F::P), F::W, F::PAD, F::NT, true>;
-    stage<R0A, R0B, G0, REAL>(s, p, p.tw, G0{}, src, tid);
-    stage<R1A, R1B>(s, p, p.tw + F::TW1, FixGeo<F::M1, F::P / F::R1, F::pp(F::M1), F::pp(F::M0), F::W, F::PAD, F::NT, false>{}, src, tid);
-    stage<R2A, R2B>(s, p, p.tw + F::TW2, FixGeo<F::M2, F::P / F::R2, F::pp(F::M2), F::pp(F::M1), F::W, F::PAD, F::NT, false>{}, src, tid);
-    stage<R3A, R3B>(s, p, p.tw, FixGeo<1, F::P / F::R3, 1, F::pp(F::M2), F::W, F::PAD, F::NT, false>{}, src, tid);
-    if constexpr (REAL) untangle_store_c64(p, s, row_a, tid, F::NT);
-    else split_store_c64(p, s, pair, row_a, row_b, tid, F::NT);
+    fixed4_body<F, R0A, R0B, R1A, R1B, R2A, R2B, R3A, R3B, REAL, ComplexRows>(p);
 }
 
 // chirpz3_kernel / chirpz4_kernel with the complex store
@@ -197,33 +181,22 @@ __global__ void __launch_bounds__(F::NT, 4) chirpz4_complex_kernel(Params p)
     else split_store_c64(p, s, pair, row_a, row_b, tid, F::NT);
 }
 
-template <typename K>
-static hipError_t go_complex(K kernel, const Params &p, unsigned nt, dim3 grid, size_t lds, hipStream_t stream)
-{
-    if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, stream, p);
-    return hipSuccess;
-}
-
 hipError_t launch_complex_kernel(const Params &p, int fixed, bool real, unsigned threads, dim3 grid, size_t lds, hipStream_t stream)
 {
     switch (fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N)                                                                                                      \
     case Pn:                                                                                                                                  \
-        if (real) return go_complex(stft_mixed_fixed_complex_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, p, N, grid, lds, stream); \
-        return go_complex(stft_mixed_fixed_complex_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, p, N, grid, lds, stream);
+        if (real) return launch_kernel(stft_mixed_fixed_complex_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, p, N, grid, lds, stream); \
+        return launch_kernel(stft_mixed_fixed_complex_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, p, N, grid, lds, stream);
         MIX_FIXED_PLANS(X)
 #undef X
 #define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N)                                                                                                               \
     case Pn:                                                                                                                                                   \
-        if (real) return go_complex(stft_mixed_fixed4_complex_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, p, N, grid, lds, stream); \
-        return go_complex(stft_mixed_fixed4_complex_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, p, N, grid, lds, stream);
+        if (real) return launch_kernel(stft_mixed_fixed4_complex_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, p, N, grid, lds, stream); \
+        return launch_kernel(stft_mixed_fixed4_complex_kernel<Fixed4<Pn, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, p, N, grid, lds, stream);
         MIX_FIXED4_PLANS(X)
 #undef X
-    default: return go_complex(stft_mixed_complex_kernel, p, threads, grid, lds, stream);
+    default: return launch_kernel(stft_mixed_complex_kernel, p, threads, grid, lds, stream);
     }
 }
 
@@ -232,14 +205,14 @@ hipError_t launch_chirpz_complex_kernel(const Params &p, uint32_t L, bool real, 
     switch (L) {
 #define X(Ln, A0, B0, A1, B1, A2, B2, N)                                                                                                    \
     case Ln:                                                                                                                                \
-        if (real) return go_complex(chirpz3_complex_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, p, N, grid, lds, stream); \
-        return go_complex(chirpz3_complex_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, p, N, grid, lds, stream);
+        if (real) return launch_kernel(chirpz3_complex_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, true>, p, N, grid, lds, stream); \
+        return launch_kernel(chirpz3_complex_kernel<Fixed3<Ln, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2, false>, p, N, grid, lds, stream);
         CHIRP_PLANS3(X)
 #undef X
 #define X(Ln, A0, B0, A1, B1, A2, B2, A3, B3, N)                                                                                                           \
     case Ln:                                                                                                                                               \
-        if (real) return go_complex(chirpz4_complex_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, p, N, grid, lds, stream); \
-        return go_complex(chirpz4_complex_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, p, N, grid, lds, stream);
+        if (real) return launch_kernel(chirpz4_complex_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, true>, p, N, grid, lds, stream); \
+        return launch_kernel(chirpz4_complex_kernel<Fixed4<Ln, A0, B0, A1, B1, A2, B2, A3, B3, N>, A0, B0, A1, B1, A2, B2, A3, B3, false>, p, N, grid, lds, stream);
         CHIRP_PLANS4(X)
 #undef X
     default: return hipErrorInvalidValue;
