@@ -332,16 +332,21 @@ __device__ __forceinline__ uchar4 color_for(const RenderParams &p, const float *
 }
 
 // Replaces the body of `for py in 0..buffer.height()` (simple_spectrogram.rs:141-161).
+// STAGED: the column's magnitudes are copied into LDS first.  A column that no LDS holds (W beyond about 20 000: the long windows of
+// SGX_FLAG_LARGE_TRANSFORM) is read where it lies; the arithmetic, and so every byte of the result, is the same.
+template <bool STAGED>
 __global__ void __launch_bounds__(256) render_kernel(RenderParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float2 *m = reinterpret_cast<float2 *>(smem_raw);                 // [M]
-    float *thr = reinterpret_cast<float *>(m + p.M + 1);              // [n_lut - 1]
+    float2 *stage = reinterpret_cast<float2 *>(smem_raw);             // [M] (STAGED)
+    float *thr = STAGED ? reinterpret_cast<float *>(stage + p.M + 1) : reinterpret_cast<float *>(smem_raw);   // [n_lut - 1]
     float *athr = thr + p.n_lut;                                      // [255]
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     const size_t col = blockIdx.x;
     const float2 *src = reinterpret_cast<const float2 *>(p.mags) + col * p.M;
-    for (uint32_t i = tid; i < p.M; i += nt) m[i] = src[i];
+    if (STAGED)
+        for (uint32_t i = tid; i < p.M; i += nt) stage[i] = src[i];
+    const float2 *m = STAGED ? stage : src;
     for (uint32_t i = tid; i + 1 < p.n_lut; i += nt) thr[i] = p.lut_thr[i];
     for (uint32_t i = tid; i < 255; i += nt) athr[i] = p.alpha_thr[i];
     __syncthreads();
@@ -691,9 +696,12 @@ hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns
 #undef SGX_TWO_PASS
         if (e2 != hipErrorNotSupported) return e2;   // (not supported: the image was refused; nothing was launched)
     }
-    const size_t lds = (size_t)(c->M + 1) * sizeof(float2) + (size_t)(c->pal.n + 255) * sizeof(float);
+    const size_t tables = (size_t)(c->pal.n + 255) * sizeof(float);
+    const bool staged = (size_t)(c->M + 1) * sizeof(float2) + tables <= lds_cap;   // else: the column is read from global memory
+    const size_t lds = (staged ? (size_t)(c->M + 1) * sizeof(float2) : 0) + tables;
+    const auto kernel = staged ? render_kernel<true> : render_kernel<false>;
     if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(render_kernel),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
@@ -704,7 +712,7 @@ hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns
         RenderParams q = p;
         q.mags = d_mags + done * (size_t)c->M * 2;
         q.rgba = d_rgba + done * (size_t)c->R * 4;
-        hipLaunchKernelGGL(render_kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         done += chunk;
@@ -725,15 +733,20 @@ struct BandsParams {
     uint32_t M, n_ranges, interp;
 };
 
+// (STAGED: as render_kernel -- a column that no LDS holds is read where it lies)
+template <bool STAGED>
 __global__ void __launch_bounds__(256) magnitude_in_kernel(BandsParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float2 *m = reinterpret_cast<float2 *>(smem_raw);
+    float2 *stage = reinterpret_cast<float2 *>(smem_raw);
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     const size_t col = blockIdx.x;
     const float2 *src = reinterpret_cast<const float2 *>(p.mags) + col * p.M;
-    for (uint32_t i = tid; i < p.M; i += nt) m[i] = src[i];
-    __syncthreads();
+    if (STAGED) {
+        for (uint32_t i = tid; i < p.M; i += nt) stage[i] = src[i];
+        __syncthreads();
+    }
+    const float2 *m = STAGED ? stage : src;
     const int32_t last = (int32_t)p.M - 1;
     float2 *dst = reinterpret_cast<float2 *>(p.out) + col * p.n_ranges;
     for (uint32_t b = tid; b < p.n_ranges; b += nt) {
@@ -775,9 +788,12 @@ hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_c
     p.M = c->M;
     p.n_ranges = n_ranges;
     p.interp = c->cfg.interp;
-    const size_t lds = (size_t)(c->M + 1) * sizeof(float2);
+    const size_t lds_cap = c->lds_optin < (size_t)160 * 1024 ? c->lds_optin : (size_t)160 * 1024;
+    const bool staged = (size_t)(c->M + 1) * sizeof(float2) <= lds_cap;   // else: the column is read from global memory
+    const size_t lds = staged ? (size_t)(c->M + 1) * sizeof(float2) : 0;
+    const auto kernel = staged ? magnitude_in_kernel<true> : magnitude_in_kernel<false>;
     if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(magnitude_in_kernel),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
@@ -787,7 +803,7 @@ hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_c
         BandsParams q = p;
         q.mags = d_mags + done * (size_t)c->M * 2;
         q.out = d_out + done * (size_t)n_ranges * 2;
-        hipLaunchKernelGGL(magnitude_in_kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -1,0 +1,538 @@
+"""Where the batch entry points read and write: every route of tests/edge_signals.py:ROUTES with its buffers inside guarded arenas
+(tests/bounds_arena.py), all through SpectrogramEngine and the C ABI.
+
+The tuned kernels address the stream and the rows through buffer descriptors whose record counts do the clipping; a count that is one
+frame, one channel or one row too generous gives correct results wherever the caller allocates exactly what the call needs.  Here
+  A  every output lies between two guards, prefilled with +inf and then with all ones, at 16-byte and at 8-modulo-16 alignment: the
+     payload must hold the bits of a clean run, both guards must be untouched and no prefill may survive;
+  B  the stream lies inside a NaN arena and every sample outside the ones the requested frames own is NaN as well;
+  C  one context runs every entry point on an overflowing and on an all-NaN stream before the real one (workspace, partial peak
+     columns, kernel 11's scratch, the inverse's tables);
+  D  the pixel-stage entry points (render_mags, render_bands, magnitude_in) get the same arenas;
+  E  the chunk loops over the 192 MiB workspace are crossed, a peak column accumulating over several chunks included.
+All of it is bit for bit against a clean baseline (the whole stream through a fresh engine on fresh, exact-size tensors), and the
+baseline's rows are held to the float64 truth on three frames at the bound the project holds white noise to.  No skips: a (row, entry
+point) pair is left out only through EXPECTED_UNSUPPORTED, and the library must refuse exactly those.  Run with -m gpu on an MI355X."""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import bounds_arena as ba
+import edge_signals as es
+import oracle
+from conftest import chirpz_bound, mags_error
+from spectrogram_rs_amd import SpectrogramEngine, _lib
+from test_gpu_peak import amax_groups, same
+
+pytestmark = pytest.mark.gpu
+
+ROWS = [r.name for r in es.ROUTES]
+VARIANTS = ["aligned", "odd"]
+KINDS = ["stft", "f16", "complex", "render", "bands", "peak_1", "peak_3", "peak_n", "peak_n5"]
+ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "istft": "f32", "magnitude_in": "f32",
+        "render_mags": "u8", "render_bands": "u8"}
+# the only (row, entry point) pairs this file leaves out: the library must answer SGX_ERR_UNSUPPORTED / istft_supported() == 0 for
+# exactly these (test_expected_unsupported), any other refusal fails the test that meets it
+EXPECTED_UNSUPPORTED = {(r.name, "istft") for r in es.ROUTES if r.kernel == 11}
+INVERSE_ROWS = [n for n in ROWS if (n, "istft") not in EXPECTED_UNSUPPORTED]
+# the rows whose column of magnitudes no LDS holds ((M + 1) * 8 bytes against the 160 KB of a workgroup): the pixel and bands stages read
+# them from global memory, in instantiations of their own (render_kernel<false>, magnitude_in_kernel<false>)
+# (the launchers compare with min(the device's opt-in LDS, 160 KB), and launch_render adds its threshold tables, (n_lut + 255) * 4
+# bytes -- about 2 KB with a built-in gradient -- to the column first.  So a row whose column lies within UNSTAGED_TABLES_MARGIN below
+# the limit may go either way and must not be added to ROUTES without deriving this list anew: test_unstaged_rows_are_the_long_windows
+# fails on one.)
+UNSTAGED_TABLES_MARGIN = 8 << 10
+UNSTAGED_ROWS = [r.name for r in es.ROUTES if r.W * 8 > 160 << 10]
+_cache = {}
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    """torch, and the end of this module's engines: the cases built on the way (45 engines with their streams and baselines, the W 2^20
+    row among them) are closed and dropped before the next test file runs"""
+    import torch
+    assert torch.cuda.is_available(), "these tests need the GPU"
+    yield torch
+    torch.cuda.synchronize()
+    for v in _cache.values():
+        (v.eng if isinstance(v, SimpleNamespace) else v).close()
+    _cache.clear()
+    torch.cuda.empty_cache()
+
+
+def engine(r, **extra):
+    return SpectrogramEngine(es.SR, device=0, **r.engine_kwargs(), **extra)
+
+
+def elem_of(kind):
+    return ELEM["bands" if kind.startswith("peak") else kind]
+
+
+def dtype_of(torch, kind):
+    return {"f32": torch.float32, "f16": torch.float16, "u8": torch.uint8}[elem_of(kind)]
+
+
+def group_of(kind, n):
+    return {"peak_1": 1, "peak_3": 3, "peak_n": n, "peak_n5": n + 5}[kind]
+
+
+def rows_of(kind, n):
+    return -(-n // group_of(kind, n)) if kind.startswith("peak") else n
+
+
+def row_bytes(eng, kind):
+    if kind in ("stft", "f16", "complex"):
+        return eng.pairs * eng.M * {"stft": 8, "f16": 4, "complex": 16}[kind]
+    return eng.pairs * eng.R * (4 if kind == "render" else 8)
+
+
+def run(eng, kind, dev, first, n, out=None):
+    if kind == "stft":
+        return eng.stft_batch(dev, first, n, out=out)
+    if kind == "f16":
+        return eng.stft_batch_f16(dev, first, n, out=out)
+    if kind == "complex":
+        return eng.stft_batch_complex(dev, first, n, out=out)
+    if kind == "render":
+        return eng.render_batch(dev, first, n, out=out)
+    if kind == "bands":
+        return eng.bands_batch(dev, first, n, out=out)
+    return eng.bands_peak_batch(dev, group_of(kind, n), first, n, out=out)
+
+
+def words(torch, t):
+    """any result as flat int32 words"""
+    if t.dtype == torch.complex64:
+        t = torch.view_as_real(t)
+    return t.contiguous().view(-1).view(torch.int32)
+
+
+class Arena:
+    """[front guard | payload | back guard] in one int32 allocation (bounds_arena.layout); `guard` fills both guards, `fill` the payload"""
+
+    def __init__(self, torch, payload_bytes, row_bytes_, odd, fill, guard=ba.GUARD_WORD, mod4=False):
+        slack = 16
+        self.torch, self.guard = torch, ba.as_i32(guard)
+        self.words = torch.full(((2 * ba.guard_bytes(row_bytes_) + payload_bytes + slack) // 4,), self.guard, dtype=torch.int32, device="cuda")
+        base = self.words.data_ptr()
+        assert base % 8 == 0
+        lay = ba.layout(payload_bytes, row_bytes_, odd, base % 16, mod4=mod4)
+        assert lay.total_bytes <= self.words.numel() * 4
+        self.lo, self.hi = lay.payload_offset // 4, lay.back_offset // 4
+        self.words[self.lo:self.hi] = ba.as_i32(fill)
+        at = base + lay.payload_offset
+        assert at % 8 == 4 if mod4 else at % 16 == (8 if odd else 0), "the payload is not where the variant puts it"
+
+    def payload(self, dtype=None):
+        p = self.words[self.lo:self.hi]
+        return p if dtype is None else p.view(dtype)
+
+    def guards_intact(self):
+        return bool((self.words[:self.lo] == self.guard).all()) and bool((self.words[self.hi:] == self.guard).all())
+
+
+def to_dev(torch, r, pcm):
+    """a fresh, exact-size stream (the align4 row: 4 but not 8 bytes aligned, as tests/test_gpu_edges.py places it)"""
+    flat = torch.from_numpy(np.ascontiguousarray(pcm, np.float32).reshape(-1)).cuda()
+    if not r.align4:
+        return flat
+    buf = torch.zeros(flat.numel() + 1, dtype=torch.float32, device="cuda")
+    buf[1:] = flat
+    assert buf[1:].data_ptr() % 8 == 4
+    return buf[1:]
+
+
+def frames_of(r):
+    return 5 if r.W >= 65536 else max(9, r.min_frames)
+
+
+def case(torch, name):
+    """The row's engine (its kernel and render_path bits asserted first, as tests/test_gpu_edges.py::test_route does), its noise stream
+    and the clean baseline of every entry point, built once and never changed."""
+    if name in _cache:
+        return _cache[name]
+    r = es.ROUTE[name]
+    eng = engine(r, gradient="viridis")
+    info = eng.info
+    assert info.stft_kernel == r.kernel, (name, info.stft_kernel)
+    assert info.render_path & r.bits_set == r.bits_set and info.render_path & r.bits_clear == 0, (name, info.render_path)
+    if r.bands_fused is not None:
+        assert eng.bands_fused == r.bands_fused, (name, eng.bands_fused)
+    W, H, Cn = r.W, r.H, r.channels
+    F = frames_of(r)
+    N = (F - 1) * H + W
+    pcm = (oracle.white_noise(N * Cn, seed=0x5EED0900 + ROWS.index(name)) * np.float32(0.25)).reshape(N, Cn)
+    dev = to_dev(torch, r, pcm)
+    cs = SimpleNamespace(r=r, eng=eng, F=F, N=N, pcm=pcm, dev=dev, base={}, flat={})
+    for kind in ("stft", "f16", "complex", "render", "bands"):
+        cs.base[kind] = run(eng, kind, dev, 0, F)
+        cs.flat[kind] = words(torch, cs.base[kind])
+        assert cs.base[kind].shape[0] == F
+    # the anchor of every bit-identity below: the baseline's rows against the float64 truth on the first, the middle and the last frame
+    got = cs.base["stft"].cpu().numpy()
+    bound = chirpz_bound(W) if r.kernel == 4 else 1.0
+    for t in (0, F // 2, F - 1):
+        for p in range(r.pairs):
+            ref = es.truth_frame(es.frame_lr(pcm[t * H:t * H + W], p), W)
+            if r.paired:   # (two frames of one transform: against the pair's peak, include/sgx.h)
+                q = t ^ 1
+                partner = float(np.abs(es.truth_frame(es.frame_lr(pcm[q * H:q * H + W], p), W)).max()) if q < F else 0.0
+                err = es.pair_error(got[t, p], ref, r.floor, partner)
+            else:
+                err = mags_error(got[t, p], ref, r.floor)
+            assert err <= bound, (name, t, p, err, "the baseline itself misses the float64 truth")
+    # the inverse, where the library serves it
+    cs.istft = eng.istft_supported()
+    assert (cs.istft == 0) == ((name, "istft") in EXPECTED_UNSUPPORTED), (name, cs.istft)
+    if cs.istft:
+        cs.spec = torch.view_as_real(cs.base["complex"]).contiguous()
+        cs.base["istft"] = eng.istft_batch(cs.spec).clone()
+        assert cs.base["istft"].shape == (N, Cn)
+        cs.flat["istft"] = words(torch, cs.base["istft"])
+    # a second copy of the stream with the longest ragged tail (H - 1 samples that belong to no frame) for the output-side families
+    tail = (oracle.white_noise((H - 1) * Cn, seed=77) * np.float32(0.25)).reshape(H - 1, Cn)
+    cs.dev_ragged = to_dev(torch, r, np.concatenate([pcm, tail], 0))
+    torch.cuda.synchronize()
+    _cache[name] = cs
+    return cs
+
+
+def calls_of(cs):
+    F = cs.F
+    calls = [(0, F), (0, 1), (1, 1), (1, F - 1), (2, 3), (F - 1, 1)]
+    if cs.r.chunk_targets:   # one range straddling each frame next to a scratch-chunk boundary of the full run
+        for b in es.chunk_boundary_frames(cs.r.W, cs.r.pairs, F):
+            first = max(b - 1, 0)
+            calls.append((first, min(3, F - first)))
+    return calls
+
+
+def want_peak(cs, kind, first, n):
+    bands = cs.base["bands"][first:first + n]
+    g = group_of(kind, n)
+    return bands if g == 1 else amax_groups(bands, g)
+
+
+def check_result(torch, cs, kind, first, n, got_words, what):
+    """got_words (flat int32) against the baseline's rows [first, first + n): bit for bit; peak columns with test_gpu_peak.same against
+    amax_groups of the baseline bands"""
+    if kind.startswith("peak"):
+        want = want_peak(cs, kind, first, n)
+        assert got_words.numel() == want.numel(), what
+        assert same(got_words.view(torch.float32), want), what
+    else:
+        rw = row_bytes(cs.eng, kind) // 4
+        assert torch.equal(got_words, cs.flat[kind][first * rw:(first + n) * rw]), what
+
+
+def check_arena(arena, prefill, what):
+    assert arena.guards_intact(), (what, "a guard was written")
+    assert not bool((arena.payload() == ba.as_i32(prefill)).any()), (what, "a payload word still holds the prefill")
+
+
+def test_expected_unsupported(torch_cuda):
+    torch = torch_cuda
+    assert {k for _, k in EXPECTED_UNSUPPORTED} == {"istft"}
+    for name in ROWS:
+        if (name, "istft") not in EXPECTED_UNSUPPORTED:
+            continue
+        cs = case(torch, name)
+        assert cs.istft == 0
+        spec = torch.view_as_real(cs.base["complex"]).contiguous()
+        out = torch.zeros(cs.N * cs.r.channels, dtype=torch.float32, device="cuda")
+        got = C.c_size_t(99)
+        rc = cs.eng._lib.sgx_istft_batch(cs.eng._ctx, C.c_void_p(spec.data_ptr()), cs.F, 0, cs.N, C.c_void_p(out.data_ptr()), C.byref(got))
+        assert rc == _lib.SGX_ERR_UNSUPPORTED and got.value == 0, (name, rc)
+        assert not bool(out.any())
+
+
+def test_unstaged_rows_are_the_long_windows():
+    assert UNSTAGED_ROWS == ["large_w1m_lr", "large_w65537_chirp_lr"]
+    # every other row is staged by both launchers, the tables of launch_render included: none lies in the margin below the limit
+    assert max(r.W for r in es.ROUTES if r.name not in UNSTAGED_ROWS) * 8 <= (160 << 10) - UNSTAGED_TABLES_MARGIN
+
+
+@pytest.mark.parametrize("name", UNSTAGED_ROWS)
+def test_unstaged_pixel_stage_against_the_oracle(torch_cuda, name):
+    """The baselines of render_batch and bands_batch on these rows come from the kernels that read the column from global memory, and
+    every arena run is compared with those baselines: here they, and render_mags / magnitude_in of the engine's own rows, are held to
+    the CPU oracle's pixel stage over those rows, bit for bit (as tests/test_gpu_large.py and tests/test_gpu_bands.py do where the column
+    fits in LDS)."""
+    torch = torch_cuda
+    from spectrogram_rs_amd import builtin_gradient
+    cs = case(torch, name)
+    eng, F = cs.eng, cs.F
+    assert eng.pairs == 1 and eng.info.render_path & 1 == 0 and eng.bands_fused == 0
+    sr = eng.info.sample_rate_u32
+    mags = cs.base["stft"][:, 0].contiguous()          # [F][M][2]
+    rows = mags.cpu().numpy()
+    # pixels: render_batch's column, render_mags of the engine's rows, the oracle's pixels of them
+    own = eng.render_mags(mags).cpu().numpy()
+    assert np.array_equal(cs.base["render"].cpu().numpy()[:, 0], own), (name, "render_batch differs from render_mags of stft_batch's rows")
+    want = oracle.render_columns(rows, sr, builtin_gradient("viridis"), R=eng.R)
+    assert np.array_equal(own, want), (name, "render_mags differs from the oracle")
+    # bands: bands_batch's column, magnitude_in of the engine's rows over the row ranges, the oracle's means of them
+    ends = eng.bin_edges()
+    got = eng.magnitude_in(mags, np.stack([ends[:-1], ends[1:]], 1)).cpu().numpy().reshape(F, eng.R, 2)
+    assert np.array_equal(cs.base["bands"].cpu().numpy()[:, 0].view(np.uint32), got.view(np.uint32)), (name, "bands_batch differs from magnitude_in")
+    for t in range(F):
+        ref = np.stack([oracle.magnitude_in(rows[t], sr, float(ends[py]), float(ends[py + 1])) for py in range(eng.R)])
+        assert np.array_equal(got[t].view(np.uint32), ref.view(np.uint32)), (name, t, "magnitude_in differs from the oracle")
+
+
+# ---- A: output guards ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("name", ROWS)
+def test_output_guards(torch_cuda, name, kind, variant):
+    torch = torch_cuda
+    cs = case(torch, name)
+    rb = row_bytes(cs.eng, kind)
+    for first, n in calls_of(cs):
+        for second in (False, True):
+            prefill = ba.prefill_word(elem_of(kind), second)
+            arena = Arena(torch, rows_of(kind, n) * rb, rb, variant == "odd", prefill)
+            run(cs.eng, kind, cs.dev_ragged, first, n, out=arena.payload(dtype_of(torch, kind)))
+            what = (name, kind, variant, first, n, "all ones" if second else "+inf")
+            check_result(torch, cs, kind, first, n, arena.payload(), what)
+            check_arena(arena, prefill, what)
+
+
+def istft_ranges(cs):
+    N, W, H = cs.N, cs.r.W, cs.r.H
+    return [(0, N), (1, 1), (W - 1, H + 1), (N - 3, 3), (H, 2 * H + 1)]
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("name", INVERSE_ROWS)   # (the rows left out: test_expected_unsupported)
+def test_inverse_output_guards(torch_cuda, name, variant):
+    torch = torch_cuda
+    cs = case(torch, name)
+    assert cs.istft == 1
+    Cn = cs.r.channels
+    for a, n in istft_ranges(cs):
+        assert a + n <= cs.N
+        for second in (False, True):
+            prefill = ba.prefill_word("f32", second)
+            arena = Arena(torch, n * Cn * 4, Cn * 4, variant == "odd", prefill)
+            cs.eng.istft_batch(cs.spec, first_sample=a, max_samples=n, out=arena.payload(torch.float32))
+            what = (name, "istft", variant, a, n, "all ones" if second else "+inf")
+            assert torch.equal(arena.payload(), cs.flat["istft"][a * Cn:(a + n) * Cn]), what
+            check_arena(arena, prefill, what)
+
+
+# ---- B: input isolation -------------------------------------------------------------------------------------------------------------
+def poisoned_stream(torch, cs, odd, tail, lo, hi):
+    """The stream plus `tail` ragged samples as the payload of a NaN arena, every sample outside [lo, hi) NaN as well; the slice handed
+    to the library ends with the tail, so n_samples is short of what lies behind it."""
+    r = cs.r
+    arena = Arena(torch, (cs.N + tail) * r.channels * 4, r.W * r.channels * 4, odd, ba.NAN_WORD, guard=ba.NAN_WORD, mod4=r.align4)
+    dev = arena.payload(torch.float32)
+    dev[lo * r.channels:hi * r.channels] = cs.dev[lo * r.channels:hi * r.channels]
+    return arena, dev
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("name", ROWS)
+def test_input_isolation(torch_cuda, name, kind):
+    torch = torch_cuda
+    cs = case(torch, name)
+    r = cs.r
+    for variant in (VARIANTS if r.channels >= 2 else VARIANTS[:1]):   # (mono: the align4 row is the odd placement)
+        for tail in sorted({0, 1, r.H - 1}):
+            for first, n in calls_of(cs):
+                lo, hi = ba.needed_samples(r, first, n)
+                hi = min(hi, cs.N)   # (a partner frame the stream does not hold has no samples)
+                arena, dev = poisoned_stream(torch, cs, variant == "odd", tail, lo, hi)
+                assert cs.eng.num_frames(dev.numel() // r.channels) == cs.F
+                got = run(cs.eng, kind, dev, first, n)
+                check_result(torch, cs, kind, first, n, words(torch, got), (name, kind, variant, tail, first, n))
+
+
+@pytest.mark.parametrize("name", INVERSE_ROWS)
+def test_inverse_input_isolation(torch_cuda, name):
+    torch = torch_cuda
+    cs = case(torch, name)
+    assert cs.istft == 1
+    r = cs.r
+    W, H, Cn = r.W, r.H, r.channels
+    per_frame = r.pairs * (W - 1) * 4
+    for variant in VARIANTS:
+        for a, n in istft_ranges(cs):
+            arena = Arena(torch, cs.F * per_frame * 4, per_frame * 4, variant == "odd", ba.NAN_WORD, guard=ba.NAN_WORD)
+            spec = arena.payload(torch.float32).view(cs.F, r.pairs, W - 1, 2, 2)
+            used = [t for t in range(cs.F) if t * H < a + n and t * H + W > a]   # the frames that cover a requested sample
+            assert used
+            spec[used[0]:used[-1] + 1] = cs.spec[used[0]:used[-1] + 1]
+            if Cn == 1:
+                spec[:, :, :, 1, :] = float("nan")   # mono: one channel from the L half (include/sgx.h)
+            got = cs.eng.istft_batch(spec, first_sample=a, max_samples=n)
+            assert torch.equal(words(torch, got), cs.flat["istft"][a * Cn:(a + n) * Cn]), (name, variant, a, n)
+
+
+# ---- C: stale state -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ROWS)
+def test_stale_state(torch_cuda, name):
+    torch = torch_cuda
+    cs = case(torch, name)
+    r, F = cs.r, cs.F
+    eng = engine(r, gradient="viridis")   # ONE context for the three runs
+    hot = to_dev(torch, r, np.full((cs.N, r.channels), 3e38, np.float32))          # the spectra overflow to inf
+    nan = to_dev(torch, r, np.full((cs.N, r.channels), np.nan, np.float32))
+    for stream in (hot, nan):
+        for kind in KINDS:
+            scratch = run(eng, kind, stream, 0, F)
+        if cs.istft:
+            eng.istft_batch(torch.view_as_real(eng.stft_batch_complex(stream)).contiguous())
+    del scratch
+    for kind in KINDS:
+        out = None
+        if kind.startswith("peak"):   # (a stale +inf would survive a max: what the buffer held before must not matter either)
+            out = torch.full((rows_of(kind, F), eng.pairs, eng.R, 2), float("inf"), dtype=torch.float32, device="cuda")
+        got = run(eng, kind, cs.dev, 0, F, out=out)
+        check_result(torch, cs, kind, 0, F, words(torch, got), (name, kind, "after an overflowing and an all-NaN stream"))
+    if cs.istft:
+        got = eng.istft_batch(cs.spec)
+        assert torch.equal(words(torch, got), cs.flat["istft"]), (name, "istft after non-finite spectra")
+    eng.close()
+
+
+# ---- D: the pixel-stage entry points ------------------------------------------------------------------------------------------------
+PIXEL_CONTEXTS = {
+    "w2048_mono": dict(window_samples=2048, hop_samples=256, channels=1),
+    "w4096_lr": dict(window_samples=4096, hop_samples=1000, channels=2),
+    "w300_lr": dict(window_samples=300, hop_samples=75, channels=2),
+    "w2048_rows7": dict(window_samples=2048, hop_samples=256, channels=1, rows=7),
+}
+PIXEL_RANGES = np.array([[32.0, 64.0], [100.0, 101.0], [440.0, 880.0], [1000.0, 12000.0], [20.0, 23999.0]], np.float32)
+
+
+def pixel_call(eng, entry, src, out=None):
+    if entry == "render_mags":
+        return eng.render_mags(src, out=out)
+    if entry == "render_bands":
+        return eng.render_bands(src, out=out)
+    return eng.magnitude_in(src, PIXEL_RANGES, out=out)
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("entry", ["render_mags", "render_bands", "magnitude_in"])
+@pytest.mark.parametrize("ctx", sorted(PIXEL_CONTEXTS))
+def test_pixel_stage(torch_cuda, ctx, entry, variant):
+    torch = torch_cuda
+    key = ("pixel", ctx)
+    if key not in _cache:
+        _cache[key] = SpectrogramEngine(es.SR, device=0, gradient="viridis", **PIXEL_CONTEXTS[ctx])
+    eng = _cache[key]
+    odd = variant == "odd"
+    rng = np.random.default_rng([len(ctx), len(entry)])
+    in_row = (eng.R if entry == "render_bands" else eng.M) * 2          # floats per input column
+    out_row = len(PIXEL_RANGES) * 8 if entry == "magnitude_in" else eng.R * 4   # bytes per output column
+    for cols in (1, 7, 700):   # 700: the persistent workgroups walk several columns each
+        # magnitudes from 1e-6 to 1: the whole of the colour ramp
+        host = (10.0 ** rng.uniform(-6.0, 0.0, (cols, in_row // 2, 2))).astype(np.float32)
+        exact_in = torch.from_numpy(host).cuda()
+        want = words(torch, pixel_call(eng, entry, exact_in))
+        src = Arena(torch, cols * in_row * 4, in_row * 4, odd, ba.NAN_WORD, guard=ba.NAN_WORD)
+        src.payload(torch.float32)[:] = exact_in.view(-1)
+        for second in (False, True):
+            prefill = ba.prefill_word(ELEM[entry], second)
+            arena = Arena(torch, cols * out_row, out_row, odd, prefill)
+            out = arena.payload(torch.uint8 if ELEM[entry] == "u8" else torch.float32)
+            pixel_call(eng, entry, src.payload(torch.float32).view(cols, in_row // 2, 2), out=out)
+            what = (ctx, entry, variant, cols, "all ones" if second else "+inf")
+            assert torch.equal(arena.payload(), want), what
+            check_arena(arena, prefill, what)
+        assert torch.equal(src.payload(torch.float32).view(-1), exact_in.view(-1)), "the input was written"
+
+
+# ---- E: chunk seams -----------------------------------------------------------------------------------------------------------------
+SEAM = dict(window_samples=8192, hop_samples=16, channels=2, rows=1024)
+
+
+def seam_engine():
+    eng = SpectrogramEngine(es.SR, device=0, gradient="viridis", **SEAM)
+    # the two-kernel routes through the workspace; a route or a constant other than bounds_arena restates fails here, nothing adapts
+    assert eng.info.stft_kernel == 10 and eng.info.render_path & 1 == 0 and eng.bands_fused == 0 and eng.bands_peak_fused == 0
+    assert (eng.W, eng.pairs, eng.R) == (8192, 1, 1024)
+    assert eng.info.mags_bytes_per_frame == ba.mags_bytes_per_frame(8192, 1)
+    return eng
+
+
+def test_seams_render_and_bands(torch_cuda):
+    torch = torch_cuda
+    eng = seam_engine()
+    chunk = ba.render_chunk(eng.W, eng.pairs)
+    assert chunk == ba.bands_chunk(eng.W, eng.pairs) == 3072   # 3072 frames of magnitudes fill the 192 MiB
+    F = 2 * chunk + 37
+    assert F > 2 * chunk
+    pcm = eng.white_noise(eng.W + (F - 1) * eng.H, seed=0x5EED0909)
+    whole = {"render": eng.render_batch(pcm), "bands": eng.bands_batch(pcm)}
+    rng = np.random.default_rng(909)
+    cuts = sorted(int(c) for c in rng.choice([f for f in range(1, F) if f % chunk], 5, replace=False))
+    edges = [0] + cuts + [F]
+    for kind in ("render", "bands"):
+        assert whole[kind].shape[0] == F
+        parts = [run(eng, kind, pcm, a, b - a) for a, b in zip(edges, edges[1:])]
+        assert torch.equal(words(torch, torch.cat(parts, 0)), words(torch, whole[kind])), (kind, cuts, "pieces differ from the whole")
+    ends = eng.bin_edges()
+    ranges = np.stack([ends[:-1], ends[1:]], 1)
+    for seam in (chunk, 2 * chunk):   # the six frames around each seam from sgx_stft_batch's own rows
+        rows = eng.stft_batch(pcm, seam - 3, 6).reshape(-1, eng.M, 2)
+        px = eng.render_mags(rows)
+        assert torch.equal(px.view(-1), whole["render"][seam - 3:seam + 3].reshape(-1)), ("render_batch", seam)
+        bands = eng.magnitude_in(rows, ranges)
+        assert torch.equal(words(torch, bands), words(torch, whole["bands"][seam - 3:seam + 3])), ("bands_batch", seam)
+
+
+def peak_against_bands(torch, eng, pcm, bands, first, groups):
+    n = bands.shape[0] - first
+    for g in groups:
+        cols = -(-n // g)
+        out = torch.full((cols, eng.pairs, eng.R, 2), float("inf"), dtype=torch.float32, device="cuda")
+        got = eng.bands_peak_batch(pcm, g, first_frame=first, out=out)
+        assert got.shape[0] == cols
+        assert same(got, amax_groups(bands[first:], g)), (first, g, "differs from amax over bands_batch")
+
+
+def test_seams_peak_workspace_route(torch_cuda):
+    torch = torch_cuda
+    eng = seam_engine()
+    F = 6000
+    pcm = eng.white_noise(eng.W + (F - 1) * eng.H, seed=0x5EED090A)
+    bands = eng.bands_batch(pcm)
+    assert bands.shape[0] == F
+    for first in (0, 3):
+        n = F - first
+        chunk = ba.peak_chunk(eng.W, eng.pairs, eng.R, n, n)
+        assert chunk == 2688 and n > 2 * chunk
+        loop = lambda g: ba.peak_chunks(eng.W, eng.pairs, eng.R, n, g)   # noqa: E731
+        # one column over three chunks; two columns, the second chunk trimmed to the end of column 0
+        assert [c[2:] for c in loop(n)] == [(0, False), (0, True), (0, True)]
+        assert loop(4000)[1] == (chunk, 4000 - chunk, 0, True) and loop(4000)[2][2:] == (1, False)
+        assert loop(chunk + 1)[1] == (chunk, 1, 0, True)
+        peak_against_bands(torch, eng, pcm, bands, first, [n, n + 5, 4000, chunk + 1, chunk, chunk - 1])
+
+
+def test_seams_peak_fused_route(torch_cuda):
+    torch = torch_cuda
+    eng = SpectrogramEngine(es.SR, device=0, window_samples=2048, hop_samples=256, channels=1)
+    # (the real-input kernel: two frames per job, as bounds_arena.fused_peak_run restates its split)
+    assert eng.bands_peak_fused == 1 and eng.info.render_path & 8 and eng.info.stft_kernel == es.ROUTE["k1r_h256"].kernel
+    F = 5000
+    pcm = eng.white_noise(eng.W + (F - 1) * eng.H, seed=0x5EED090B)
+    bands = eng.bands_batch(pcm)
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    # the seams of this route are the ends of the persistent workgroups' runs (bounds_arena.fused_peak_run: six frames each on 256 CUs):
+    # columns of one run, one frame more and one less, and the long ones the combine pass finishes
+    for first in (0, 3):
+        n = F - first
+        run = ba.fused_peak_run(n, n, n_cu)
+        assert 2 <= run and 2 * run < n, "more than two runs, each of more than one frame"
+        groups = [n, n + 5, 4000, run + 1, run, run - 1]
+        for g in groups:   # as the launcher splits THIS call: no group lengthens the run, so every one but `run` has columns across seams
+            assert ba.fused_peak_run(n, min(g, n), n_cu) == run, (g, "the run was aligned to the group")
+            assert (run % min(g, n) == 0) == (g == run or g == 1), (g, "no column of this group crosses a run's end")
+        peak_against_bands(torch, eng, pcm, bands, first, groups)
