@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle
+from length_sweep import mixed_radix_plan
 from spectrogram_rs_amd.fourier import AudioStreamTransform, AudioTransform, RingBuffer
 from spectrogram_rs_amd.log_scaling import LogCoordf64
 
@@ -79,49 +80,6 @@ def test_log_axis_matches_oracle_and_roundtrips():
         assert ax.map(ax.unmap(p, (0, 1024)), (0, 1024)) == p
     e = np.array([np.float32(ax.unmap(p, (0, 1024))) for p in range(1025)], np.float32)
     assert np.array_equal(e, oracle.bin_edges(1024))
-
-
-def mixed_radix_plan(P):
-    """csrc/stft_mixed.hip make_plan restated: P's factors 7, 5, 4 (pairs of twos), 3 and a last 2, grouped into stages of
-    one or two factors with a product <= 28 -- fewest stages, then the smallest largest radix, then the smallest sum."""
-    n, factors = P, []
-    for f in (7, 5):
-        while n % f == 0:
-            factors.append(f)
-            n //= f
-    threes = []
-    while n % 3 == 0:
-        threes.append(3)
-        n //= 3
-    while n % 4 == 0:
-        factors.append(4)
-        n //= 4
-    factors += threes
-    if n % 2 == 0:
-        factors.append(2)
-        n //= 2
-    if n != 1:
-        return None
-    factors.sort(reverse=True)
-    best = [None, None]
-
-    def search(rest, cur):
-        if not rest:
-            prods = [a * b for a, b in cur]
-            key = (len(cur), max(prods), sum(prods))
-            if best[0] is None or key < best[0]:
-                best[0], best[1] = key, list(cur)
-            return
-        f, rest = rest[-1], rest[:-1]
-        search(rest, cur + [(f, 1)])
-        for i, g in enumerate(rest):
-            if (i > 0 and rest[i] == rest[i - 1]) or f * g > 28:
-                continue
-            search(rest[:i] + rest[i + 1:], cur + [(max(f, g), min(f, g))])
-
-    search(factors, [])
-    odd = lambda g: (g[0] * g[1]) & (g[0] * g[1] - 1) != 0  # noqa: E731
-    return sorted(best[1], key=lambda g: (not odd(g), -(g[0] * g[1]) if odd(g) else g[0] * g[1]))
 
 
 def test_mixed_radix_plan_and_block_index_arithmetic_for_every_supported_length():
