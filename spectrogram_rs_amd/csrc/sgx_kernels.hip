@@ -385,6 +385,58 @@ __global__ void __launch_bounds__(256) render_kernel(RenderParams p)
     }
 }
 
+// The same kernel for a palette whose threshold tables no LDS holds (n_lut + 255 floats above 160 KiB: more than 40 705 entries;
+// sgx_set_gradient accepts 65536): the tables stay in global memory and count_reached bisects them there.  (A copy: with one body behind
+// both kernels, and again with only the row loop shared as a __forceinline__ function taking the two table pointers, render_kernel<true>
+// and <false> compile to other code than they had -- tools/isa_unchanged.py.  A change to the row loop goes into both.)
+template <bool STAGED>
+__global__ void __launch_bounds__(256) render_far_tables_kernel(RenderParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float2 *stage = reinterpret_cast<float2 *>(smem_raw);             // [M] (STAGED)
+    const float *thr = p.lut_thr, *athr = p.alpha_thr;                // [n_lut - 1], [255]: bisected where they lie
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    const size_t col = blockIdx.x;
+    const float2 *src = reinterpret_cast<const float2 *>(p.mags) + col * p.M;
+    if (STAGED)
+        for (uint32_t i = tid; i < p.M; i += nt) stage[i] = src[i];
+    const float2 *m = STAGED ? stage : src;
+    if (STAGED) __syncthreads();
+
+    const int32_t last = (int32_t)p.M - 1;
+    uchar4 *dst = reinterpret_cast<uchar4 *>(p.rgba) + col * p.R;
+    for (uint32_t py = tid; py < p.R; py += nt) {
+        const RowEntry row = p.rows[py];
+        float sl = 0.0f, sr = 0.0f;  // Complex::sum starts at zero (interpolated_frequency_sample.rs:70-72)
+        for (uint32_t i = 0; i < row.count; ++i) {
+            const SampleEntry se = p.samples[row.first + i];
+            float vl, vr;
+            if (p.interp == SGX_INTERP_COSINE) {
+                // :79-86  data[low] * (1 - o') + data[high] * o'
+                const float2 a = m[se.i0], b = m[se.i1];
+                vl = a.x * se.w1 + b.x * se.w2;
+                vr = a.y * se.w1 + b.y * se.w2;
+            } else {
+                // :89-105
+                const int32_t x1 = se.i0;
+                const int32_t x0 = x1 > 0 ? x1 - 1 : 0;
+                const int32_t x2 = x1 + 1 < last ? x1 + 1 : last;
+                const int32_t x3 = x1 + 2 < last ? x1 + 2 : last;
+                const float2 y0 = m[x0], y1 = m[x1], y2 = m[x2], y3 = m[x3];
+                const float mu = se.w0, mu2 = se.w1, mu3 = se.w2;
+                const float2 vv = cubic_pair(y0, y1, y2, y3, mu, mu2, mu3);
+                vl = vv.x; vr = vv.y;
+            }
+            sl = sl + vl;
+            sr = sr + vr;
+        }
+        const float l = sl / row.count_f, r = sr / row.count_f;  // :72
+
+        const uchar4 px = color_for(p, thr, athr, p.t_thr, p.lut_rgba, p.t_cell, l, r);
+        dst[p.R - 1 - py] = px;  // simple_spectrogram.rs:150
+    }
+}
+
 // The same column in two balanced passes over LDS (see stft4096_wg.hpp: one thread per magnitude_in SAMPLE,
 // then one thread per row), by persistent workgroups that keep the threshold tables in LDS and request the
 // next column's magnitudes while the current one is rendered.  Used whenever the column, its interpolated
@@ -696,10 +748,12 @@ hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns
 #undef SGX_TWO_PASS
         if (e2 != hipErrorNotSupported) return e2;   // (not supported: the image was refused; nothing was launched)
     }
-    const size_t tables = (size_t)(c->pal.n + 255) * sizeof(float);
+    const bool tables_lds = (size_t)(c->pal.n + 255) * sizeof(float) <= lds_cap;   // else: the thresholds are bisected in global memory
+    const size_t tables = tables_lds ? (size_t)(c->pal.n + 255) * sizeof(float) : 0;
     const bool staged = (size_t)(c->M + 1) * sizeof(float2) + tables <= lds_cap;   // else: the column is read from global memory
     const size_t lds = (staged ? (size_t)(c->M + 1) * sizeof(float2) : 0) + tables;
-    const auto kernel = staged ? render_kernel<true> : render_kernel<false>;
+    const auto kernel = tables_lds ? (staged ? render_kernel<true> : render_kernel<false>)
+                                   : (staged ? render_far_tables_kernel<true> : render_far_tables_kernel<false>);
     if (lds > 64 * 1024) {  // per launch: the attribute is per device, and a process may hold contexts on several
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -18,6 +18,8 @@ A Length names a window, the engine flags, the channel counts it runs with, and 
 render_path bits 2 (compile-time plan / chirp-z through the composite stages) and 3 (real-input mode, mono contexts only)."""
 from __future__ import annotations
 
+import os
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -105,6 +107,14 @@ MIX_FIXED = {
     9600: ((4, 3), (5, 2), (5, 1), (4, 4)), 19200: ((5, 3), (5, 1), (4, 4), (4, 4)), 17640: ((5, 3), (7, 2), (4, 3), (7, 1)),
     8192: ((4, 1), (4, 2), (4, 4), (4, 4)),
 }
+
+
+def macro(name):
+    """the X(...) argument lists of a #define in csrc/stft_mixed.hip, continuation lines included (the tests hold the tables here to them)"""
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spectrogram_rs_amd", "csrc", "stft_mixed.hip")
+    m = re.search(r"#define " + name + r"\(X\)((?:.*\\\n)*.*)\n", open(src).read())
+    assert m, name
+    return [tuple(int(v) for v in args.split(",")) for args in re.findall(r"X\(([^)]*)\)", m.group(1))]
 
 
 def mixed_is_fixed(P: int) -> bool:

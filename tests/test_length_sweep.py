@@ -2,8 +2,6 @@
 cover what they are for -- every (RA, RB) stage case and every stage count of the mixed-radix plans, every N1 and every N2 of kernel 11's
 direct plans, every exact fit of a chirp-z convolution -- that no length is run twice, and that the truth of the longest is affordable."""
 import collections
-import os
-import re
 import time
 
 import numpy as np
@@ -11,16 +9,6 @@ import numpy as np
 import edge_signals as es
 import length_sweep as ls
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MIXED_SRC = os.path.join(ROOT, "spectrogram_rs_amd", "csrc", "stft_mixed.hip")
-
-
-def _macro(name):
-    """the X(...) argument lists of a #define in stft_mixed.hip, continuation lines included"""
-    text = open(MIXED_SRC).read()
-    m = re.search(r"#define " + name + r"\(X\)((?:.*\\\n)*.*)\n", text)
-    assert m, name
-    return [tuple(int(v) for v in args.split(",")) for args in re.findall(r"X\(([^)]*)\)", m.group(1))]
 
 
 def test_smooth_is_every_smooth_window_but_those_of_other_kernels():
@@ -48,7 +36,7 @@ def test_smooth_is_every_smooth_window_but_those_of_other_kernels():
 
 def test_fixed_plan_table_is_the_macros():
     plans = {}
-    for row in _macro("MIX_FIXED_PLANS") + _macro("MIX_FIXED4_PLANS"):
+    for row in ls.macro("MIX_FIXED_PLANS") + ls.macro("MIX_FIXED4_PLANS"):
         P, ab = row[0], row[1:-1]
         plans[P] = tuple(zip(ab[0::2], ab[1::2]))
     assert plans == ls.MIX_FIXED
@@ -58,7 +46,7 @@ def test_fixed_plan_table_is_the_macros():
 
 
 def test_every_stage_case_and_every_stage_count_occurs():
-    cases = set(_macro("MIX_STAGE_CASES"))
+    cases = set(ls.macro("MIX_STAGE_CASES"))
     asked, counts = set(), collections.Counter()
     for W in ls.ALL_SMOOTH_W:                       # what any plan of any served window asks for
         for plan in (ls.mixed_radix_plan(2 * W), ls.mixed_radix_plan(W)):
