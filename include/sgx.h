@@ -103,7 +103,10 @@ typedef struct sgx_config {
  * SGX_FLAG_PAIRED_FRAMES (opt-in): two frames (2j, 2j+1) per transform in its real and imaginary part -- half the work of the (s, s)
  * transform, but the quieter frame of a pair carries the louder one's float32 rounding floor: the tolerance then holds against the
  * PAIR's peak only (measured: up to 4.7 x the own-peak tolerance across a 60 dB step inside one hop, unbounded next to digital
- * silence; invisible on stationary signals.  DESIGN.md section 4). */
+ * silence; invisible on stationary signals.  DESIGN.md section 4).  At W 2400 and W 8192 a context whose hop and window together
+ * exceed 2^31 - 1 bytes of mono samples (H + W >= 2^29) runs every frame as its own transform, as without the flag -- at W 8192 on a
+ * duplicated (s, s) plane of the call's sample range, which the library allocates: 2 (n - 1) H + 2 W floats for n frames, 17 GB for three
+ * frames at H = 2^30. */
 #define SGX_FLAG_PAIRED_FRAMES 1024u /* mono: two frames per transform (the default of rounds 1-3) */
 #define SGX_FLAG_COMPLEX_MONO 512u /* mono: the literal (s, s) 2W-point complex transform per frame -- fft.rs:47-57 -- wherever a
                                       real-input kernel would run (A/B; implies no pairing) */

@@ -678,7 +678,11 @@ hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm
     p.total_frames = total_frames;
     p.H = c->H;
     p.pairs = pairs;
-    const bool mono = channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES);
+    // Frame pairs read the partner frame through the first frame's descriptor, H * 4 bytes on as its scalar offset: that offset plus the
+    // window must stay inside the descriptor's 2^31 - 1 records (beyond them the loads return zero, and from H = 2^30 the 32-bit offset
+    // has wrapped).  A context with such a hop takes the route of unpaired frames: a property of the context, not of the call.
+    const bool pairs_fit = 4ull * ((unsigned long long)c->H + kW) <= 0x7fffffffull;
+    const bool mono = channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && pairs_fit;
     // a mono stream whose frames are not paired (the default): every frame the (s, s) transform of the reference
     // (audio_input_list_model.rs:67-69) -- the sample range duplicated into one (s, s) plane, then the two-channel kernel
     const bool dup = channels == 1 && !mono;

@@ -422,7 +422,11 @@ hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *
     p.H = c->H;
     p.pairs = 1;
     p.half_scale = 0.5f * (2.0f / (float)c->W);
-    const int mode = channels == 2 ? 0 : ((c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) ? 1 : 2);
+    // Frame pairs read the partner frame through the first frame's descriptor, H * 4 bytes on as its scalar offset: that offset plus the
+    // window must stay inside the descriptor's 2^31 - 1 records (beyond them the loads return zero, and from H = 2^30 the 32-bit offset
+    // has wrapped).  A context with such a hop runs every frame as its own (s, s) transform: a property of the context, not of the call.
+    const bool pairs_fit = 4ull * ((unsigned long long)c->H + kW) <= 0x7fffffffull;
+    const int mode = channels == 2 ? 0 : (((c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && pairs_fit) ? 1 : 2);
     p.pair_base = mode == 1 ? first_frame / 2 : 0;
     p.n_jobs = mode == 1 ? (first_frame + n_frames + 1) / 2 - first_frame / 2 : n_frames;
     // persistent workgroups, three per CU, each with a contiguous run of transforms: neighbouring frames share 96 % of their samples
