@@ -215,77 +215,175 @@ int upload_palette(sgx_ctx *c)
     return SGX_OK;
 }
 
+using sgx::Out;
+using sgx::StftCall;
+
+// ---- the host dispatch: which family serves a call, and the bounded workspace of the routes that take two kernels -------------------
+
+enum class Family { kGeneric, kWg4096, kBluestein, kChirpz, kMixed, kW4800, kW16384, kLarge };
+// `fused`: one launch of `family` writes the call's Out.  Otherwise `family` writes the rows (Out::kMags) into the workspace and a second
+// kernel makes the Out of them.  real_input: the rows are the family's real-input mode (sgx_info.render_path bit 3).
+struct Route { Family family; bool fused, real_input; };
+
+// The one place that answers: on this context, a call of `channels` channels for `kind` -- which family launches, and is the Out fused?
+//
+// Channel counts.  The rows' family goes by the CALL's channel count: sgx_process_one passes 2 on any context, so on a W 2400 context that
+// is mono (real-input mode) or has more than two channels its one (l, r) frame runs the tuned 4800-point kernel.  The fused columns go by
+// the CONTEXT's channel count (wg4096_can_fuse_*, mixed_can_fuse_* read c->C: the tables they test were built for it).  Only the batch entry
+// points ask for a column, and their channel count is the context's, so one `channels` serves both here; the queries (sgx_query,
+// sgx_bands_fused, sgx_bands_peak_fused) pass c->C.
+Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind)
+{
+    const bool mixed = c->stft_kernel == sgx::kKernelMixed || c->stft_kernel == sgx::kKernelW4800;
+    // The W 2400 rows of one or two channels come from the 4800-point kernel, unless real-input mode takes the stream (a mono stream, every
+    // frame its own transform: 2400 points instead of 4800 on (s, s)); more channels run the mixed-radix kernels
+    const bool rows_from_w4800 = c->stft_kernel == sgx::kKernelW4800 && channels <= 2 && !sgx::mixed_real_serves(c, c->d_mix, channels);
+    Route rows{Family::kGeneric, true, false};
+    switch (c->stft_kernel) {
+    case sgx::kKernelW16384: rows.family = Family::kW16384; break;   // (a mono stream whose frames are not paired: as an (s, s) plane through the two-channel instantiation)
+    case sgx::kKernelLarge: rows.family = Family::kLarge; break;     // lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM)
+    case sgx::kKernelW4800:
+    case sgx::kKernelMixed:
+        rows.family = rows_from_w4800 ? Family::kW4800 : Family::kMixed;
+        rows.real_input = sgx::mixed_real_serves(c, c->d_mix, channels);
+        break;
+    case sgx::kKernelChirp:
+        rows.family = c->d_chz ? Family::kChirpz : Family::kBluestein;
+        rows.real_input = sgx::chirpz_real_serves(c, c->d_chz, channels);
+        break;
+    case sgx::kKernelWg4096:
+        rows.family = Family::kWg4096;
+        rows.real_input = !sgx::paired_mono(c, channels) && !(c->cfg.flags & SGX_FLAG_COMPLEX_MONO) && sgx::real4096_serves(c, nullptr, channels);
+        break;
+    case sgx::kKernelGeneric: break;
+    }
+    const bool may_fuse = !(c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER);
+    bool fused = false;
+    switch (kind) {
+    case Out::kMags:
+    case Out::kComplex: return rows;
+    case Out::kMagsF16:   // the tuned and the mixed-radix kernels store half pairs themselves; the others convert float32 rows
+        fused = rows.family == Family::kWg4096 || rows.family == Family::kW4800 || rows.family == Family::kMixed;
+        break;
+    case Out::kRgba:      // (the pixels of a W 2400 stream come from the mixed-radix kernel whichever kernel its rows come from)
+        fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_render(c, c->d_fast_wg);
+        if (may_fuse && mixed && sgx::mixed_can_fuse_render(c, c->d_mix)) {
+            rows.family = Family::kMixed;
+            fused = true;
+        }
+        break;
+    case Out::kBands:     // Only the transform decides, not the palette: the column has no colour.  It must hold the bits of the context's rows, so
+                          // a fused kernel serves only where the rows come from the same transform: not where they come from the 4800-point kernel
+        fused = may_fuse && ((rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_bands(c, c->d_fast_wg)) ||
+                             (rows.family == Family::kMixed && sgx::mixed_can_fuse_bands(c, c->d_mix)));
+        break;
+    case Out::kPeak:      // in one kernel where sgx_bands_batch runs the 4096-point kernels and the frames are not paired
+        fused = stft_route(c, channels, Out::kBands).fused && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_peak(c, c->d_fast_wg);
+        break;
+    }
+    rows.fused = fused;
+    return rows;
+}
+
+hipError_t launch_family(const sgx_ctx *c, Family f, const StftCall &call)
+{
+    switch (f) {
+    case Family::kGeneric: return sgx::launch_generic(c, call);
+    case Family::kWg4096: return sgx::launch_wg4096(c, call);
+    case Family::kBluestein: return sgx::launch_bluestein(c, call);
+    case Family::kChirpz: return sgx::launch_chirpz(c, call);
+    case Family::kMixed: return sgx::launch_mixed(c, call);
+    case Family::kW4800: return sgx::launch_w4800(c, call);
+    case Family::kW16384: return sgx::launch_w16384(c, call);
+    case Family::kLarge: return sgx::launch_large(c, call);
+    }
+    return hipErrorInvalidValue;
+}
+
+// frames [first, first + n) of the context's own stream layout into `out`, by the family `r` names
+hipError_t run_call(const sgx_ctx *c, const Route &r, const float *d_pcm, size_t first, size_t n, size_t total, void *out, Out kind, size_t peak_group = 0)
+{
+    return launch_family(c, r.family, StftCall{d_pcm, c->C, c->pairs, first, n, total, out, kind, peak_group});
+}
+
+// The bounded workspace: the routes that take two kernels keep the magnitudes of a chunk of frames in it (L2 / Infinity-Cache sized chunks,
+// reused), grown on demand and kept.  ensure_workspace counts frames of magnitudes.
+constexpr size_t kWorkspaceBytes = (size_t)192u << 20;
+size_t mags_bytes_per_frame(const sgx_ctx *c) { return (size_t)c->pairs * c->M * 2 * sizeof(float); }
+
+size_t workspace_chunk(size_t bytes_per_frame, size_t n)
+{
+    const size_t chunk = kWorkspaceBytes / bytes_per_frame;
+    return chunk < 1 ? 1 : (chunk > n ? n : chunk);
+}
+
 int ensure_workspace(sgx_ctx *c, size_t frames)
 {
-    if (frames <= c->ws_frames) return SGX_OK;
-    if (c->d_ws_mags) { (void)hipFree(c->d_ws_mags); c->d_ws_mags = nullptr; c->ws_frames = 0; }
-    const size_t bytes = frames * (size_t)c->pairs * c->M * 2 * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_ws_mags), bytes);
-    if (e != hipSuccess) return fail_hip(c, e, "hipMalloc(render workspace)");
-    c->ws_frames = frames;
-    return SGX_OK;
+    const hipError_t e = sgx::grow(c->stream, c->d_ws_mags, c->ws_frames, frames, frames * mags_bytes_per_frame(c));
+    return e == hipSuccess ? SGX_OK : fail_hip(c, e, "hipMalloc(render workspace)");
 }
 
-// `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index).  `out`: magnitude pairs (sgx_stft_batch)
-// or complex rows (sgx_stft_batch_complex) -- one dispatch, so that both outputs of a context come from the same kernel family
-enum class StftOut { kMagnitudes, kComplex };
-hipError_t run_stft(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first, size_t n,
-                    size_t total, float *d_mags, StftOut out = StftOut::kMagnitudes)
+// n frames in chunks whose magnitudes fit the workspace: body(done, m) runs frames [done, done + m) of the call and returns an SGX code
+template <typename Body>
+int in_workspace_chunks(sgx_ctx *c, size_t n, Body body)
 {
-    const bool cx = out == StftOut::kComplex;
-    // W = 8192 (a mono stream whose frames are not paired: as an (s, s) plane through the two-channel instantiation; the 8192-point plan of
-    // the mixed-radix kernel's real-input mode measured no faster, round 4)
-    if (c->stft_kernel == 10) return sgx::launch_stft_w16384(c, c->d_w16k, d_pcm, channels, pairs, first, n, total, d_mags, cx);
-    // lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM): four-step passes through the context's scratch
-    if (c->stft_kernel == 11) return sgx::launch_stft_large(c, c->d_large, d_pcm, channels, pairs, first, n, total, d_mags, cx);
-    // (a mono stream, every frame its own transform: real-input mode of the mixed-radix kernel, 2400 points instead of 4800 on (s, s))
-    if (c->stft_kernel == 9 && channels <= 2 && !sgx::mixed_real_serves(c, c->d_mix, channels)) return sgx::launch_stft_w4800(c, c->d_w4800, d_pcm, channels, first, n, total, d_mags, false, cx);
-    if (c->stft_kernel == 6 || c->stft_kernel == 9) return sgx::launch_stft_mixed(c, c->d_mix, d_pcm, channels, pairs, first, n, total, d_mags, false, cx);
-    if (c->stft_kernel == 4 && c->d_chz) return sgx::launch_stft_chirpz(c, c->d_chz, d_pcm, channels, pairs, first, n, total, d_mags, cx);
-    if (c->stft_kernel == 4) return sgx::launch_stft_bluestein(c, c->d_blu, d_pcm, channels, pairs, first, n, total, d_mags, cx);
-    if (c->stft_kernel == 2) return sgx::launch_stft_wg4096(c, c->d_fast_wg, d_pcm, channels, pairs, first, n, total, d_mags, cx);
-    return sgx::launch_stft_generic(c, d_pcm, channels, pairs, first, n, total, d_mags, cx);
+    const size_t chunk = workspace_chunk(mags_bytes_per_frame(c), n);
+    int rc = ensure_workspace(c, chunk);
+    for (size_t done = 0; rc == SGX_OK && done < n; done += chunk) rc = body(done, n - done < chunk ? n - done : chunk);
+    return rc;
 }
 
-// sgx_bands_batch's route: 1 the fused 4096-point kernels (K1 / real-input K1R), 2 the fused mixed-radix kernels, 0 two kernels.  Only the
-// transform decides it, not the palette: the bands column has no colour.  The fused column must hold the bits of sgx_stft_batch's rows, so
-// a fused kernel serves only contexts whose rows come from the same transform: a W 2400 stream of one or two channels that real-input
-// mode does not take gets its rows from the tuned 4800-point kernel (run_stft), whose last bits differ from the mixed-radix kernel's --
-// those take the two-kernel route (sgx_render_batch's pixels there come from the mixed-radix kernel).
-int bands_route(const sgx_ctx *c)
+// The rows of frames [first, first + m) into the workspace (the caller has grown it to m frames), for the second kernel of a two-kernel route
+hipError_t rows_to_workspace(const sgx_ctx *c, const float *d_pcm, size_t first, size_t m, size_t total)
 {
-    if (c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER) return 0;
-    if (c->stft_kernel == 2 && sgx::wg4096_can_fuse_bands(c, c->d_fast_wg)) return 1;
-    const bool rows_from_w4800 = c->stft_kernel == 9 && c->C <= 2 && !sgx::mixed_real_serves(c, c->d_mix, c->C);
-    if ((c->stft_kernel == 6 || c->stft_kernel == 9) && !rows_from_w4800 && sgx::mixed_can_fuse_bands(c, c->d_mix)) return 2;
-    return 0;
+    return run_call(c, stft_route(c, c->C, Out::kMags), d_pcm, first, m, total, c->d_ws_mags, Out::kMags);
 }
 
-// What sgx_bands_batch runs on frames [first, first + n): the fused kernel of its route, or the STFT into the first `mags_chunk` frames
-// of the workspace (the caller has grown it) and magnitude_in over the context's own row and sample tables, chunk by chunk.
-int run_bands(sgx_ctx *c, const char *who, const float *d_pcm, size_t first, size_t n, size_t total, float *d_bands, size_t mags_chunk)
+// What sgx_bands_batch runs on frames [first, first + m): the fused kernel of its route, or the rows into the workspace (m frames fit: the
+// caller's chunk) and magnitude_in over the context's own row and sample tables.
+int run_bands(sgx_ctx *c, const char *who, const Route &r, const float *d_pcm, size_t first, size_t m, size_t total, float *d_bands)
 {
-    const int route = bands_route(c);
-    if (route != 0) {
+    if (r.fused) {
         // one kernel from PCM to bands: the magnitudes stay in LDS, 8 B per row leave the kernel
-        const hipError_t e = route == 1 ? sgx::launch_bands_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first, n, total, d_bands)
-                                        : sgx::launch_bands_mixed(c, c->d_mix, d_pcm, c->C, c->pairs, first, n, total, d_bands);
-        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": fused launch").c_str());
-        return SGX_OK;
+        const hipError_t e = run_call(c, r, d_pcm, first, m, total, d_bands, Out::kBands);
+        return e == hipSuccess ? SGX_OK : fail_hip(c, e, (std::string(who) + ": fused launch").c_str());
     }
     // two kernels, as sgx_render_batch
-    for (size_t done = 0; done < n; done += mags_chunk) {
-        const size_t m = n - done < mags_chunk ? n - done : mags_chunk;
-        hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first + done, m, total, c->d_ws_mags);
-        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": stft launch").c_str());
-        e = sgx::launch_magnitude_in(c, c->d_ws_mags, m * c->pairs, c->d_rows, c->d_samples, c->R, d_bands + done * (size_t)c->pairs * c->R * 2);
-        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": magnitude_in launch").c_str());
-    }
+    hipError_t e = rows_to_workspace(c, d_pcm, first, m, total);
+    if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": stft launch").c_str());
+    e = sgx::launch_magnitude_in(c, c->d_ws_mags, m * c->pairs, c->d_rows, c->d_samples, c->R, d_bands);
+    if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": magnitude_in launch").c_str());
     return SGX_OK;
 }
 
-// sgx_bands_peak_batch in one kernel: where sgx_bands_batch runs the 4096-point kernels and the frames are not paired
-bool peak_fused(const sgx_ctx *c) { return bands_route(c) == 1 && sgx::wg4096_can_fuse_peak(c, c->d_fast_wg); }
+// The opening of the six batch calls.  SGX_OK with n == 0: nothing to do (no frames in range: None, fft.rs:72 -- answered before the buffers
+// are looked at); another code: the error, recorded; else frames [first_frame, first_frame + n) of the stream's `total` are to be computed.
+int begin_batch(sgx_ctx *c, const char *who, size_t n_samples, size_t first_frame, size_t max_frames, const void *d_pcm, const void *d_out,
+                size_t *n_out, size_t &total, size_t &n)
+{
+    total = n = 0;
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    total = sgx_num_frames(c, n_samples);
+    if (first_frame >= total || max_frames == 0) return SGX_OK;
+    if (!d_pcm || !d_out) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    n = total - first_frame < max_frames ? total - first_frame : max_frames;
+    return SGX_OK;
+}
+
+// sgx_stft_batch and sgx_stft_batch_complex: one dispatch, so that both outputs of a context come from the same kernel family
+int stft_batch(sgx_ctx *c, const char *who, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, float *d_out, Out kind,
+               size_t *n_out)
+{
+    size_t total, n;
+    const int rc = begin_batch(c, who, n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    const hipError_t e = run_call(c, stft_route(c, c->C, kind), d_pcm, first_frame, n, total, d_out, kind);
+    if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": kernel launch").c_str());
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
 
 }  // namespace
 
@@ -406,7 +504,7 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     int rc = upload_palette(c);
     if (rc != SGX_OK) { std::string m = c->err; return bail(rc, m); }
 
-    c->stft_kernel = 0;
+    c->stft_kernel = sgx::kKernelGeneric;
     if (cfg->flags & (2u | 8u | 32u | 128u | 2048u))   // the flag bits of superseded A/B kernels: wave-per-transform, packed arithmetic, the first three 16384-point designs
         return bail(SGX_ERR_UNSUPPORTED, "sgx_create: flag bits 2, 8, 32 (removed in round 5), 128 and 2048 (SGX_FLAG_RESIDUE_16K, SGX_FLAG_CHANNEL_PLANES: removed in "
                                          "round 6) selected superseded A/B kernels (their measurements: profiles/r01_*, r02_*, r03_k16_ablation.txt, r05_k16.txt, r06_k16.txt)");
@@ -419,16 +517,16 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
         // no in-LDS kernel serves this length (SGX_FLAG_LARGE_TRANSFORM): four-step passes through a scratch allocated here
         e = sgx::large_init(c, &c->d_large);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: multi-pass transform tables and scratch: ") + hipGetErrorString(e));
-        c->stft_kernel = 11;
+        c->stft_kernel = sgx::kKernelLarge;
     } else if (pow2_mixed || (!pow2 && sgx::mixed_supported(c->W) && !((cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::bluestein_supported(c->W)))) {
         // a length FFTW would factor: mixed-radix transform of exactly 2W points (SGX_FLAG_FORCE_GENERIC: chirp-z instead)
         e = sgx::mixed_init(c, &c->d_mix);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: mixed-radix tables: ") + hipGetErrorString(e));
-        c->stft_kernel = 6;
+        c->stft_kernel = sgx::kKernelMixed;
         if (!(cfg->flags & (SGX_FLAG_FORCE_GENERIC | SGX_FLAG_MIXED_GENERIC)) && sgx::w4800_supported(c)) {
             e = sgx::w4800_init(c, &c->d_w4800);
             if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: 4800-point kernel tables: ") + hipGetErrorString(e));
-            c->stft_kernel = 9;
+            c->stft_kernel = sgx::kKernelW4800;
         }
     } else if (!pow2) {
         e = sgx::bluestein_init(c, &c->d_blu);
@@ -437,7 +535,7 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
             e = sgx::chirpz_init(c, &c->d_chz);
             if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: chirp-z tables: ") + hipGetErrorString(e));
         }
-        c->stft_kernel = 4;
+        c->stft_kernel = sgx::kKernelChirp;
     } else if (!(cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::fast4096_supported(c)) {
         e = sgx::wg4096_init(c, &c->d_fast_wg);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: tuned kernel tables: ") + hipGetErrorString(e));
@@ -445,11 +543,11 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
             e = sgx::real4096_init(c, &c->d_real);
             if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: real-input kernel tables: ") + hipGetErrorString(e));
         }
-        c->stft_kernel = 2;
+        c->stft_kernel = sgx::kKernelWg4096;
     } else if (!(cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::w16384_supported(c)) {
         e = sgx::w16384_init(c, &c->d_w16k);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: 16384-point kernel tables: ") + hipGetErrorString(e));
-        c->stft_kernel = 10;
+        c->stft_kernel = sgx::kKernelW16384;
     }
     *out_ctx = c;
     return SGX_OK;
@@ -503,16 +601,14 @@ int sgx_query(const sgx_ctx *c, sgx_info *out)
     out->sample_rate_u32 = c->sr_u32;
     out->total_samples_per_column = (uint32_t)c->tab.samples.size();
     out->stft_kernel = (uint32_t)c->stft_kernel;
+    // render_path from the routes the calls themselves take: bit 0 the fused pixels (bit 1: their LUT search needs no walk), bit 2 a compile-time
+    // plan of the composite-radix stages, bit 3 real-input rows
+    const Route rows = stft_route(c, c->C, Out::kMags), pixels = stft_route(c, c->C, Out::kRgba);
     out->render_path = 0;
-    if (c->stft_kernel == 2 && !(c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER) && sgx::wg4096_can_fuse_render(c, c->d_fast_wg))
-        out->render_path = 1u | (sgx::wg4096_seed_is_within_one(c) ? 2u : 0u);
-    if ((c->stft_kernel == 6 || c->stft_kernel == 9) && sgx::mixed_fixed_plan(c->d_mix)) out->render_path |= 4u;
-    if (c->stft_kernel == 2 && c->d_real && !(c->cfg.flags & SGX_FLAG_COMPLEX_MONO) && !(c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) out->render_path |= 8u;
-    if ((c->stft_kernel == 6 || c->stft_kernel == 9) && sgx::mixed_real_serves(c, c->d_mix, c->C)) out->render_path |= 8u;
-    if (c->stft_kernel == 4 && c->d_chz) out->render_path |= 4u;
-    if (c->stft_kernel == 4 && sgx::chirpz_real_serves(c, c->d_chz, c->C)) out->render_path |= 8u;
-    if ((c->stft_kernel == 6 || c->stft_kernel == 9) && !(c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER) && sgx::mixed_can_fuse_render(c, c->d_mix)) out->render_path |= 3u;
-    out->mags_bytes_per_frame = (uint64_t)c->pairs * c->M * 2 * sizeof(float);
+    if (pixels.fused) out->render_path = pixels.family == Family::kMixed ? 3u : 1u | (sgx::wg4096_seed_is_within_one(c) ? 2u : 0u);
+    if (rows.family == Family::kChirpz || ((rows.family == Family::kMixed || rows.family == Family::kW4800) && sgx::mixed_fixed_plan(c->d_mix))) out->render_path |= 4u;
+    if (rows.real_input) out->render_path |= 8u;
+    out->mags_bytes_per_frame = mags_bytes_per_frame(c);
     out->rgba_bytes_per_frame = (uint64_t)c->pairs * c->R * 4;
     return SGX_OK;
 }
@@ -541,35 +637,13 @@ int sgx_sync(sgx_ctx *c)
 int sgx_stft_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
                    float *d_mags, size_t *n_out)
 {
-    if (n_out) *n_out = 0;
-    if (!c) return SGX_ERR_INVALID_ARG;
-    const size_t total = sgx_num_frames(c, n_samples);
-    if (first_frame >= total || max_frames == 0) return SGX_OK;  // None: not an error (fft.rs:72)
-    size_t n = total - first_frame;
-    if (n > max_frames) n = max_frames;
-    if (!d_pcm || !d_mags) return fail(c, SGX_ERR_INVALID_ARG, "sgx_stft_batch: null buffer");
-    SGX_HIP(c, hipSetDevice(c->device));
-    hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame, n, total, d_mags);
-    if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch: kernel launch");
-    if (n_out) *n_out = n;
-    return SGX_OK;
+    return stft_batch(c, "sgx_stft_batch", d_pcm, n_samples, first_frame, max_frames, d_mags, Out::kMags, n_out);
 }
 
 int sgx_stft_batch_complex(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
                            float *d_spec, size_t *n_out)
 {
-    if (n_out) *n_out = 0;
-    if (!c) return SGX_ERR_INVALID_ARG;
-    const size_t total = sgx_num_frames(c, n_samples);
-    if (first_frame >= total || max_frames == 0) return SGX_OK;
-    size_t n = total - first_frame;
-    if (n > max_frames) n = max_frames;
-    if (!d_pcm || !d_spec) return fail(c, SGX_ERR_INVALID_ARG, "sgx_stft_batch_complex: null buffer");
-    SGX_HIP(c, hipSetDevice(c->device));
-    hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame, n, total, d_spec, StftOut::kComplex);
-    if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_complex: kernel launch");
-    if (n_out) *n_out = n;
-    return SGX_OK;
+    return stft_batch(c, "sgx_stft_batch_complex", d_pcm, n_samples, first_frame, max_frames, d_spec, Out::kComplex, n_out);
 }
 
 int sgx_istft_supported(const sgx_ctx *c)
@@ -605,39 +679,24 @@ int sgx_istft_batch(sgx_ctx *c, const float *d_spec, size_t n_frames, size_t fir
 int sgx_stft_batch_f16(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
                        void *d_mags_f16, size_t *n_out)
 {
-    if (n_out) *n_out = 0;
-    if (!c) return SGX_ERR_INVALID_ARG;
-    const size_t total = sgx_num_frames(c, n_samples);
-    if (first_frame >= total || max_frames == 0) return SGX_OK;
-    size_t n = total - first_frame;
-    if (n > max_frames) n = max_frames;
-    if (!d_pcm || !d_mags_f16) return fail(c, SGX_ERR_INVALID_ARG, "sgx_stft_batch_f16: null buffer");
-    SGX_HIP(c, hipSetDevice(c->device));
-    if (c->stft_kernel == 2) {
-        hipError_t e = sgx::launch_stft_wg4096_f16(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first_frame, n, total, d_mags_f16);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_f16: kernel launch");
-    } else if (c->stft_kernel == 9 && c->C <= 2 && !sgx::mixed_real_serves(c, c->d_mix, c->C)) {
-        hipError_t e = sgx::launch_stft_w4800(c, c->d_w4800, d_pcm, c->C, first_frame, n, total, static_cast<float *>(d_mags_f16), true);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_f16: kernel launch");
-    } else if (c->stft_kernel == 6 || c->stft_kernel == 9) {
-        // the application's own window lengths: half pairs straight from the split (no float32 round trip)
-        hipError_t e = sgx::launch_stft_mixed(c, c->d_mix, d_pcm, c->C, c->pairs, first_frame, n, total, static_cast<float *>(d_mags_f16), true);
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_stft_batch_f16", n_samples, first_frame, max_frames, d_pcm, d_mags_f16, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    const Route r = stft_route(c, c->C, Out::kMagsF16);
+    if (r.fused) {
+        // half pairs straight from the kernel's split (no float32 round trip)
+        const hipError_t e = run_call(c, r, d_pcm, first_frame, n, total, d_mags_f16, Out::kMagsF16);
         if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_f16: kernel launch");
     } else {
         // kernels without a native half store: float32 into the bounded workspace, then one conversion pass
         const size_t per_frame = (size_t)c->pairs * c->M;  // (l, r) pairs per frame
-        size_t chunk = (size_t)(192u << 20) / (per_frame * 8);
-        if (chunk < 1) chunk = 1;
-        if (chunk > n) chunk = n;
-        int rc = ensure_workspace(c, chunk);
-        if (rc != SGX_OK) return rc;
-        for (size_t done = 0; done < n; done += chunk) {
-            const size_t m = n - done < chunk ? n - done : chunk;
-            hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame + done, m, total, c->d_ws_mags);
+        rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+            hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
             if (e == hipSuccess)
                 e = sgx::launch_to_half(c, c->d_ws_mags, static_cast<char *>(d_mags_f16) + done * per_frame * 4, m * per_frame);
-            if (e != hipSuccess) return fail_hip(c, e, "sgx_stft_batch_f16: kernel launch");
-        }
+            return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_stft_batch_f16: kernel launch");
+        });
+        if (rc != SGX_OK) return rc;
     }
     if (n_out) *n_out = n;
     return SGX_OK;
@@ -650,7 +709,8 @@ int sgx_process_one(sgx_ctx *c, const float *h_lr, size_t n_avail, float *h_out)
     if (!h_lr || !h_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_process_one: null buffer");
     SGX_HIP(c, hipSetDevice(c->device));
     SGX_HIP(c, hipMemcpyAsync(c->d_one_in, h_lr, (size_t)c->W * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hipError_t e = run_stft(c, c->d_one_in, 2, 1, 0, 1, 1, c->d_one_out);
+    // one (l, r) frame whatever the context's channel count: the family goes by the call's two channels (stft_route)
+    hipError_t e = launch_family(c, stft_route(c, 2, Out::kMags).family, StftCall{c->d_one_in, 2, 1, 0, 1, 1, c->d_one_out, Out::kMags, 0});
     if (e != hipSuccess) return fail_hip(c, e, "sgx_process_one: kernel launch");
     SGX_HIP(c, hipMemcpyAsync(h_out, c->d_one_out, (size_t)c->M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SGX_HIP(c, hipStreamSynchronize(c->stream));
@@ -671,41 +731,24 @@ int sgx_render_mags(sgx_ctx *c, const float *d_mags, size_t n_columns, uint8_t *
 int sgx_render_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
                      uint8_t *d_rgba, size_t *n_out)
 {
-    if (n_out) *n_out = 0;
-    if (!c) return SGX_ERR_INVALID_ARG;
-    const size_t total = sgx_num_frames(c, n_samples);
-    if (first_frame >= total || max_frames == 0) return SGX_OK;
-    size_t n = total - first_frame;
-    if (n > max_frames) n = max_frames;
-    if (!d_pcm || !d_rgba) return fail(c, SGX_ERR_INVALID_ARG, "sgx_render_batch: null buffer");
-    SGX_HIP(c, hipSetDevice(c->device));
-    if (c->stft_kernel == 2 && !(c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER) && sgx::wg4096_can_fuse_render(c, c->d_fast_wg)) {
-        // one kernel from PCM to pixels: magnitudes never leave LDS (5 120 B of HBM traffic per frame)
-        hipError_t e = sgx::launch_render_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first_frame, n, total, d_rgba);
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_render_batch", n_samples, first_frame, max_frames, d_pcm, d_rgba, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    const Route r = stft_route(c, c->C, Out::kRgba);
+    if (r.fused) {
+        // one kernel from PCM to pixels: the magnitudes never leave LDS (the 4096-point kernels: 5 120 B of HBM traffic per frame; the
+        // application's own window lengths: the pixel stage runs on the mixed-radix transform's LDS image)
+        const hipError_t e = run_call(c, r, d_pcm, first_frame, n, total, d_rgba, Out::kRgba);
         if (e != hipSuccess) return fail_hip(c, e, "sgx_render_batch: fused launch");
-        if (n_out) *n_out = n;
-        return SGX_OK;
-    }
-    if ((c->stft_kernel == 6 || c->stft_kernel == 9) && !(c->cfg.flags & SGX_FLAG_NO_FUSED_RENDER) && sgx::mixed_can_fuse_render(c, c->d_mix)) {
-        // the application's own window lengths, one kernel from PCM to pixels: the pixel stage runs on the transform's LDS image
-        hipError_t e = sgx::launch_render_mixed(c, c->d_mix, d_pcm, c->C, c->pairs, first_frame, n, total, d_rgba);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_render_batch: fused launch");
-        if (n_out) *n_out = n;
-        return SGX_OK;
-    }
-    // two kernels; magnitudes stay in a bounded, reused workspace (L2 / Infinity-Cache sized chunks)
-    const size_t bytes_per_frame = (size_t)c->pairs * c->M * 2 * sizeof(float);
-    size_t chunk = (size_t)(192u << 20) / bytes_per_frame;
-    if (chunk < 1) chunk = 1;
-    if (chunk > n) chunk = n;
-    int rc = ensure_workspace(c, chunk);
-    if (rc != SGX_OK) return rc;
-    for (size_t done = 0; done < n; done += chunk) {
-        const size_t m = n - done < chunk ? n - done : chunk;
-        hipError_t e = run_stft(c, d_pcm, c->C, c->pairs, first_frame + done, m, total, c->d_ws_mags);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_render_batch: stft launch");
-        e = sgx::launch_render(c, c->d_ws_mags, m * c->pairs, d_rgba + done * (size_t)c->pairs * c->R * 4);
-        if (e != hipSuccess) return fail_hip(c, e, "sgx_render_batch: render launch");
+    } else {
+        // two kernels; magnitudes stay in the bounded, reused workspace
+        rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+            hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
+            if (e != hipSuccess) return fail_hip(c, e, "sgx_render_batch: stft launch");
+            e = sgx::launch_render(c, c->d_ws_mags, m * c->pairs, d_rgba + done * (size_t)c->pairs * c->R * 4);
+            return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_render_batch: render launch");
+        });
+        if (rc != SGX_OK) return rc;
     }
     if (n_out) *n_out = n;
     return SGX_OK;
@@ -713,23 +756,15 @@ int sgx_render_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fi
 
 int sgx_bands_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, float *d_bands, size_t *n_out)
 {
-    if (n_out) *n_out = 0;
-    if (!c) return SGX_ERR_INVALID_ARG;
-    const size_t total = sgx_num_frames(c, n_samples);
-    if (first_frame >= total || max_frames == 0) return SGX_OK;
-    size_t n = total - first_frame;
-    if (n > max_frames) n = max_frames;
-    if (!d_pcm || !d_bands) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_batch: null buffer");
-    SGX_HIP(c, hipSetDevice(c->device));
-    size_t chunk = 0;
-    if (bands_route(c) == 0) {   // two kernels: the magnitudes of a chunk of frames in the bounded workspace
-        chunk = (size_t)(192u << 20) / ((size_t)c->pairs * c->M * 2 * sizeof(float));
-        if (chunk < 1) chunk = 1;
-        if (chunk > n) chunk = n;
-        int rc = ensure_workspace(c, chunk);
-        if (rc != SGX_OK) return rc;
-    }
-    int rc = run_bands(c, "sgx_bands_batch", d_pcm, first_frame, n, total, d_bands, chunk);
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_bands_batch", n_samples, first_frame, max_frames, d_pcm, d_bands, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    const Route r = stft_route(c, c->C, Out::kBands);
+    if (r.fused) rc = run_bands(c, "sgx_bands_batch", r, d_pcm, first_frame, n, total, d_bands);
+    else   // two kernels: the magnitudes of a chunk of frames in the bounded workspace
+        rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+            return run_bands(c, "sgx_bands_batch", r, d_pcm, first_frame + done, m, total, d_bands + done * (size_t)c->pairs * c->R * 2);
+        });
     if (rc != SGX_OK) return rc;
     if (n_out) *n_out = n;
     return SGX_OK;
@@ -738,38 +773,35 @@ int sgx_bands_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fir
 int sgx_bands_peak_fused(const sgx_ctx *c)
 {
     if (!c) return SGX_ERR_INVALID_ARG;
-    return peak_fused(c) ? 1 : 0;
+    return stft_route(c, c->C, Out::kPeak).fused ? 1 : 0;
 }
 
 int sgx_bands_peak_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, size_t group,
                          float *d_peak, size_t *n_out)
 {
     if (n_out) *n_out = 0;
-    if (!c) return SGX_ERR_INVALID_ARG;
-    if (group == 0) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_peak_batch: group is 0");
-    const size_t total = sgx_num_frames(c, n_samples);
-    if (first_frame >= total || max_frames == 0) return SGX_OK;
-    size_t n = total - first_frame;
-    if (n > max_frames) n = max_frames;
-    if (!d_pcm || !d_peak) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_peak_batch: null buffer");
-    SGX_HIP(c, hipSetDevice(c->device));
+    if (c && group == 0) return fail(c, SGX_ERR_INVALID_ARG, "sgx_bands_peak_batch: group is 0");
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_bands_peak_batch", n_samples, first_frame, max_frames, d_pcm, d_peak, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
     const size_t g = group < n ? group : n;              // (one column: any group from n on)
     const size_t n_cols = (n - 1) / g + 1;
-    if (peak_fused(c)) {
+    const Route peak = stft_route(c, c->C, Out::kPeak);
+    if (peak.fused) {
         // one kernel from PCM to peak columns: every persistent workgroup keeps the running maximum of its current column (in L2),
         // the columns that span several workgroups are finished by one combine launch
-        const hipError_t e = sgx::launch_bands_peak_wg4096(c, c->d_fast_wg, d_pcm, c->C, c->pairs, first_frame, n, total, g, d_peak);
+        const hipError_t e = run_call(c, peak, d_pcm, first_frame, n, total, d_peak, Out::kPeak, g);
         if (e != hipSuccess) return fail_hip(c, e, "sgx_bands_peak_batch: fused launch");
         if (n_out) *n_out = n_cols;
         return SGX_OK;
     }
     // The workspace route: chunks of frames through sgx_bands_batch's own route into the bounded workspace, bands_peak_kernel reduces
-    // each chunk.  The 192 MiB hold, per frame of a chunk: its band column; on the two-kernel bands route its magnitudes in front;
-    // and behind the columns the sub-columns of a two-level reduction (kSubNum / kSubDen of a column and two more: below).
+    // each chunk.  The workspace's budget (kWorkspaceBytes) holds, per frame of a chunk: its band column; on the two-kernel bands route its
+    // magnitudes in front; and behind the columns the sub-columns of a two-level reduction (kSubNum / kSubDen of a column and two more: below).
     const size_t col = (size_t)c->pairs * c->R * 2, col_bytes = col * sizeof(float);
-    const int route = bands_route(c);
-    const size_t mags_bytes = route == 0 ? (size_t)c->pairs * c->M * 2 * sizeof(float) : 0;
-    constexpr size_t kBudget = (size_t)192u << 20, kSubNum = 9, kSubDen = 64, kTwoLevelMin = 64;
+    const Route bands = stft_route(c, c->C, Out::kBands);
+    const size_t mags_bytes = bands.fused ? 0 : mags_bytes_per_frame(c);
+    constexpr size_t kBudget = kWorkspaceBytes, kSubNum = 9, kSubDen = 64, kTwoLevelMin = 64;
     const size_t per_frame = col_bytes + mags_bytes + (col_bytes * kSubNum + kSubDen - 1) / kSubDen;
     size_t chunk = kBudget > 2 * col_bytes ? (kBudget - 2 * col_bytes) / per_frame : 0;
     if (chunk < 1) chunk = 1;
@@ -777,15 +809,15 @@ int sgx_bands_peak_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_
     if (g <= chunk) chunk -= chunk % g;                  // whole columns per chunk; else a column accumulates over several chunks
     const size_t sub_cap = chunk * kSubNum / kSubDen + 2;
     const size_t ws_bytes = chunk * (col_bytes + mags_bytes) + sub_cap * col_bytes;
-    const size_t ws_unit = (size_t)c->pairs * c->M * 2 * sizeof(float);   // (ensure_workspace counts frames of magnitudes)
-    int rc = ensure_workspace(c, (ws_bytes + ws_unit - 1) / ws_unit);
+    const size_t ws_unit = mags_bytes_per_frame(c);   // (ensure_workspace counts frames of magnitudes)
+    rc = ensure_workspace(c, (ws_bytes + ws_unit - 1) / ws_unit);
     if (rc != SGX_OK) return rc;
     float *ws_bands = c->d_ws_mags + chunk * (mags_bytes / sizeof(float)), *ws_sub = ws_bands + chunk * col;
     for (size_t done = 0; done < n;) {
         const size_t j = done / g;                       // the column this chunk starts in: at its first frame unless g > chunk
         size_t m = n - done < chunk ? n - done : chunk;
         if (g > chunk && m > (j + 1) * g - done) m = (j + 1) * g - done;
-        rc = run_bands(c, "sgx_bands_peak_batch", d_pcm, first_frame + done, m, total, ws_bands, chunk);
+        rc = run_bands(c, "sgx_bands_peak_batch", bands, d_pcm, first_frame + done, m, total, ws_bands);
         if (rc != SGX_OK) return rc;
         const size_t ge = g < m ? g : m;                 // frames per column inside this chunk
         const bool accumulate = done != j * g;
@@ -827,7 +859,7 @@ int sgx_render_bands(sgx_ctx *c, const float *d_bands, size_t n_columns, uint8_t
 int sgx_bands_fused(const sgx_ctx *c)
 {
     if (!c) return SGX_ERR_INVALID_ARG;
-    return bands_route(c) != 0 ? 1 : 0;
+    return stft_route(c, c->C, Out::kBands).fused ? 1 : 0;
 }
 
 int sgx_magnitude_in(sgx_ctx *c, const float *d_mags, size_t n_columns, const float *h_ranges, uint32_t n_ranges, float *d_out)

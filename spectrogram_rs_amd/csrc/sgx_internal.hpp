@@ -98,6 +98,11 @@ int lut_index_host(double t, uint32_t n, uint32_t mode);
 uint8_t alpha_u8_host(float alpha);
 float bounded_db_host(float min_db, float max_db, float power);
 
+// sgx_info.stft_kernel (ABI: the numbers stay): generic radix-4 ladder, tuned 4096 workgroup-per-transform, Bluestein / chirp-z (2W with a
+// prime factor above 7), mixed radix (2W = 2^a 3^b 5^c 7^d), tuned 4800 (W = 2400; more than two channels run the mixed-radix kernels),
+// tuned 16384 (32 x 32 x 16: stft16384_w.hip), multi-pass (stft_large.hip).  Retired numbers: docs/history/stft_kernel_numbers.md
+enum StftKernel : int { kKernelGeneric = 0, kKernelWg4096 = 2, kKernelChirp = 4, kKernelMixed = 6, kKernelW4800 = 9, kKernelW16384 = 10, kKernelLarge = 11 };
+
 }  // namespace sgx
 
 struct sgx_ctx {
@@ -105,10 +110,7 @@ struct sgx_ctx {
     uint32_t W = 0, P = 0, M = 0, H = 0, C = 0, pairs = 0, R = 0, sr_u32 = 0, logP = 0;
     int device = 0;
     hipStream_t stream = nullptr;
-    // sgx_info.stft_kernel (ABI: the numbers stay): 0 generic, 2 tuned 4096 workgroup-per-transform, 4 Bluestein / chirp-z (2W with a prime
-    // factor above 7), 6 mixed radix (2W = 2^a 3^b 5^c 7^d), 9 tuned 4800 (W = 2400; more than two channels run 6's kernels), 10 tuned 16384
-    // (32 x 32 x 16: stft16384_w.hip), 11 multi-pass (stft_large.hip).  Retired numbers: docs/history/stft_kernel_numbers.md
-    int stft_kernel = 0;
+    sgx::StftKernel stft_kernel = sgx::kKernelGeneric;   // what sgx_create chose; sgx_info.stft_kernel reports the number
 
     sgx::Tables tab;
     sgx::Palette pal;
@@ -162,82 +164,110 @@ struct sgx_ctx {
 
 namespace sgx {
 
+// ---- one transform call, as every family's launcher takes it --------------------------------------------------------------
+// What the call writes: magnitude pairs [F][pairs][M][2] floats, the same as half pairs (4 B per bin), the complex rows of
+// sgx_stft_batch_complex [F][pairs][M][2][2] floats, or the fused column: RGBA pixels [F][pairs][R][4] bytes, the rows' (l, r) means as
+// float2 [F][pairs][R] (sgx_bands_batch), or those held as a maximum over groups of frames, float2 [ceil(F / group)][pairs][R].
+enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak };
+// `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index).  channels and pairs are the CALL's, not the
+// context's: sgx_process_one runs a two-channel frame (2, 1) on a context of any channel count.  peak_group (kPeak): 1 .. n.
+struct StftCall {
+    const float *pcm;
+    uint32_t channels, pairs;
+    size_t first, n, total;
+    void *out;
+    Out kind;
+    size_t peak_group;
+};
+// Each launcher takes its tables from the context, returns hipSuccess or the launch error, and hipErrorInvalidValue for an Out (or a
+// channel count) its family has no kernel for.
+hipError_t launch_generic(const sgx_ctx *c, const StftCall &call);     // sgx_kernels.hip: kMags, kComplex
+hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call);      // stft4096_wg.hip (and stft4096_real.hip): every Out
+hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call);      // stft16384_w.hip: kMags, kComplex
+hipError_t launch_w4800(const sgx_ctx *c, const StftCall &call);       // stft4800_wg.hip: kMags, kMagsF16, kComplex of one or two channels
+hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call);       // stft_mixed.hip: every Out but kPeak
+hipError_t launch_chirpz(const sgx_ctx *c, const StftCall &call);      // stft_mixed.hip: kMags, kComplex
+hipError_t launch_bluestein(const sgx_ctx *c, const StftCall &call);   // stft_bluestein.hip: kMags, kComplex
+hipError_t launch_large(const sgx_ctx *c, const StftCall &call);       // stft_large.hip: kMags, kComplex
+
+// a mono stream whose frames share transforms two by two (SGX_FLAG_PAIRED_FRAMES; the literal (s, s) transform of SGX_FLAG_COMPLEX_MONO never pairs)
+inline bool paired_mono(const sgx_ctx *c, uint32_t channels)
+{
+    return channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && !(c->cfg.flags & SGX_FLAG_COMPLEX_MONO);
+}
+// Frame pairs of the tuned kernels read the partner frame through the first frame's buffer descriptor, H * 4 bytes on as its scalar offset:
+// that offset plus the window must stay inside the descriptor's 2^31 - 1 records (beyond them the loads return zero, and from H = 2^30 the
+// 32-bit offset has wrapped).  A context with such a hop runs every frame as its own transform: a property of the context, not of the call.
+inline bool descriptor_pairs_fit(uint32_t H, uint32_t W) { return 4ull * ((unsigned long long)H + W) <= 0x7fffffffull; }
+// Persistent workgroups, `per_cu` to a CU at most, each with a contiguous run of `per` jobs (neighbouring frames share most of their samples:
+// the overlap is re-read from L1 / L2, not from HBM).  runs_of: the workgroups that runs of `per` jobs need.
+struct RunSplit { unsigned long long per, blocks; };
+inline RunSplit runs_of(unsigned long long n_jobs, unsigned long long per) { return {per, (n_jobs + per - 1) / per}; }
+inline RunSplit run_split(const sgx_ctx *c, unsigned long long n_jobs, unsigned per_cu)
+{
+    const unsigned long long blocks = (unsigned long long)c->n_cu * per_cu, per = (n_jobs + blocks - 1) / blocks;
+    return runs_of(n_jobs, per < 1 ? 1 : per);
+}
+// A device buffer that launches on `stream` may still use grows to `want` units (`bytes` bytes): wait for the stream, free, allocate, record
+// the size.  A failed allocation leaves the buffer null and its size 0.
+template <typename T>
+hipError_t grow(hipStream_t stream, T *&buf, size_t &have, size_t want, size_t bytes)
+{
+    if (want <= have) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    if (buf) { (void)hipFree(buf); buf = nullptr; have = 0; }
+    e = hipMalloc(reinterpret_cast<void **>(&buf), bytes);
+    if (e != hipSuccess) return e;
+    have = want;
+    return hipSuccess;
+}
+
 inline bool fast4096_supported(const sgx_ctx *c) { return c->W == 2048; }   // the tuned 4096-point kernels (stft4096_wg.hip)
-// kernel launchers (each returns hipSuccess or the launch error)
-// out_c64 (every STFT launcher): complex rows of sgx_stft_batch_complex, [F][pairs][M][2][2] floats, instead of the magnitude pairs
-hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                               size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 hipError_t wg4096_init(sgx_ctx *c, void **out);
 void wg4096_destroy(void *tables);
-hipError_t launch_stft_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables);
 bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables);   // the fused column without the colour (sgx_bands_batch): no palette condition
-hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_bands);   // float2 [F][pairs][R]
 bool wg4096_can_fuse_peak(const sgx_ctx *c, const void *tables);    // sgx_bands_peak_batch in one kernel (plus the combine pass)
-hipError_t launch_bands_peak_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                    size_t first_frame, size_t n_frames, size_t total_frames, size_t group, float *d_peak);   // group <= n_frames
 hipError_t launch_deinterleave_pairs(const sgx_ctx *c, const float *d_pcm, float *d_planes, size_t plane_floats, size_t first_sample, size_t n_samples,
                                      uint32_t channels, uint32_t pairs);   // deinterleave.hip
 bool wg4096_seed_is_within_one(const sgx_ctx *c);
 void lut_seed_coefficients(const sgx_ctx *c, float &a, float &b);
 namespace wg { bool seed_within_one(const std::vector<float> &thr, double guess_a, double guess_b); }   // stft4096_wg.hip: is floor(log2(p + 1e-7) a + b) within one of the threshold count for every power?   // LUT level ~ floor(log2(power + 1e-7) a + b): the seed of the threshold count
-hipError_t launch_render_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                size_t first_frame, size_t n_frames, size_t total_frames, uint8_t *d_rgba);
 // stft16384_w.hip: W = 8192 as 32 x 32 x 16 in one 512-thread workgroup, 32 points per thread
 bool w16384_supported(const sgx_ctx *c);
 hipError_t w16384_init(sgx_ctx *c, void **out);
 void w16384_destroy(void *tables);
-hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
-// W = 2400 (48 kHz x 0.05 s): persistent 320-thread workgroups, 16 x 20 x 15 (stft4800_wg.hip); rows and half rows of one or two channels -- more
-// channels and the fused PCM-to-pixel path go to the composite-radix kernel, whose tables such a context carries too
 // stft4096_real.hip: independent mono frames at W 2048 / H 256 as 2048-point complex transforms of the real frame
 hipError_t real4096_init(sgx_ctx *c, void **out);
 void real4096_destroy(void *tables);
-bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels);   // (launched from stft4096_wg.hip: launch_wg)
+bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels);   // (launched from stft4096_wg.hip: launch_wg4096)
+// W = 2400 (48 kHz x 0.05 s): persistent 320-thread workgroups, 16 x 20 x 15 (stft4800_wg.hip); rows and half rows of one or two channels -- more
+// channels and the fused PCM-to-pixel path go to the composite-radix kernel, whose tables such a context carries too
 bool w4800_supported(const sgx_ctx *c);
 hipError_t w4800_init(sgx_ctx *c, void **out);
 void w4800_destroy(void *tables);
-hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, size_t first_frame, size_t n_frames,
-                             size_t total_frames, float *d_mags, bool out_f16, bool out_c64 = false);
 bool mixed_supported(uint32_t W);
 hipError_t mixed_init(sgx_ctx *c, void **out);
 hipError_t mixed_length_tables(uint32_t n, void **out);   // the stage plan and tables of an n-point transform alone (mixed_destroy frees them)
 void mixed_destroy(void *tables);
-uint32_t mixed_fixed_plan(const void *tables);
+uint32_t mixed_fixed_plan(const void *tables);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
 bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode: a mono stream, every frame its own W-point transform
 // chirp-z through the composite stages of the mixed-radix kernel (stft_mixed.hip): L = 512 .. 16384, i.e. W = 86 .. 5461
 bool chirpz_supported(uint32_t W);
 hipError_t chirpz_init(sgx_ctx *c, void **out);
 void chirpz_destroy(void *tables);
 bool chirpz_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode, as mixed_real_serves
-hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables);   // one kernel from PCM to pixels at this length, palette and row table
 bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables);    // one kernel from PCM to the rows' (l, r) means at this length and row table
-hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                              size_t n_frames, size_t total_frames, float *d_bands);
-hipError_t launch_render_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                               size_t n_frames, size_t total_frames, uint8_t *d_rgba);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
-hipError_t launch_stft_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16 = false,
-                             bool out_c64 = false);   // out_f16: (l, r) half pairs, 4 B per bin
 bool bluestein_supported(uint32_t W);
 hipError_t bluestein_init(sgx_ctx *c, void **out);
 void bluestein_destroy(void *tables);
-hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                 size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
-hipError_t launch_stft_wg4096_f16(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                  size_t first_frame, size_t n_frames, size_t total_frames, void *d_mags_f16);
 // stft_large.hip: lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM), W up to 2^20: four-step passes through a scratch the
 // context holds (allocated here, at create time), direct for a 2-3-5-7-smooth 2W, chirp-z otherwise
 bool large_supported(uint32_t W);
 hipError_t large_init(sgx_ctx *c, void **out);
 void large_destroy(void *tables);
-hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64 = false);
 // stft_istft.hip: the inverse of sgx_stft_batch_complex by weighted overlap-add; route 1 = the composite stages of 2W points,
 // 2 = chirp-z through a power-of-two plan, 0 = none (the lengths only kernel 11 serves)
 int istft_route(const sgx_ctx *c);

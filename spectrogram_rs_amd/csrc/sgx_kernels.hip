@@ -177,10 +177,15 @@ __global__ void __launch_bounds__(1024) stft_generic_complex_kernel(StftGenericP
     }
 }
 
-hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                               size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
+hipError_t launch_generic(const sgx_ctx *c, const StftCall &call)
 {
-    const auto kernel = out_c64 ? stft_generic_complex_kernel : stft_generic_kernel;
+    if (call.kind != Out::kMags && call.kind != Out::kComplex) return hipErrorInvalidValue;
+    const bool complex_rows = call.kind == Out::kComplex;
+    const float *d_pcm = call.pcm;
+    float *d_mags = static_cast<float *>(call.out);
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
+    const auto kernel = complex_rows ? stft_generic_complex_kernel : stft_generic_kernel;
     if (n_frames == 0) return hipSuccess;
     StftGenericParams p{};
     p.pcm = d_pcm;
@@ -206,7 +211,7 @@ hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t ch
     }
     p.n_frames = n_frames;
     p.total_frames = total_frames;
-    if (channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) {
+    if (paired_mono(c, channels)) {
         // one workgroup per frame PAIR (2q, 2q+1); an odd first frame / last frame shares its transform with a
         // neighbour outside the range, which is computed and not stored
         p.mono_pairs = 1;
@@ -229,7 +234,7 @@ hipError_t launch_stft_generic(const sgx_ctx *c, const float *d_pcm, uint32_t ch
         StftGenericParams q = p;
         q.first_frame = first_frame + done;
         q.n_frames = chunk;
-        q.mags = d_mags + done * (size_t)pairs * c->M * (out_c64 ? 4 : 2);
+        q.mags = d_mags + done * (size_t)pairs * c->M * (complex_rows ? 4 : 2);
         hipLaunchKernelGGL(kernel, dim3((unsigned)chunk, pairs), dim3(threads), lds, c->stream, q);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

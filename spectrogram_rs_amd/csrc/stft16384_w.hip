@@ -662,12 +662,17 @@ void w16384_destroy(void *tables)
 // stft16384_w_complex.hip: the complex-row kernels, launched on this file's parameter block (the same struct there)
 hipError_t launch_w16384_complex(const void *params, size_t params_size, bool mono, bool slide, bool direct, dim3 grid, hipStream_t stream);
 
-hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
+hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call)
 {
     using namespace w16k;
+    if (call.kind != Out::kMags && call.kind != Out::kComplex) return hipErrorInvalidValue;
+    const bool complex_rows = call.kind == Out::kComplex;
+    const float *d_pcm = call.pcm;
+    float *d_mags = static_cast<float *>(call.out);
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     if (n_frames == 0) return hipSuccess;
-    auto *t = static_cast<TablesW *>(tables);
+    auto *t = static_cast<TablesW *>(c->d_w16k);
     Params p{};
     p.T1 = t->d_T1;
     p.tw2 = t->d_tw2;
@@ -678,11 +683,8 @@ hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm
     p.total_frames = total_frames;
     p.H = c->H;
     p.pairs = pairs;
-    // Frame pairs read the partner frame through the first frame's descriptor, H * 4 bytes on as its scalar offset: that offset plus the
-    // window must stay inside the descriptor's 2^31 - 1 records (beyond them the loads return zero, and from H = 2^30 the 32-bit offset
-    // has wrapped).  A context with such a hop takes the route of unpaired frames: a property of the context, not of the call.
-    const bool pairs_fit = 4ull * ((unsigned long long)c->H + kW) <= 0x7fffffffull;
-    const bool mono = channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && pairs_fit;
+    // (a hop whose frame pairs do not fit a descriptor takes the route of unpaired frames)
+    const bool mono = paired_mono(c, channels) && descriptor_pairs_fit(c->H, kW);
     // a mono stream whose frames are not paired (the default): every frame the (s, s) transform of the reference
     // (audio_input_list_model.rs:67-69) -- the sample range duplicated into one (s, s) plane, then the two-channel kernel
     const bool dup = channels == 1 && !mono;
@@ -695,17 +697,11 @@ hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm
         const size_t first_sample = first_frame * (size_t)c->H;
         const size_t n_samp = (n_frames - 1) * (size_t)c->H + kW;
         const size_t plane = (2 * n_samp + 63) & ~(size_t)63;  // floats
-        if (plane > t->planes_floats) {
-            hipError_t e = hipStreamSynchronize(c->stream);  // a previous launch may still read the old plane
-            if (e != hipSuccess) return e;
-            if (t->d_planes) { (void)hipFree(t->d_planes); t->d_planes = nullptr; t->planes_floats = 0; }
-            e = hipMalloc(reinterpret_cast<void **>(&t->d_planes), plane * sizeof(float));
-            if (e != hipSuccess) return e;
-            t->planes_floats = plane;
-        }
+        hipError_t e = grow(c->stream, t->d_planes, t->planes_floats, plane, plane * sizeof(float));   // (a previous launch may still read the old plane)
+        if (e != hipSuccess) return e;
         const unsigned blocks = (unsigned)std::min<size_t>((n_samp + 255) / 256, (size_t)c->n_cu * 16);
         hipLaunchKernelGGL(w16k::duplicate_mono_kernel, dim3(blocks), dim3(256), 0, c->stream, d_pcm, t->d_planes, first_sample, n_samp);
-        const hipError_t e = hipGetLastError();
+        e = hipGetLastError();
         if (e != hipSuccess) return e;
         p.pcm = t->d_planes;
         p.plane_floats = plane;
@@ -733,7 +729,7 @@ hipError_t launch_stft_w16384(const sgx_ctx *c, void *tables, const float *d_pcm
         p.xcds = blocks % kXcdHint == 0 ? kXcdHint : 1u;
     }
     const dim3 grid((unsigned)blocks), block(512);
-    if (out_c64) return launch_w16384_complex(&p, sizeof p, mono, slide, direct, grid, c->stream);   // stft16384_w_complex.hip
+    if (complex_rows) return launch_w16384_complex(&p, sizeof p, mono, slide, direct, grid, c->stream);   // stft16384_w_complex.hip
     if (mono) hipLaunchKernelGGL((stft16384_w_kernel<true>), grid, block, kLdsBytes, c->stream, p);
     else if (slide && direct) hipLaunchKernelGGL((stft16384_w_kernel<false, true, true>), grid, block, kLdsBytes, c->stream, p);
     else if (slide) hipLaunchKernelGGL((stft16384_w_kernel<false, false, true>), grid, block, kLdsBytes, c->stream, p);

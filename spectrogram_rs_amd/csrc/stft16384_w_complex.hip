@@ -9,7 +9,7 @@
 
 namespace sgx {
 
-// params: stft16384_w.hip's w16k::Params, filled by launch_stft_w16384 (the same definition, compiled into w16kc here)
+// params: stft16384_w.hip's w16k::Params, filled by launch_w16384 (the same definition, compiled into w16kc here)
 hipError_t launch_w16384_complex(const void *params, size_t params_size, bool mono, bool slide, bool direct, dim3 grid, hipStream_t stream)
 {
     using namespace w16kc;

@@ -630,44 +630,42 @@ bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels)
 
 namespace wg {
 
-// p: as launch_wg (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
+// p: as launch_wg4096 (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
 // transform's own tables and the job split are set here
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands, bool out_c64, bool peak)
+hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
 {
     using namespace wgr;
     if (p.n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const RealTables *>(real_tables);
+    const auto *t = static_cast<const RealTables *>(c->d_real);
+    const bool hold_peak = kind == Out::kPeak;
     p.tw1 = t->d_tw1;
     p.tw2 = t->d_tw2;
     p.twu = t->d_twu;
     p.stream_samples = p.total_frames ? (p.total_frames - 1) * (unsigned long long)c->H + (unsigned long long)kW : 0;   // what the stream's frames cover (the caller may hold more)
     p.n_jobs = (p.n_frames + 1) / 2;
-    unsigned long long blocks = (unsigned long long)c->n_cu * 4;   // persistent workgroups, four per CU, each a contiguous run of frame pairs
-    unsigned long long per = (p.n_jobs + blocks - 1) / blocks;
-    if (per < 1) per = 1;
-    if (peak) {   // sgx_bands_peak_batch: a run is 2 per frames
-        per = peak_align_run(per, 2, p.peak_group);
-        p.peak_run = 2 * per;
+    RunSplit runs = run_split(c, p.n_jobs, 4);   // persistent workgroups, four per CU, each a contiguous run of frame pairs
+    if (hold_peak) {   // sgx_bands_peak_batch: a run is 2 per frames
+        runs = runs_of(p.n_jobs, peak_align_run(runs.per, 2, p.peak_group));
+        p.peak_run = 2 * runs.per;
     }
-    blocks = (p.n_jobs + per - 1) / per;
-    p.jobs_per_block = per;
-    const dim3 grid((unsigned)blocks), block(256);
+    p.jobs_per_block = runs.per;
+    const dim3 grid((unsigned)runs.blocks), block(256);
     auto launch = [&](auto slide_c) {
         constexpr bool S_ = decltype(slide_c)::value;
         constexpr size_t lds_rows = (S_ && SGX_ADDTID_R) ? kLdsBytesR : kLdsBytes, lds_render = (S_ && SGX_ADDTID_R) ? kLdsBytesRenderR : kLdsBytesRender;
-        if (render && bands && peak) {
+        if (hold_peak) {
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCubic, S_>), grid, block, lds_rows, c->stream, p);
-        } else if (render && bands) {   // (no palette: the row-image LDS size)
+        } else if (kind == Out::kBands) {   // (no palette: the row-image LDS size)
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCubic, S_>), grid, block, lds_rows, c->stream, p);
-        } else if (render) {
+        } else if (kind == Out::kRgba) {
             if (!p.seed_pm1) hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixGeneric, S_>), grid, block, lds_render, c->stream, p);
             else if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixCosine, S_>), grid, block, lds_render, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPixels, kPixCubic, S_>), grid, block, lds_render, c->stream, p);
-        } else if (out_c64) {
+        } else if (kind == Out::kComplex) {
             hipLaunchKernelGGL((stft4096_real_kernel<kRowsC64, kPixNone, S_>), grid, block, lds_rows, c->stream, p);
-        } else if (out_f16) {
+        } else if (kind == Out::kMagsF16) {
             hipLaunchKernelGGL((stft4096_real_kernel<kRowsF16, kPixNone, S_>), grid, block, lds_rows, c->stream, p);
         } else {
             hipLaunchKernelGGL((stft4096_real_kernel<kRowsF32, kPixNone, S_>), grid, block, lds_rows, c->stream, p);
@@ -676,7 +674,7 @@ hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, 
     if (c->H == 256) launch(std::true_type{});
     else launch(std::false_type{});
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess && peak ? launch_peak_combine(c, p, blocks) : e;
+    return e == hipSuccess && hold_peak ? launch_peak_combine(c, p, runs.blocks) : e;
 }
 
 }  // namespace wg

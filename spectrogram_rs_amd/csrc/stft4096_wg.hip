@@ -778,28 +778,24 @@ bool wg4096_seed_is_within_one(const sgx_ctx *c)
     return !(c->cfg.flags & SGX_FLAG_LUT_WALK) && wg::seed_within_one(c->pal.lut_thr, (double)a, (double)b);
 }
 
-namespace {
-
-// RENDER: the fused column into d_rgba -- RGBA pixels, or with `bands` the (l, r) means as float2 per row
-template <bool RENDER>
-hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                     size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, uint8_t *d_rgba, bool out_f16 = false,
-                     bool bands = false, bool out_c64 = false, size_t peak_group = 0)
+// One launcher for every Out.  `column`: the fused column into call.out -- RGBA pixels, or with `bands` the (l, r) means as float2 per row,
+// held as a running maximum over call.peak_group frames where that is set (sgx_bands_peak_batch)
+hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
 {
     using namespace wg;
+    const float *d_pcm = call.pcm;
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n;
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const WgTables *>(tables);
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    // peak_group (with `bands`): sgx_bands_peak_batch, d_rgba the columns; the partial columns of every persistent workgroup
-    const size_t partial_floats = (size_t)(n_cu > c->n_cu ? n_cu : c->n_cu) * 4 * 2 * c->R * 2;
-    if (peak_group && partial_floats > t->peak_partial_floats) {
-        hipError_t e = hipStreamSynchronize(c->stream);  // a previous launch may still use the old buffer
+    const auto *t = static_cast<const WgTables *>(c->d_fast_wg);
+    const bool band_means = call.kind == Out::kBands || call.kind == Out::kPeak, column = band_means || call.kind == Out::kRgba;
+    const size_t peak_group = call.kind == Out::kPeak ? call.peak_group : 0;
+    if (call.kind == Out::kPeak && peak_group == 0) return hipErrorInvalidValue;
+    // the partial columns of every persistent workgroup
+    if (peak_group) {
+        const size_t partial_floats = (size_t)c->n_cu * 4 * 2 * c->R * 2;
+        const hipError_t e = grow(c->stream, t->d_peak_partial, t->peak_partial_floats, partial_floats, partial_floats * sizeof(float));
         if (e != hipSuccess) return e;
-        if (t->d_peak_partial) { (void)hipFree(t->d_peak_partial); t->d_peak_partial = nullptr; t->peak_partial_floats = 0; }
-        e = hipMalloc(reinterpret_cast<void **>(&t->d_peak_partial), partial_floats * sizeof(float));
-        if (e != hipSuccess) return e;
-        t->peak_partial_floats = partial_floats;
     }
     // More than two channels: the (l, r) pairs are split into planes first and every pair runs the two-channel kernel on its
     // own plane.  (Reading a pair at a stride of C floats kept the strided variant at the register cap with 60-68 bytes of
@@ -808,15 +804,9 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
     if (channels > 2) {
         const size_t first_sample = first_frame * (size_t)c->H, n_samp = (n_frames - 1) * (size_t)c->H + kW;
         plane_floats = (2 * n_samp + 63) & ~(size_t)63;
-        if (plane_floats * pairs > t->planes_floats) {
-            hipError_t e = hipStreamSynchronize(c->stream);  // a previous launch may still read the old planes
-            if (e != hipSuccess) return e;
-            if (t->d_planes) { (void)hipFree(t->d_planes); t->d_planes = nullptr; t->planes_floats = 0; }
-            e = hipMalloc(reinterpret_cast<void **>(&t->d_planes), plane_floats * pairs * sizeof(float));
-            if (e != hipSuccess) return e;
-            t->planes_floats = plane_floats * pairs;
-        }
-        const hipError_t e = launch_deinterleave_pairs(c, d_pcm, t->d_planes, plane_floats, first_sample, n_samp, channels, pairs);
+        hipError_t e = grow(c->stream, t->d_planes, t->planes_floats, plane_floats * pairs, plane_floats * pairs * sizeof(float));   // (a previous launch may still read the old planes)
+        if (e != hipSuccess) return e;
+        e = launch_deinterleave_pairs(c, d_pcm, t->d_planes, plane_floats, first_sample, n_samp, channels, pairs);
         if (e != hipSuccess) return e;
     }
     for (uint32_t pair = 0; pair < pairs; ++pair) {
@@ -825,11 +815,11 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         p.tw1 = t->d_tw1;
         p.tw2 = t->d_tw2;
         p.window = c->d_window;
-        p.mags = d_mags;
-        p.out_f16 = out_f16 ? 1u : 0u;
+        p.mags = column ? nullptr : static_cast<float *>(call.out);
+        p.out_f16 = call.kind == Out::kMagsF16 ? 1u : 0u;
         p.first_frame = first_frame;
         p.n_frames = n_frames;
-        p.total_frames = total_frames;
+        p.total_frames = call.total;
         p.H = c->H;
         p.C = channels;
         p.pairs = pairs;
@@ -842,16 +832,16 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
             p.pair_l = 0;
             p.pair_r = 1;
         }
-        if (RENDER) {
+        if (column) {
             p.rows = t->d_rows;
             p.samples = t->d_samples;
             p.n_samples = t->n_samples;
             p.lut_thr = c->d_lut_thr;
             p.lut_rgba = c->d_lut_rgba;
-            p.rgba = d_rgba;
+            p.rgba = static_cast<uint8_t *>(call.out);
             p.R = c->R;
             p.interp = c->cfg.interp;
-            if (!bands) {
+            if (!band_means) {
                 lut_seed_coefficients(c, p.guess_a, p.guess_b);
                 p.seed_pm1 = wg4096_seed_is_within_one(c) ? 1u : 0u;
             }
@@ -865,49 +855,40 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
         // A one-channel stream (include/sgx.h, "Mono streams"): by default every frame its own real-input transform
         // (stft4096_real.hip); SGX_FLAG_PAIRED_FRAMES: two frames per transform; SGX_FLAG_COMPLEX_MONO: every frame as its own (s, s)
         // transform
-        const uint32_t fl = c->cfg.flags;      // (sgx_create: INDEPENDENT is set unless PAIRED was asked for)
-        const bool own_transform = !(fl & SGX_FLAG_PAIRED_FRAMES) || (fl & SGX_FLAG_COMPLEX_MONO) != 0;
-        if (channels == 1 && own_transform && !(fl & SGX_FLAG_COMPLEX_MONO) && real4096_serves(c, d_pcm, channels))
-            return launch_real4096(c, c->d_real, p, out_f16, RENDER, bands, out_c64, peak_group != 0);
-        const bool mono = channels == 1 && (fl & SGX_FLAG_PAIRED_FRAMES) && !(fl & SGX_FLAG_COMPLEX_MONO);
+        const bool mono = paired_mono(c, channels);
+        if (channels == 1 && !mono && !(c->cfg.flags & SGX_FLAG_COMPLEX_MONO) && real4096_serves(c, d_pcm, channels))
+            return launch_real4096(c, p, call.kind);
         p.pair_base = mono ? first_frame / 2 : 0;
         p.n_jobs = mono ? (first_frame + n_frames + 1) / 2 - first_frame / 2 : n_frames;
         // persistent workgroups, 4 per CU; each owns a contiguous run of transforms so that the
         // overlapping audio of consecutive frames is re-read from L1/L2, not HBM
-        unsigned long long blocks = (unsigned long long)n_cu * 4;
-        unsigned long long per = (p.n_jobs + blocks - 1) / blocks;
-        if (per < 1) per = 1;
+        RunSplit runs = run_split(c, p.n_jobs, 4);
         if (peak_group) {
             if (mono) return hipErrorInvalidValue;   // (paired frames: the workspace route, wg4096_can_fuse_peak)
-            per = peak_align_run(per, 1, peak_group);
-            p.peak_run = per;
+            runs = runs_of(p.n_jobs, peak_align_run(runs.per, 1, peak_group));
+            p.peak_run = runs.per;
         }
-        blocks = (p.n_jobs + per - 1) / per;
-        p.jobs_per_block = per;
-        const dim3 grid((unsigned)blocks), block(256);
-        const size_t lds = RENDER && !bands ? kLdsBytesRender : kLdsBytes;   // (the bands rows need no palette)
+        p.jobs_per_block = runs.per;
+        const dim3 grid((unsigned)runs.blocks), block(256);
+        const size_t lds = call.kind == Out::kRgba ? kLdsBytesRender : kLdsBytes;   // (the bands rows need no palette)
         // the pixel code of the instantiation: the interpolator and the seed-only LUT search are compile-time (kPixCubic / kPixCosine);
         // SGX_FLAG_LUT_WALK and palettes whose seed proof fails run kPixGeneric
-        const int pix = !RENDER ? kPixNone : peak_group ? (p.interp == SGX_INTERP_COSINE ? kPixPeakCosine : kPixPeakCubic)
-                                   : bands ? (p.interp == SGX_INTERP_COSINE ? kPixBandsCosine : kPixBandsCubic)
-                                   : (!p.seed_pm1 ? kPixGeneric : (p.interp == SGX_INTERP_COSINE ? kPixCosine : kPixCubic));
+        const bool cosine = p.interp == SGX_INTERP_COSINE;
+        const int pix = call.kind == Out::kComplex ? kPixRowsC64 : call.kind == Out::kMagsF16 ? kPixRowsF16 : call.kind == Out::kMags ? kPixNone
+                      : peak_group ? (cosine ? kPixPeakCosine : kPixPeakCubic) : band_means ? (cosine ? kPixBandsCosine : kPixBandsCubic)
+                      : (!p.seed_pm1 ? kPixGeneric : (cosine ? kPixCosine : kPixCubic));
         auto launch = [&](auto mono_c, auto pairing_c, auto c2_c) {
             constexpr bool M_ = decltype(mono_c)::value, C2_ = decltype(c2_c)::value;
             constexpr int P_ = decltype(pairing_c)::value;
-            if (!RENDER && out_c64) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixNone : kPixRowsC64>), grid, block, lds, c->stream, p);
-            else if (!RENDER && out_f16) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixRowsF16>), grid, block, lds, c->stream, p);
-            else if (!RENDER) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixNone>), grid, block, lds, c->stream, p);
-            else if (pix_peak(pix)) {
-                if constexpr (RENDER && !M_) {
-                    if (pix == kPixPeakCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixPeakCubic>), grid, block, lds, c->stream, p);
-                    else hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, kPixPeakCosine>), grid, block, lds, c->stream, p);
-                }
+            auto go = [&](auto pix_c) { hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, decltype(pix_c)::value>), grid, block, lds, c->stream, p); };
+            switch (pix) {
+#define PIX(K) case K: go(std::integral_constant<int, K>{}); break;
+            PIX(kPixRowsC64) PIX(kPixRowsF16) PIX(kPixNone) PIX(kPixBandsCubic) PIX(kPixBandsCosine) PIX(kPixCubic) PIX(kPixCosine) PIX(kPixGeneric)
+            case kPixPeakCubic: case kPixPeakCosine:   // (no peak instantiation pairs frames: refused above)
+                if constexpr (!M_) { if (pix == kPixPeakCubic) go(std::integral_constant<int, kPixPeakCubic>{}); else go(std::integral_constant<int, kPixPeakCosine>{}); }
+                break;
+#undef PIX
             }
-            else if (pix == kPixBandsCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCubic : kPixNone>), grid, block, lds, c->stream, p);
-            else if (pix == kPixBandsCosine) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixBandsCosine : kPixNone>), grid, block, lds, c->stream, p);
-            else if (pix == kPixCubic) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixCubic : kPixNone>), grid, block, lds, c->stream, p);
-            else if (pix == kPixCosine) hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixCosine : kPixNone>), grid, block, lds, c->stream, p);
-            else hipLaunchKernelGGL((stft4096_wg_kernel<M_, P_, C2_, RENDER ? kPixGeneric : kPixNone>), grid, block, lds, c->stream, p);
         };
         using T = std::true_type;
         using F = std::false_type;
@@ -924,54 +905,17 @@ hipError_t launch_wg(const sgx_ctx *c, const void *tables, const float *d_pcm, u
             launch(F{}, std::integral_constant<int, kPairAdjacent>{}, T{});
         }
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess && peak_group) e = launch_peak_combine(c, p, blocks);
+        if (e == hipSuccess && peak_group) e = launch_peak_combine(c, p, runs.blocks);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-}  // namespace
-
-hipError_t launch_stft_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
-{
-    return launch_wg<false>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, d_mags, nullptr, false, false, out_c64);
-}
-
-hipError_t launch_stft_wg4096_f16(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                  size_t first_frame, size_t n_frames, size_t total_frames, void *d_mags_f16)
-{
-    return launch_wg<false>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, static_cast<float *>(d_mags_f16), nullptr, true);
-}
-
-hipError_t launch_render_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                size_t first_frame, size_t n_frames, size_t total_frames, uint8_t *d_rgba)
-{
-    return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr, d_rgba);
-}
-
-hipError_t launch_bands_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_bands)
-{
-    return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr,
-                           reinterpret_cast<uint8_t *>(d_bands), false, true);
-}
-
-// sgx_bands_peak_batch in one kernel: every stream launch_bands_wg4096 serves but paired mono frames (two frames of one transform may
+// sgx_bands_peak_batch in one kernel: every stream the bands column serves but paired mono frames (two frames of one transform may
 // fall into different columns of different workgroups' bookkeeping: those contexts take the workspace route)
 bool wg4096_can_fuse_peak(const sgx_ctx *c, const void *tables)
 {
-    const uint32_t fl = c->cfg.flags;
-    const bool paired = c->C == 1 && (fl & SGX_FLAG_PAIRED_FRAMES) && !(fl & SGX_FLAG_COMPLEX_MONO);
-    return wg4096_can_fuse_bands(c, tables) && !paired;
-}
-
-// group: 1 .. n_frames.  d_peak: float2 [ceil(n_frames / group)][pairs][R]
-hipError_t launch_bands_peak_wg4096(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                    size_t first_frame, size_t n_frames, size_t total_frames, size_t group, float *d_peak)
-{
-    return launch_wg<true>(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr,
-                           reinterpret_cast<uint8_t *>(d_peak), false, true, false, group);
+    return wg4096_can_fuse_bands(c, tables) && !paired_mono(c, c->C);
 }
 
 }  // namespace sgx

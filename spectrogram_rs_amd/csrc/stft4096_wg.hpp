@@ -84,8 +84,7 @@ inline unsigned long long peak_align_run(unsigned long long per, unsigned fpj, u
 hipError_t launch_peak_combine(const sgx_ctx *c, const Params &p, unsigned long long blocks);   // stft4096_wg.hip
 
 // stft4096_real.hip
-hipError_t launch_real4096(const sgx_ctx *c, const void *real_tables, Params p, bool out_f16, bool render, bool bands = false,
-                          bool out_c64 = false, bool peak = false);   // out_c64: complex rows (sgx_stft_batch_complex); peak: p.peak_group, p.peak_partial
+hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind);   // kPeak: p.peak_group, p.peak_partial
 
 // Which two mono frames share a transform: always (2j, 2j+1).
 //   kPairAdjacentRow : H = 256: frame 2j+1's rows are frame 2j's rows shifted by one (9 rows feed both)

@@ -403,43 +403,39 @@ void w4800_destroy(void *tables)
     delete t;
 }
 
-hipError_t launch_stft_w4800(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, size_t first_frame, size_t n_frames,
-                               size_t total_frames, float *d_mags, bool out_f16, bool out_c64)
+hipError_t launch_w4800(const sgx_ctx *c, const StftCall &call)
 {
     using namespace w48;
+    const uint32_t channels = call.channels;
+    const size_t first_frame = call.first, n_frames = call.n;
     if (n_frames == 0) return hipSuccess;
-    if (channels > 2) return hipErrorInvalidValue;   // (the caller sends more channels to the composite-radix kernel)
-    const auto *t = static_cast<const W48Tables *>(tables);
+    // (the caller sends more channels, and the fused columns, to the composite-radix kernel)
+    if (channels > 2 || (call.kind != Out::kMags && call.kind != Out::kMagsF16 && call.kind != Out::kComplex)) return hipErrorInvalidValue;
+    const auto *t = static_cast<const W48Tables *>(c->d_w4800);
     Params p{};
-    p.pcm = d_pcm;
+    p.pcm = call.pcm;
     p.tw1 = t->d_tw1;
     p.tw2 = t->d_tw2;
     p.window = c->d_window;
-    p.mags = d_mags;
+    p.mags = static_cast<float *>(call.out);
     p.first_frame = first_frame;
     p.n_frames = n_frames;
-    p.total_frames = total_frames;
+    p.total_frames = call.total;
     p.H = c->H;
     p.pairs = 1;
     p.half_scale = 0.5f * (2.0f / (float)c->W);
-    // Frame pairs read the partner frame through the first frame's descriptor, H * 4 bytes on as its scalar offset: that offset plus the
-    // window must stay inside the descriptor's 2^31 - 1 records (beyond them the loads return zero, and from H = 2^30 the 32-bit offset
-    // has wrapped).  A context with such a hop runs every frame as its own (s, s) transform: a property of the context, not of the call.
-    const bool pairs_fit = 4ull * ((unsigned long long)c->H + kW) <= 0x7fffffffull;
-    const int mode = channels == 2 ? 0 : (((c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && pairs_fit) ? 1 : 2);
+    // (a hop whose frame pairs do not fit a descriptor runs every frame as its own (s, s) transform)
+    const int mode = channels == 2 ? 0 : (paired_mono(c, channels) && descriptor_pairs_fit(c->H, kW) ? 1 : 2);
     p.pair_base = mode == 1 ? first_frame / 2 : 0;
     p.n_jobs = mode == 1 ? (first_frame + n_frames + 1) / 2 - first_frame / 2 : n_frames;
     // persistent workgroups, three per CU, each with a contiguous run of transforms: neighbouring frames share 96 % of their samples
-    unsigned long long blocks = (unsigned long long)(c->n_cu > 0 ? c->n_cu : 256) * 3;
-    unsigned long long per = (p.n_jobs + blocks - 1) / blocks;
-    if (per < 1) per = 1;
-    blocks = (p.n_jobs + per - 1) / per;
-    p.jobs_per_block = per;
-    const dim3 grid((unsigned)blocks), block(kT);
+    const RunSplit runs = run_split(c, p.n_jobs, 3);
+    p.jobs_per_block = runs.per;
+    const dim3 grid((unsigned)runs.blocks), block(kT);
 #define W48_GO(MODE_) \
     do { \
-        if (out_c64) hipLaunchKernelGGL((stft4800_wg_kernel<4 + MODE_, false>), grid, block, kLdsBytes, c->stream, p); \
-        else if (out_f16) hipLaunchKernelGGL((stft4800_wg_kernel<MODE_, true>), grid, block, kLdsBytes, c->stream, p); \
+        if (call.kind == Out::kComplex) hipLaunchKernelGGL((stft4800_wg_kernel<4 + MODE_, false>), grid, block, kLdsBytes, c->stream, p); \
+        else if (call.kind == Out::kMagsF16) hipLaunchKernelGGL((stft4800_wg_kernel<MODE_, true>), grid, block, kLdsBytes, c->stream, p); \
         else hipLaunchKernelGGL((stft4800_wg_kernel<MODE_, false>), grid, block, kLdsBytes, c->stream, p); \
     } while (0)
     if (mode == 0) W48_GO(0);

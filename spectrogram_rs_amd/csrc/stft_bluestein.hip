@@ -233,13 +233,18 @@ void bluestein_destroy(void *tables)
     delete t;
 }
 
-hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                                 size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
+hipError_t launch_bluestein(const sgx_ctx *c, const StftCall &call)
 {
     using namespace blu;
-    const auto kernel = out_c64 ? stft_bluestein_complex_kernel : stft_bluestein_kernel;
+    if (call.kind != Out::kMags && call.kind != Out::kComplex) return hipErrorInvalidValue;
+    const bool complex_rows = call.kind == Out::kComplex;
+    const float *d_pcm = call.pcm;
+    float *d_mags = static_cast<float *>(call.out);
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
+    const auto kernel = complex_rows ? stft_bluestein_complex_kernel : stft_bluestein_kernel;
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const BluTables *>(tables);
+    const auto *t = static_cast<const BluTables *>(c->d_blu);
     Params p{};
     p.pcm = d_pcm;
     p.window = c->d_window;
@@ -262,7 +267,7 @@ hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const flo
     p.first_frame = first_frame;
     p.n_frames = n_frames;
     p.total_frames = total_frames;
-    if (channels == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) {
+    if (paired_mono(c, channels)) {
         p.mono_pairs = 1;
         p.mags = d_mags;
         const unsigned long long q0 = first_frame / 2, q1 = (first_frame + n_frames + 1) / 2;
@@ -279,7 +284,7 @@ hipError_t launch_stft_bluestein(const sgx_ctx *c, const void *tables, const flo
         const size_t chunk = n_frames - done < max_chunk ? n_frames - done : max_chunk;
         p.first_frame = first_frame + done;
         p.n_frames = chunk;
-        p.mags = d_mags + done * (size_t)pairs * c->M * (out_c64 ? 4 : 2);
+        p.mags = d_mags + done * (size_t)pairs * c->M * (complex_rows ? 4 : 2);
         hipLaunchKernelGGL(kernel, dim3((unsigned)chunk, pairs), dim3(threads), lds, c->stream, p);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

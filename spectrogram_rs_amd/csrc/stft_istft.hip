@@ -297,7 +297,7 @@ static void cis_pi(unsigned long long x, uint32_t W, double &re, double &im)
 
 int istft_route(const sgx_ctx *c)
 {
-    if (c->stft_kernel == 11) return 0;
+    if (c->stft_kernel == kKernelLarge) return 0;
     if (c->W > istft::kMaxRing * 512) return 0;   // (no such W outside kernel 11: mixed_supported and bluestein_supported stop below)
     if (mixed_supported(c->W)) return 1;
     if (bluestein_supported(c->W)) return 2;

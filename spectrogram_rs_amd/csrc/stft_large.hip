@@ -448,13 +448,18 @@ void large_destroy(void *tables)
     delete t;
 }
 
-hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
+hipError_t launch_large(const sgx_ctx *c, const StftCall &call)
 {
     using namespace large;
+    if (call.kind != Out::kMags && call.kind != Out::kComplex) return hipErrorInvalidValue;
+    const bool complex_rows = call.kind == Out::kComplex;
+    const float *d_pcm = call.pcm;
+    float *d_mags = static_cast<float *>(call.out);
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     (void)total_frames;   // every frame its own transform: no frame pairing
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const LargeTables *>(tables);
+    const auto *t = static_cast<const LargeTables *>(c->d_large);
     const Plan &pl = t->pl;
     Params p{};
     p.pcm = d_pcm;
@@ -490,7 +495,7 @@ hipError_t launch_stft_large(const sgx_ctx *c, const void *tables, const float *
         hipLaunchKernelGGL(large_cols_kernel<true>, dim3(gx_cols, m), dim3(kThreads), lds_cols, c->stream, p);
         hipLaunchKernelGGL(large_rows_kernel, dim3(gx_rows, m), dim3(kThreads), lds_rows, c->stream, p);
         if (pl.chirp) hipLaunchKernelGGL(large_cols_kernel<false>, dim3(gx_cols, m), dim3(kThreads), lds_cols, c->stream, p);
-        if (out_c64) hipLaunchKernelGGL(large_split_complex_kernel, dim3(gx_split, m), dim3(kThreads), 0, c->stream, p);
+        if (complex_rows) hipLaunchKernelGGL(large_split_complex_kernel, dim3(gx_split, m), dim3(kThreads), 0, c->stream, p);
         else hipLaunchKernelGGL(large_split_kernel, dim3(gx_split, m), dim3(kThreads), 0, c->stream, p);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

@@ -711,7 +711,7 @@ hipError_t launch_kernel(K kernel, const Params &p, unsigned nt, dim3 grid, size
 // two frames per workgroup, as it chose them), writing the (l, r) means instead; hipErrorNotSupported when no bands kernel has that plan
 hipError_t launch_bands_kernel(const Params &p, int fixed, bool real, bool two_frames, dim3 grid, size_t lds, hipStream_t stream);
 bool bands_kernel_exists(int fixed, bool real, bool two_frames);
-// the complex-row instantiations (stft_mixed_complex.hip, sgx_stft_batch_complex): the row kernel launch_mixed / launch_stft_chirpz would run
+// the complex-row instantiations (stft_mixed_complex.hip, sgx_stft_batch_complex): the row kernel launch_mixed / launch_chirpz would run
 hipError_t launch_complex_kernel(const Params &p, int fixed, bool real, unsigned threads, dim3 grid, size_t lds, hipStream_t stream);
 hipError_t launch_chirpz_complex_kernel(const Params &p, uint32_t L, bool real, dim3 grid, size_t lds, hipStream_t stream);
 
@@ -969,19 +969,31 @@ static bool real_two_frames(int fixed)   // real-input mode to pixels or bands: 
     return false;
 }
 
-static bool real_column_fits(const sgx_ctx *c, const mix::MixTables *t)
+// the threads of a compile-time plan (0: `fixed` names none); real_render: as real-input mode runs it to a column, two plans wider
+static unsigned plan_threads(int fixed, bool real_render = false)
 {
-    const auto *h = t->half;
-    if (!h || !h->fixed) return false;
     unsigned nt = 0;
-#define X(Pn, A0, B0, A1, B1, A2, B2, N) if (h->fixed == Pn) nt = N;
+#define X(Pn, A0, B0, A1, B1, A2, B2, N) if (fixed == Pn) nt = N;
     MIX_FIXED_PLANS(X)
-    MIX_REAL_RENDER_PLANS(X)
+    if (real_render) { MIX_REAL_RENDER_PLANS(X) }
 #undef X
-#define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N) if (h->fixed == Pn) nt = N;
+#define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N) if (fixed == Pn) nt = N;
     MIX_FIXED4_PLANS(X)
 #undef X
+    return nt;
+}
+
+// the column and its interpolated samples on the transform's LDS image; ten bins per thread in registers at most
+static bool real_column_fits(const sgx_ctx *c, const mix::MixTables *t)
+{
+    const unsigned nt = t->half ? plan_threads(t->half->fixed, true) : 0;
     return nt && c->W / 2 <= nt * 10u && ((size_t)c->M + 1 + c->tab.samples.size()) * sizeof(float2) <= 160 * 1024;
+}
+
+static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t)
+{
+    const unsigned nt = t ? plan_threads(t->fixed) : 0;
+    return nt && (size_t)c->M + 1 + c->tab.samples.size() <= t->lds_points && c->M <= nt * 10u;
 }
 
 static bool real_fuses_render(const sgx_ctx *c, const mix::MixTables *t) { return fused_palette(c) && real_column_fits(c, t); }
@@ -990,8 +1002,6 @@ static bool real_fuses_bands(const sgx_ctx *c, const mix::MixTables *t)
 {
     return real_column_fits(c, t) && mix::bands_kernel_exists(t->half->fixed, true, real_two_frames(t->half->fixed));
 }
-
-static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t);
 
 bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables)
 {
@@ -1009,20 +1019,6 @@ bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables)
     return mixed_column_fits(c, t) && mix::bands_kernel_exists(t->fixed, false, false);
 }
 
-static bool mixed_column_fits(const sgx_ctx *c, const mix::MixTables *t)
-{
-    if (!t || !t->fixed) return false;
-    // the column and its interpolated samples on the transform's LDS image; ten bins per thread in registers at most
-    unsigned nt = 0;
-#define X(Pn, A0, B0, A1, B1, A2, B2, N) if (t->fixed == Pn) nt = N;
-    MIX_FIXED_PLANS(X)
-#undef X
-#define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N) if (t->fixed == Pn) nt = N;
-    MIX_FIXED4_PLANS(X)
-#undef X
-    return nt && (size_t)c->M + 1 + c->tab.samples.size() <= t->lds_points && c->M <= nt * 10u;
-}
-
 // The frames p.first_frame .. + p.n_frames in launches of at most 2^30 workgroups (gridDim.x is limited to 2^31 - 1).  launch(grid) starts
 // one with p as this leaves it and returns the error of setting it up.  A mono stream under SGX_FLAG_PAIRED_FRAMES: one workgroup per frame
 // PAIR (2q, 2q+1) by global index, every launch addressing the whole range's rows.  Otherwise one per frame and channel pair, every launch
@@ -1033,7 +1029,7 @@ template <typename Launch>
 static hipError_t launch_chunks(const sgx_ctx *c, mix::Params &p, float *d_mags, size_t mags_stride, uint8_t *d_rgba, size_t rgba_stride, Launch launch)
 {
     const size_t first_frame = p.first_frame, n_frames = p.n_frames, max_chunk = 1u << 30;
-    if (p.C == 1 && (c->cfg.flags & SGX_FLAG_PAIRED_FRAMES)) {
+    if (paired_mono(c, p.C)) {
         p.mono_pairs = 1;
         p.mags = d_mags;
         const unsigned long long q0 = first_frame / 2, q1 = (first_frame + n_frames + 1) / 2;
@@ -1059,39 +1055,22 @@ static hipError_t launch_chunks(const sgx_ctx *c, mix::Params &p, float *d_mags,
     return hipSuccess;
 }
 
-static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
-                               bool bands = false, bool out_c64 = false);
-
-hipError_t launch_stft_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                             size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, bool out_c64)
-{
-    return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, d_mags, out_f16, nullptr, false, out_c64);
-}
-
-hipError_t launch_render_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                               size_t n_frames, size_t total_frames, uint8_t *d_rgba)
-{
-    return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr, false, d_rgba);
-}
-
-hipError_t launch_bands_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs, size_t first_frame,
-                              size_t n_frames, size_t total_frames, float *d_bands)
-{
-    return launch_mixed(c, tables, d_pcm, channels, pairs, first_frame, n_frames, total_frames, nullptr, false,
-                        reinterpret_cast<uint8_t *>(d_bands), true);
-}
-
 // d_rgba: the fused column -- RGBA pixels, or with `bands` float2 (l, r) means per row (sgx_bands_batch)
-static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                               size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_f16, uint8_t *d_rgba,
-                               bool bands, bool out_c64)
+hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call)
 {
+    if (call.kind == Out::kPeak) return hipErrorInvalidValue;
+    const void *tables = c->d_mix;
+    const float *d_pcm = call.pcm;
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
+    const bool band_means = call.kind == Out::kBands, half_rows = call.kind == Out::kMagsF16, complex_rows = call.kind == Out::kComplex;
+    uint8_t *d_rgba = band_means || call.kind == Out::kRgba ? static_cast<uint8_t *>(call.out) : nullptr;
+    float *d_mags = d_rgba ? nullptr : static_cast<float *>(call.out);
     using namespace mix;
     if (n_frames == 0) return hipSuccess;
     const auto *t = static_cast<const MixTables *>(tables);
     // a mono stream, every frame its own transform (the default): real-input mode on the W-point plan, where there is one
-    const bool real = mixed_real_serves(c, tables, channels) && (!d_rgba || (bands ? real_fuses_bands(c, t) : real_fuses_render(c, t)));
+    const bool real = mixed_real_serves(c, tables, channels) && (!d_rgba || (band_means ? real_fuses_bands(c, t) : real_fuses_render(c, t)));
     if (real) t = t->half;
     Params p{};
     if (d_rgba) {
@@ -1103,7 +1082,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         p.rows = c->d_rows;
         p.samples = c->d_samples;
         p.pal = c->d_pal_seed;
-        if (!bands) lut_seed_coefficients(c, p.guess_a, p.guess_b);
+        if (!band_means) lut_seed_coefficients(c, p.guess_a, p.guess_b);
     }
     p.pcm = d_pcm;
     p.window = c->d_window;
@@ -1118,7 +1097,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
     p.pairs = pairs;
     p.scale = 2.0f / (float)c->W;
     p.n_stages = t->n_stages;
-    p.out_f16 = out_f16 ? 1u : 0u;
+    p.out_f16 = half_rows ? 1u : 0u;
     p.inv_pad = t->pad_every ? 1.0f / (float)t->pad_every : 0.0f;
     for (uint32_t i = 0; i < t->n_stages; ++i) {
         p.ra[i] = t->ra[i];
@@ -1142,9 +1121,9 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
     const unsigned threads = t->threads;
     auto go = [&](auto kernel, unsigned nt, dim3 grid) { return launch_kernel(kernel, p, nt, grid, lds, c->stream); };
     auto launch = [&](dim3 grid) -> hipError_t {
-        if (bands) return launch_bands_kernel(p, t->fixed, real, two_frames, grid, lds, c->stream);
+        if (band_means) return launch_bands_kernel(p, t->fixed, real, two_frames, grid, lds, c->stream);
         // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
-        if (out_c64) return launch_complex_kernel(p, t->fixed, real, threads, grid, lds, c->stream);
+        if (complex_rows) return launch_complex_kernel(p, t->fixed, real, threads, grid, lds, c->stream);
         if (two_frames)
             switch (t->fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N)                                                                                                  \
@@ -1178,7 +1157,7 @@ static hipError_t launch_mixed(const sgx_ctx *c, const void *tables, const float
         default: return go(stft_mixed_kernel, threads, grid);
         }
     };
-    return launch_chunks(c, p, d_mags, (size_t)pairs * c->M * (out_f16 ? 1 : (out_c64 ? 4 : 2)), d_rgba, (size_t)pairs * c->R * (bands ? 8 : 4), launch);
+    return launch_chunks(c, p, d_mags, (size_t)pairs * c->M * (half_rows ? 1 : (complex_rows ? 4 : 2)), d_rgba, (size_t)pairs * c->R * (band_means ? 8 : 4), launch);
 }
 
 // ---- chirp-z through the composite stages (see chirpz3_kernel) --------------------------------------------------------
@@ -1350,10 +1329,16 @@ void chirpz_destroy(void *tables)
     delete t;
 }
 
-hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float *d_pcm, uint32_t channels, uint32_t pairs,
-                              size_t first_frame, size_t n_frames, size_t total_frames, float *d_mags, bool out_c64)
+hipError_t launch_chirpz(const sgx_ctx *c, const StftCall &call)
 {
     using namespace mix;
+    if (call.kind != Out::kMags && call.kind != Out::kComplex) return hipErrorInvalidValue;
+    const bool complex_rows = call.kind == Out::kComplex;
+    const void *tables = c->d_chz;
+    const float *d_pcm = call.pcm;
+    float *d_mags = static_cast<float *>(call.out);
+    const uint32_t channels = call.channels, pairs = call.pairs;
+    const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     if (n_frames == 0) return hipSuccess;
     const auto *t = static_cast<const ChirpTables *>(tables);
     const bool real = chirpz_real_serves(c, tables, channels);   // a mono stream, every frame its own transform (the default)
@@ -1381,7 +1366,7 @@ hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float 
     auto go = [&](auto kernel, unsigned nt, dim3 grid) { return launch_kernel(kernel, p, nt, grid, lds, c->stream); };
     auto launch = [&](dim3 grid) -> hipError_t {
         // complex rows (sgx_stft_batch_complex): the same plan's kernel with the complex store
-        if (out_c64) return launch_chirpz_complex_kernel(p, t->L, real, grid, lds, c->stream);
+        if (complex_rows) return launch_chirpz_complex_kernel(p, t->L, real, grid, lds, c->stream);
         switch (t->L) {
 #define X(Ln, A0, B0, A1, B1, A2, B2, N)                                                                             \
     case Ln:                                                                                                         \
@@ -1398,7 +1383,7 @@ hipError_t launch_stft_chirpz(const sgx_ctx *c, const void *tables, const float 
         default: return hipErrorInvalidValue;
         }
     };
-    return launch_chunks(c, p, d_mags, (size_t)pairs * c->M * (out_c64 ? 4 : 2), nullptr, 0, launch);
+    return launch_chunks(c, p, d_mags, (size_t)pairs * c->M * (complex_rows ? 4 : 2), nullptr, 0, launch);
 }
 
 #endif  // SGX_MIXED_KERNELS_ONLY

@@ -159,7 +159,7 @@ def large_chunk(W: int) -> int:
 
 
 def chunk_boundary_frames(W: int, pairs: int, frames: int) -> list:
-    """frames on both sides of every chunk boundary of a full run (launch_stft_large: transforms frame-major, pair-minor)"""
+    """frames on both sides of every chunk boundary of a full run (launch_large: transforms frame-major, pair-minor)"""
     chunk = large_chunk(W)
     out = set()
     for t in range(chunk, frames * pairs, chunk):

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import edge_signals as es
 import oracle
 from conftest import FLOOR_K16, FLOOR_WIDE     # floors of the kernels outside BASELINE configs 1-3 (tests/conftest.py: measured need)
 
@@ -348,6 +349,22 @@ def test_process_one_mirrors_process(torch_cuda, mags_err):
     assert out.shape == (M, 2) and mags_err(out, oracle.np_truth_frame(lr, W)) <= 1.0
     assert fft.process(lr[:-1]) is None                       # fft.rs:72
     assert fft.process(iter([tuple(x) for x in lr])) is not None  # any iterable of (l, r)
+
+
+@pytest.mark.parametrize("route", es.ROUTES, ids=lambda r: r.name)
+def test_process_one_on_every_route(torch_cuda, mags_err, route):
+    """sgx_process_one is the one caller whose channel count (2) is not the context's: one (l, r) frame on the context of every route,
+    mono, four- and eight-channel ones included, against the float64 truth at the row's own floor."""
+    eng = engine(**route.engine_kwargs())
+    assert eng.info.stft_kernel == route.kernel
+    Wt = route.W
+    lr = oracle.white_noise(2 * Wt, seed=0x0E + Wt).reshape(-1, 2)
+    out = eng.process_one(lr)
+    assert out is not None and out.shape == (Wt - 1, 2)
+    err = mags_err(out, es.truth_frame(lr, Wt), route.floor)
+    print(f"{route.name}: {err:.4f}")
+    assert err <= 1.0
+    assert eng.process_one(lr[:-1]) is None                   # W - 1 pairs: None (fft.rs:72)
 
 
 def test_unsupported_length_is_reported_not_approximated(torch_cuda):
