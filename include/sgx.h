@@ -18,7 +18,13 @@
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
  *     stream; no call waits for another context's stream (tests/test_gpu_streams.py).
  *     sgx_istft_batch builds its tables on a context's first call (sgx_create does not); that first call may wait for the
- *     context's own stream, as a grown workspace does.  Later calls only enqueue.
+ *     context's own stream, as a grown workspace does.  Later calls only enqueue.  Every kernel, copy and memset of a call goes
+ *     onto the context's stream, helper passes included (tests/test_gpu_stream_routes.py holds every route and entry point to it).
+ *   - sgx_set_stream may be called at any time, also while the context's earlier work is pending.  With the stream the context
+ *     is already on it returns at once (a wrapper may bind before every call).  With another stream it orders, on the device,
+ *     everything enqueued on the new stream from now on behind everything the context has enqueued on the old one -- the context's
+ *     own buffers (workspace, planes, scratch, partial columns, tables) are shared by both -- through an event the context holds;
+ *     the host does not wait.  The stream the context leaves must still exist.  The caller's own buffers are the caller's to order.
  *   - Every function returns SGX_OK (0) or a negative sgx_status; the text of the last error is
  *     available from sgx_last_error().  The library never aborts the host process (the
  *     reference unwrap()s: fft.rs:24,77).
@@ -175,7 +181,8 @@ SGX_API int sgx_query(const sgx_ctx *ctx, sgx_info *out);
  * live-capture artefact that a batch engine must not reproduce.) */
 SGX_API size_t sgx_num_frames(const sgx_ctx *ctx, size_t n_samples);
 
-/* `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default. */
+/* `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default.  Unchanged stream: returns at once.
+ * Another stream: its later work is ordered behind the context's earlier work on the old stream; asynchronous (the conventions above). */
 SGX_API int sgx_set_stream(sgx_ctx *ctx, void *stream);
 SGX_API int sgx_sync(sgx_ctx *ctx);
 

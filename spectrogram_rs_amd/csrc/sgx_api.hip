@@ -581,6 +581,7 @@ void sgx_destroy(sgx_ctx *c)
                     c->d_lut_rgba, c->d_pal_seed, c->d_t_thr, c->d_t_cell, c->d_band_rows, c->d_band_samples, c->d_levels, c->d_ws_mags, c->d_one_in, c->d_one_out, c->d_cksum};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    if (c->rebind_event) (void)hipEventDestroy(c->rebind_event);
     delete c;
 }
 
@@ -622,7 +623,15 @@ size_t sgx_num_frames(const sgx_ctx *c, size_t n_samples)
 int sgx_set_stream(sgx_ctx *c, void *stream)
 {
     if (!c) return SGX_ERR_INVALID_ARG;
-    c->stream = reinterpret_cast<hipStream_t>(stream);
+    const hipStream_t next = reinterpret_cast<hipStream_t>(stream);
+    if (next == c->stream) return SGX_OK;   // (a wrapper that binds before every call: nothing to do, no runtime call)
+    // The context's buffers (workspace, planes, scratch, peak partials, tables) may still be in use by what it enqueued on the stream it
+    // leaves: the new stream's work is ordered behind that, on the device -- the host does not wait
+    SGX_HIP(c, hipSetDevice(c->device));
+    if (!c->rebind_event) SGX_HIP(c, hipEventCreateWithFlags(&c->rebind_event, hipEventDisableTiming));
+    SGX_HIP(c, hipEventRecord(c->rebind_event, c->stream));
+    SGX_HIP(c, hipStreamWaitEvent(next, c->rebind_event, 0));
+    c->stream = next;
     return SGX_OK;
 }
 

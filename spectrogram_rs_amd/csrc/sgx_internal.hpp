@@ -110,6 +110,7 @@ struct sgx_ctx {
     uint32_t W = 0, P = 0, M = 0, H = 0, C = 0, pairs = 0, R = 0, sr_u32 = 0, logP = 0;
     int device = 0;
     hipStream_t stream = nullptr;
+    hipEvent_t rebind_event = nullptr;   // sgx_set_stream: recorded on the stream the context leaves, waited for by the one it moves to (made by the first rebinding)
     sgx::StftKernel stft_kernel = sgx::kKernelGeneric;   // what sgx_create chose; sgx_info.stft_kernel reports the number
 
     sgx::Tables tab;

@@ -93,7 +93,9 @@ class SpectrogramEngine:
             pass
 
     def use_current_stream(self):
-        """Enqueue on torch's current stream for this device."""
+        """Enqueue on torch's current stream for this device.  Free when the context is on that stream already (sgx_set_stream
+        returns at once).  When the stream changes, what the context enqueues from now on is ordered, on the device, behind what it
+        has enqueued on the stream it leaves -- its workspace, planes and scratch are shared by both; the host does not wait."""
         import torch
 
         s = torch.cuda.current_stream(self.device)
@@ -115,7 +117,9 @@ class SpectrogramEngine:
 
     def _out(self, out, shape, dtype):
         """The caller's output buffer, checked (the kernels write shape-many elements through a raw pointer), or a
-        fresh one.  Also re-binds the context to torch's current stream: a batch call is ordered like a torch op."""
+        fresh one.  Also re-binds the context to torch's current stream: a batch call is ordered like a torch op -- behind the work
+        already on that stream, and, when the engine was last used under another stream, behind the engine's own pending work there
+        too (use_current_stream).  The tensors passed in are the caller's to order across streams, as with any torch op."""
         import torch
 
         self.use_current_stream()

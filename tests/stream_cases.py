@@ -1,0 +1,179 @@
+"""The case table of tests/test_gpu_stream_routes.py: which entry points run on which route when the context's stream is held back (a
+plain helper: no GPU, no torch at import time; tests/test_stream_cases.py checks it).
+
+Every other GPU file runs on torch's default stream, the legacy NULL stream, where a helper pass launched on stream 0 is ordered exactly
+like one launched on the context's stream.  The sweep runs every row of edge_signals.ROUTES on a non-default stream that a sleep kernel
+holds back: a kernel, copy or memset on another stream runs before its input exists.  The table names, per row, the entry points the row's
+route serves, in the order the test calls them, and -- from what the context reports about its routes -- the helper passes each call takes
+besides its main kernel (the passes a launcher could misplace one by one)."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import edge_signals as es
+
+PEAK_GROUP = 3
+# the order of the calls: the batch entry points, then the calls that consume what those just made
+BATCH = ("stft", "f16", "complex", "render", "bands", "peak_3")
+STAGE = ("render_mags", "magnitude_in", "render_bands", "checksum_add")
+ENTRIES = BATCH + ("istft",) + STAGE
+SYMBOL = {"stft": "sgx_stft_batch", "f16": "sgx_stft_batch_f16", "complex": "sgx_stft_batch_complex", "render": "sgx_render_batch",
+          "bands": "sgx_bands_batch", "peak_3": "sgx_bands_peak_batch", "istft": "sgx_istft_batch", "render_mags": "sgx_render_mags",
+          "magnitude_in": "sgx_magnitude_in", "render_bands": "sgx_render_bands", "checksum_add": "sgx_checksum_add"}
+# what a call reads that another call of the same run wrote: a wrong input makes a wrong output whatever the call itself does
+READS = {"istft": "complex", "render_mags": "stft", "magnitude_in": "stft", "render_bands": "bands", "checksum_add": "stft"}
+# entry points that wait on the host in their steady state, with the reason (include/sgx.h's conventions name them): none
+HOST_WAITS: dict = {}
+
+FRAMES = 23            # 8 peak columns at group 3, the last of two frames; more frames than one run of a persistent workgroup
+FRAMES_LONG = 5        # W >= 65536 (a frame of 0.5 .. 8 MiB of samples): two columns, the last of two frames
+LONG_W = 65536
+SEED_A, SEED_B = 0x5EED0A00, 0x5EED0B00
+
+
+def frames_of(r: es.Route) -> int:
+    return FRAMES_LONG if r.W >= LONG_W else FRAMES
+
+
+def istft_served(r: es.Route) -> bool:
+    """sgx_istft_supported: every length an in-LDS kernel serves (stft_istft.hip: istft_route)"""
+    return r.kernel != 11
+
+
+def peak_fused(r: es.Route) -> int:
+    """sgx_bands_peak_fused at the default 1024 rows: the 4096-point kernels, unless a mono stream's frames are paired"""
+    return int(r.kernel == 2 and not r.paired)
+
+
+def entries_served(r: es.Route) -> tuple:
+    return tuple(e for e in ENTRIES if e != "istft" or istft_served(r))
+
+
+@dataclass(frozen=True)
+class Case:
+    row: str
+    entry: str
+
+    @property
+    def route(self) -> es.Route:
+        return es.ROUTE[self.row]
+
+
+CASES = [Case(r.name, e) for r in es.ROUTES for e in entries_served(r)]
+
+
+def by_row() -> dict:
+    out: dict = {}
+    for c in CASES:
+        out.setdefault(c.row, []).append(c.entry)
+    return out
+
+
+# ---- the helper passes -------------------------------------------------------------------------------------------------------------------
+HELPERS = ("deinterleave", "k16_plane", "to_half", "workspace", "workspace_render", "workspace_magnitude_in", "workspace_peak",
+           "peak_combine", "ladder", "large_passes", "inverse")
+
+
+def family(r: es.Route) -> str:
+    """the transform family of the row's rows (sgx_api.hip: stft_route), from what ROUTES pins"""
+    if r.kernel == 9:   # the 4800-point kernel: one or two channels, not real-input mode; else the mixed-radix kernels
+        return "w4800" if r.channels <= 2 and not r.bits_set & es.R8 else "mixed"
+    if r.kernel == 4:
+        return "chirpz" if r.bits_set & es.R4 else "bluestein"
+    return {0: "generic", 2: "wg4096", 6: "mixed", 10: "w16384", 11: "large"}[r.kernel]
+
+
+def rows_helpers(r: es.Route) -> set:
+    """what a launch of the row's rows runs besides one kernel"""
+    out = set()
+    fam = family(r)
+    if fam == "wg4096" and r.channels > 2:
+        out.add("deinterleave")
+    if fam == "w16384" and r.channels == 1 and not r.paired:
+        out.add("k16_plane")
+    if fam in ("chirpz", "bluestein"):
+        out.add("ladder")
+    if fam == "large":
+        out.add("large_passes")
+    return out
+
+
+def helpers(r: es.Route, entry: str, render_fused: bool, bands_fused: bool) -> set:
+    """the helper passes of one call, given the two routes the context reports (render_path bit 0, sgx_bands_fused)"""
+    fam = family(r)
+    rows = rows_helpers(r)
+    if entry in ("stft", "complex"):
+        return rows
+    if entry == "f16":
+        return rows if fam in ("wg4096", "w4800", "mixed") else rows | {"workspace", "to_half"}
+    if entry == "render":
+        # (the fused pixels of a W 2400 context are the mixed-radix kernel's: one kernel whatever the rows' family)
+        return (rows if fam == "wg4096" else set()) if render_fused else rows | {"workspace", "workspace_render"}
+    if entry == "bands":
+        return rows if bands_fused else rows | {"workspace", "workspace_magnitude_in"}
+    if entry == "peak_3":
+        if peak_fused(r):
+            return rows | {"peak_combine"}
+        return helpers(r, "bands", render_fused, bands_fused) | {"workspace", "workspace_peak"}
+    if entry == "istft":
+        return {"inverse"}
+    return set()
+
+
+# ---- the stand-alone objects ---------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class ViewCase:
+    name: str
+    W: int
+    H: int
+    channels: int
+    viewport: int      # rows of the ring: fewer than the frames written, so that the copy wraps
+    frames: int        # rows per write; two writes bring the ring back to the same offset (a view is warmed: its first draw uploads the palette)
+    width: int
+    height: int
+
+
+VIEW_CASES = [ViewCase("view_k1r", 2048, 256, 1, 16, 24, 300, 37), ViewCase("view_w1024_lr", 1024, 100, 2, 10, 25, 257, 64)]
+
+
+@dataclass(frozen=True)
+class ImageCase:
+    name: str
+    W: int
+    H: int
+    channels: int
+    width: int         # fewer columns than the frames written: the ring laps itself and the scrolled read composes two parts
+
+
+IMAGE_CASES = [ImageCase("image_w1024_lr", 1024, 100, 2, 19)]
+
+
+@dataclass(frozen=True)
+class PixelCase:
+    name: str
+    body: str          # far_offsets.pixel_body: the kernel body the context must take
+    entry: str         # render_mags, magnitude_in
+    W: int
+    R: int
+    large: bool = False
+    n_lut: int = 256
+    n_ranges: int = 64
+    cols: int = 7
+
+
+# one context per kernel body of the stand-alone pixel stage (far_offsets.PIXEL_CASES at a handful of columns)
+PIXEL_CASES = [
+    PixelCase("two_pass_w64", "render_two_pass_kernel", "render_mags", 64, 126),
+    PixelCase("staged_w10290", "render_kernel<true>", "render_mags", 10290, 20578, large=True),
+    PixelCase("unstaged_w20481", "render_kernel<false>", "render_mags", 20481, 40960, large=True),
+    PixelCase("far_tables_w64", "render_far_tables_kernel<true>", "render_mags", 64, 126, n_lut=40706),
+    PixelCase("magnitude_in_w64", "magnitude_in_kernel<true>", "magnitude_in", 64, 126),
+    PixelCase("magnitude_in_w20481", "magnitude_in_kernel<false>", "magnitude_in", 20481, 1024, large=True, n_ranges=20480),
+]
+
+# rebinding a busy context: (name, engine keywords, the wrapper's method)
+REBIND_CASES = [
+    ("seam_bands", dict(window_samples=8192, hop_samples=16, channels=2), "bands_batch"),
+    ("seam_render", dict(window_samples=8192, hop_samples=16, channels=2), "render_batch"),
+    ("k16_mono_bands", dict(window_samples=8192, hop_samples=512, channels=1), "bands_batch"),
+]
