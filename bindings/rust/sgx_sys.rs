@@ -46,6 +46,8 @@ extern "C" {
     pub fn sgx_set_builtin_scheme(ctx: *mut SgxCtx, name: *const c_char, stereo: c_int) -> c_int;
     pub fn sgx_lookup_table(ctx: *mut SgxCtx, resolution: u32, h_out: *mut f32) -> c_int;
     pub fn sgx_sync(ctx: *mut SgxCtx) -> c_int;
+    pub fn sgx_set_cu_limit(ctx: *mut SgxCtx, n: u32) -> c_int;
+    pub fn sgx_cu_limit(ctx: *const SgxCtx) -> u32;
 }
 extern "C" {   // from libamdhip64, for staging buffers
     pub fn hipMalloc(p: *mut *mut c_void, bytes: usize) -> c_int;

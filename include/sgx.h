@@ -186,6 +186,12 @@ SGX_API size_t sgx_num_frames(const sgx_ctx *ctx, size_t n_samples);
 SGX_API int sgx_set_stream(sgx_ctx *ctx, void *stream);
 SGX_API int sgx_sync(sgx_ctx *ctx);
 
+/* The number of compute units the context sizes its persistent launches for. Default: the device's own count.
+ * n = 0 restores it; 1 .. the device's count is accepted; a larger n: SGX_ERR_INVALID_ARG.
+ * Takes effect for calls made afterwards; does not wait; results do not depend on it (tests/test_gpu_cu_counts.py). */
+SGX_API int sgx_set_cu_limit(sgx_ctx *ctx, uint32_t n);
+SGX_API uint32_t sgx_cu_limit(const sgx_ctx *ctx);   /* the count in force; 0 for a null context */
+
 /* ---- the transform: replaces AudioTransform::process / AudioStreamTransform::process ----- */
 
 /* Batched FastFourierTransform::process (fft.rs:43-99) driven by the hop loop

@@ -482,7 +482,7 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     {   // device limits the launchers need: read once, here
         int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) c->n_cu = v;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) c->n_cu = c->n_cu_device = v;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, c->device) == hipSuccess && v > 0) c->lds_optin = (size_t)v;
         else if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) == hipSuccess && v > 0) c->lds_optin = (size_t)v;
     }
@@ -634,6 +634,21 @@ int sgx_set_stream(sgx_ctx *c, void *stream)
     c->stream = next;
     return SGX_OK;
 }
+
+int sgx_set_cu_limit(sgx_ctx *c, uint32_t n)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (n > (uint32_t)c->n_cu_device) {
+        c->err = "sgx_set_cu_limit: more compute units than the device has";
+        return SGX_ERR_INVALID_ARG;
+    }
+    // Only grids and job splits read the count.  The one buffer sized by it, the 4096-point kernels' peak partials, is checked by grow() at
+    // every launch: a limit raised again regrows it.
+    c->n_cu = n ? (int)n : c->n_cu_device;
+    return SGX_OK;
+}
+
+uint32_t sgx_cu_limit(const sgx_ctx *c) { return c ? (uint32_t)c->n_cu : 0u; }
 
 int sgx_sync(sgx_ctx *c)
 {

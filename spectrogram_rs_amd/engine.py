@@ -107,6 +107,16 @@ class SpectrogramEngine:
     def sync(self):
         self._check(self._lib.sgx_sync(self._ctx))
 
+    def set_cu_limit(self, n: int):
+        """Size the persistent launches of later calls for n compute units (0: the device's own count; more than it has is refused).
+        Results do not depend on it: an application that shares the GPU with its renderer bounds the engine's footprint this way."""
+        self._check(self._lib.sgx_set_cu_limit(self._ctx, C.c_uint32(n)))
+
+    @property
+    def cu_limit(self) -> int:
+        """the compute-unit count in force"""
+        return int(self._lib.sgx_cu_limit(self._ctx))
+
     def _dev_f32(self, t):
         import torch
 
