@@ -12,6 +12,7 @@ pub struct SgxConfig {
     pub device: i32, pub flags: u32,
 }
 #[repr(C)] pub struct SgxCtx { _private: [u8; 0] }
+#[repr(C)] pub struct SgxFbank { _private: [u8; 0] }   // a filterbank's tables on the device (the header spells the handle `void *`)
 
 extern "C" {
     pub fn sgx_config_init(cfg: *mut SgxConfig) -> c_int;
@@ -40,6 +41,17 @@ extern "C" {
                                 group: usize, d_peak: *mut f32, n_out: *mut usize) -> c_int;   // peak-hold of the bands over groups of frames
     pub fn sgx_bands_peak_fused(ctx: *const SgxCtx) -> c_int;
     pub fn sgx_render_bands(ctx: *mut SgxCtx, d_bands: *const f32, n_columns: usize, d_rgba: *mut u8) -> c_int;   // color_for over band columns
+    // filterbanks: weighted sums of bin magnitudes or powers over sparse filters (mel, bark, third octaves ...)
+    pub fn sgx_fbank_create(ctx: *mut SgxCtx, n_filters: u32, h_first: *const u32, h_count: *const u32, h_weights: *const f32,
+                            power: u32, out_fbank: *mut *mut SgxFbank) -> c_int;
+    pub fn sgx_fbank_destroy(fbank: *mut SgxFbank);
+    pub fn sgx_fbank_filters(fbank: *const SgxFbank) -> u32;
+    pub fn sgx_fbank_batch(fbank: *mut SgxFbank, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                           d_out: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][n_filters][2]
+    pub fn sgx_fbank_mags(fbank: *mut SgxFbank, d_mags: *const f32, n_columns: usize, d_out: *mut f32) -> c_int;   // the stage alone
+    pub fn sgx_fbank_fused(fbank: *const SgxFbank) -> c_int;
+    pub fn sgx_mel_weights(sample_rate: f64, window_samples: u32, n_mels: u32, f_min: f64, f_max: f64, scale: u32, norm: u32,
+                           h_first: *mut u32, h_count: *mut u32, h_weights: *mut f32, n_weights: *mut usize) -> c_int;   // host only
     pub fn sgx_set_gradient(ctx: *mut SgxCtx, h_rgb: *const u8, n: u32, stereo: c_int) -> c_int;
     pub fn sgx_set_gradient_fn(ctx: *mut SgxCtx, eval: extern "C" fn(f64, *mut u8, *mut c_void), user: *mut c_void,
                                stereo: c_int) -> c_int;
@@ -61,4 +73,8 @@ pub const HIP_MEMCPY_DEVICE_TO_HOST: c_int = 2;
 pub const SGX_FLAG_PAIRED_FRAMES: u32 = 1024;   // opt-in: two frames per transform (half the work; tolerance against the pair's peak)
 pub const SGX_FLAG_COMPLEX_MONO: u32 = 512;     // A/B: the literal (s, s) transform per frame where a real-input kernel would run
 pub const SGX_FLAG_LARGE_TRANSFORM: u32 = 4096; // opt-in: lengths no in-LDS kernel serves, W up to 2^20, as a multi-pass transform through a device scratch
+pub const SGX_MEL_HTK: u32 = 0;                 // sgx_mel_weights: mel = 2595 log10(1 + f / 700)
+pub const SGX_MEL_SLANEY: u32 = 1;              // linear below 1 kHz, logarithmic above
+pub const SGX_MEL_NORM_NONE: u32 = 0;
+pub const SGX_MEL_NORM_SLANEY: u32 = 1;         // every triangle times 2 / (f_hi - f_lo)
 pub const SGX_LIVE_BANDS: c_int = 3;            // sgx_live_tick: [frames][R][2] f32, the rows of sgx_bands_batch

@@ -13,7 +13,8 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise, sgx_checksum_add) only enqueue;
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
  *     stream; no call waits for another context's stream (tests/test_gpu_streams.py).
@@ -299,6 +300,78 @@ SGX_API int sgx_bands_peak_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samp
                                  size_t group, float *d_peak, size_t *n_out);
 /* 1: one kernel from PCM to peak columns (plus at most one combine pass over partial columns); 0: the workspace route; < 0: error */
 SGX_API int sgx_bands_peak_fused(const sgx_ctx *ctx);
+/* ---- filterbanks: weighted sums of bin magnitudes or powers over overlapping filters ---------------------------------------------
+ * What a mel, bark or ERB front end, a third-octave analyser, a chroma vector or an A-weighted level is (the reference has none: every
+ * reduction there is magnitude_in, an unweighted mean).
+ *
+ * A filterbank is n_filters sparse rows over the M = W - 1 stored bins.  Element j of a row of sgx_stft_batch is bin k = j + 1 of the
+ * 2W-point transform.  Filter f is (first[f], count[f]) plus count[f] float weights, stored consecutively in filter order (CSR);
+ * first[f] + count[f] <= M.  Filters may overlap, repeat, come in any order and have count == 0; weights are any finite floats,
+ * negative ones included.  power is 1 (magnitude) or 2 (power).  Per frame, pair and side
+ *
+ *     out[f] = sum_{i < count[f]} w[f][i] * x[first[f] + i],    x[j] = m[j] (power 1) or m[j] * m[j] rounded to float (power 2)
+ *
+ * with m[j] exactly the float32 that sgx_stft_batch stores for that frame, side and bin.  The order of the sum is part of the definition:
+ *   1. 64 partial sums: a[l], l = 0 .. 63, takes the elements i = l, l + 64, l + 128, ... in ascending order as one chain of fused
+ *      multiply-adds from +0: a = fma(w[f][i], x[first[f] + i], a), one rounding per element;
+ *   2. a balanced binary tree over a[0 .. 63] by halving, float32 adds: for s = 32, 16, 8, 4, 2, 1 in turn a[l] = a[l] + a[l + s] for every
+ *      l < s; the sum is a[0].
+ * (A wave of 64 lanes per filter on the device: consecutive lanes read consecutive bins and weights, and the tree serves both sides at
+ * once; DESIGN.md says what was measured and what was not.)  count == 0 gives exactly +0.0f.  Every kernel that computes a bank runs this order,
+ * so the output is a pure function of the frame's row and the bank: bit-identical across routes, sub-ranges, chunk seams,
+ * compute-unit limits and streams (tests/test_gpu_fbank.py).  No logarithm, no dB: the output is about 1 KB per frame, and a log
+ * over it is the caller's.
+ *
+ * The handle is `sgx_fbank *`; the prototypes below spell it `void *` (C converts both ways without a cast; pass `(void **)&fb` to
+ * sgx_fbank_create) because the checker of the Rust binding maps the header's types by a fixed table (tests/test_rust_binding.py).
+ * A bank belongs to its context: destroy it before sgx_destroy(ctx) (a bank that outlives its context answers SGX_ERR_INVALID_ARG).
+ * Several banks may live on one context at once. */
+typedef struct sgx_fbank sgx_fbank;
+
+/* Validates the bank and uploads its tables.  SGX_ERR_INVALID_ARG for a null array, n_filters == 0 (or above 2^30),
+ * first + count > M, a power other than 1 or 2, a non-finite weight, or 2^31 weights and more.  Waits for nothing but its own uploads on
+ * the context's stream.  h_weights holds sum(count) floats. */
+SGX_API int sgx_fbank_create(sgx_ctx *ctx, uint32_t n_filters, const uint32_t *h_first, const uint32_t *h_count,
+                             const float *h_weights, uint32_t power, void **out_fbank);
+SGX_API void sgx_fbank_destroy(void *fbank);
+/* n_filters, or 0 for null */
+SGX_API uint32_t sgx_fbank_filters(const void *fbank);
+/* PCM to the bank's sums for every frame of the hop loop.
+ *   d_out [n_out][pairs][n_filters][2] float: (l, r) per filter.  A mono stream holds (v, v), as sgx_bands_batch does; with
+ *   SGX_FLAG_PAIRED_FRAMES it holds what the rows hold.
+ * first_frame / max_frames / *n_out as sgx_bands_batch: too few samples is *n_out = 0, not an error; a null buffer is
+ * SGX_ERR_INVALID_ARG.  Stream-ordered and asynchronous; nothing waits on the host.  Device memory beyond the caller's buffers is
+ * bounded whatever the number of frames (none on the fused route, the 192 MiB workspace of the two-kernel routes otherwise). */
+SGX_API int sgx_fbank_batch(void *fbank, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                            float *d_out, size_t *n_out);
+/* The stage alone, from rows already on the device (as sgx_render_mags is to sgx_render_batch):
+ *   d_mags [n_columns][M][2] -> d_out [n_columns][n_filters][2].  Every W the library accepts, every bank. */
+SGX_API int sgx_fbank_mags(void *fbank, const float *d_mags, size_t n_columns, float *d_out);
+/* 1: sgx_fbank_batch runs one kernel from PCM to sums for this bank on its context; 0: the workspace route (the rows of a chunk of
+ * frames by their own route, then the stage kernel); < 0: error.
+ * One kernel: W = 2048 with 1, 2 or 2k channels (the 4096-point kernels; any hop), without SGX_FLAG_NO_FUSED_RENDER,
+ * SGX_FLAG_PAIRED_FRAMES, SGX_FLAG_COMPLEX_MONO or SGX_FLAG_FORCE_GENERIC, for banks of at most 1024 filters and 16384 weights (a 128-
+ * or 256-filter mel bank has about 4000).  Every other window, flag and bank: the workspace route.  Same bits either way. */
+SGX_API int sgx_fbank_fused(const void *fbank);
+
+/* The triangular mel bank as sgx_fbank_create takes it.  Host only: no context, no device.
+ * Over the TRUE bin frequencies f_k = k * sample_rate / (2W), k = 1 .. W - 1 (stored element j = k - 1) -- deliberately not the axis of
+ * the reference's index_of (quirk Q2), which a caller comparing with librosa / torchaudio / HTK would not expect.
+ *   n_mels + 2 points equally spaced in mel between f_min and f_max; filter m spans (f_lo, f_c, f_hi) = points m, m + 1, m + 2:
+ *   w = max(0, min((f - f_lo) / (f_c - f_lo), (f_hi - f) / (f_hi - f_c))), times 2 / (f_hi - f_lo) with SGX_MEL_NORM_SLANEY;
+ *   computed in double, rounded once to float.  A filter's support is its bins with w > 0 (none: count = 0, first = 0).
+ *   scale: SGX_MEL_HTK, mel = 2595 log10(1 + f / 700); SGX_MEL_SLANEY, linear below 1 kHz at 200 / 3 Hz per mel, logarithmic above with
+ *   step ln(6.4) / 27.
+ * h_first [n_mels], h_count [n_mels], h_weights [*n_weights]; with all three null only *n_weights is returned, for sizing.
+ * SGX_ERR_INVALID_ARG: n_mels == 0, f_min < 0, f_max <= f_min, f_max > sample_rate / 2, window_samples < 2, an unknown scale or norm,
+ * a null n_weights, or only some of the arrays null. */
+#define SGX_MEL_HTK 0u
+#define SGX_MEL_SLANEY 1u
+#define SGX_MEL_NORM_NONE 0u
+#define SGX_MEL_NORM_SLANEY 1u
+SGX_API int sgx_mel_weights(double sample_rate, uint32_t window_samples, uint32_t n_mels, double f_min, double f_max, uint32_t scale,
+                            uint32_t norm, uint32_t *h_first, uint32_t *h_count, float *h_weights, size_t *n_weights);
+
 /* ColorScheme::color_for (colorscheme.rs:55-71) + put_pixel's row order over columns of bands: d_bands [n_columns][R][2] (py = 0 lowest)
  * -> d_rgba [n_columns][R][4], image order (row 0 = highest frequency), the context's current colour scheme (mono or diverging). */
 SGX_API int sgx_render_bands(sgx_ctx *ctx, const float *d_bands, size_t n_columns, uint8_t *d_rgba);

@@ -367,6 +367,66 @@ private:
     std::uint32_t width_ = 0, rows_ = 0;
 };
 
+// A filterbank on the device (sgx_fbank_*): weighted sums of the bin magnitudes (power 1) or powers (power 2) over sparse filters --
+// filter f weighs bins first[f] .. first[f] + count[f] - 1 with the next count[f] weights.  mel(): the triangular mel bank of
+// sgx_mel_weights over the transform's own bins.  Destroyed before its transform.
+class FilterBank {
+public:
+    FilterBank(FastFourierTransform &transform, const std::vector<std::uint32_t> &first, const std::vector<std::uint32_t> &count,
+               const std::vector<float> &weights, std::uint32_t power = 2)
+        : transform_(transform)
+    {
+        if (first.size() != count.size()) throw Error(SGX_ERR_INVALID_ARG, "FilterBank: first and count hold one entry per filter");
+        const float none = 0.0f;
+        void *h = nullptr;
+        const int rc = sgx_fbank_create(transform.ctx(), (std::uint32_t)first.size(), first.data(), count.data(),
+                                        weights.empty() ? &none : weights.data(), power, &h);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform.ctx()));
+        bank_ = static_cast<sgx_fbank *>(h);
+    }
+    static FilterBank mel(FastFourierTransform &transform, double sample_rate, std::uint32_t window_samples, std::uint32_t n_mels = 128,
+                          double f_min = 0.0, double f_max = -1.0, std::uint32_t scale = SGX_MEL_HTK, std::uint32_t norm = SGX_MEL_NORM_NONE,
+                          std::uint32_t power = 2)
+    {
+        if (f_max < 0.0) f_max = sample_rate / 2.0;
+        std::size_t n = 0;
+        int rc = sgx_mel_weights(sample_rate, window_samples, n_mels, f_min, f_max, scale, norm, nullptr, nullptr, nullptr, &n);
+        if (rc != SGX_OK) throw Error(rc, "sgx_mel_weights: invalid argument");
+        std::vector<std::uint32_t> first(n_mels), count(n_mels);
+        std::vector<float> weights(n ? n : 1);
+        rc = sgx_mel_weights(sample_rate, window_samples, n_mels, f_min, f_max, scale, norm, first.data(), count.data(), weights.data(), &n);
+        if (rc != SGX_OK) throw Error(rc, "sgx_mel_weights: invalid argument");
+        weights.resize(n);
+        return FilterBank(transform, first, count, weights, power);
+    }
+    FilterBank(const FilterBank &) = delete;
+    FilterBank &operator=(const FilterBank &) = delete;
+    FilterBank(FilterBank &&o) noexcept : transform_(o.transform_), bank_(o.bank_) { o.bank_ = nullptr; }
+    ~FilterBank() { sgx_fbank_destroy(bank_); }
+
+    std::uint32_t filters() const { return sgx_fbank_filters(bank_); }
+    bool fused() const { return sgx_fbank_fused(bank_) == 1; }
+    // device to device: PCM -> [frames][pairs][filters][2]; returns the frames written
+    std::size_t batch(const float *d_pcm, std::size_t n_samples, float *d_out, std::size_t first_frame = 0, std::size_t max_frames = (std::size_t)-1)
+    {
+        std::size_t got = 0;
+        const int rc = sgx_fbank_batch(bank_, d_pcm, n_samples, first_frame, max_frames, d_out, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
+        return got;
+    }
+    // the stage alone: [columns][M][2] rows -> [columns][filters][2]
+    void apply(const float *d_mags, std::size_t n_columns, float *d_out)
+    {
+        const int rc = sgx_fbank_mags(bank_, d_mags, n_columns, d_out);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
+    }
+    sgx_fbank *raw() const { return bank_; }
+
+private:
+    FastFourierTransform &transform_;
+    sgx_fbank *bank_ = nullptr;
+};
+
 // audio_transform.rs:14-43; the three members are public and assignable, as in the reference
 template <typename T>
 struct AudioStreamTransform {

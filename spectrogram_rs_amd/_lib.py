@@ -29,6 +29,8 @@ FLAG_PAIRED_FRAMES = 1024
 FLAG_LARGE_TRANSFORM = 4096
 LIVE_MAGS, LIVE_MAGS_F16, LIVE_RGBA, LIVE_BANDS = 0, 1, 2, 3
 LIVE_REFERENCE_SKIP = 1
+MEL_HTK, MEL_SLANEY = 0, 1
+MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
 
 
 class SgxError(RuntimeError):
@@ -106,6 +108,14 @@ SIGNATURES = [
     ("sgx_bands_peak_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_bands_peak_fused", C.c_int, [_ctx]),
     ("sgx_render_bands", C.c_int, [_ctx, _vp, _sz, _vp]),
+    ("sgx_fbank_create", C.c_int, [_ctx, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    ("sgx_fbank_destroy", None, [_vp]),
+    ("sgx_fbank_filters", C.c_uint32, [_vp]),
+    ("sgx_fbank_batch", C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_fbank_mags", C.c_int, [_vp, _vp, _sz, _vp]),
+    ("sgx_fbank_fused", C.c_int, [_vp]),
+    ("sgx_mel_weights", C.c_int, [C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
+                                  C.POINTER(_sz)]),
     ("sgx_spectrum_levels", C.c_int, [_ctx, _vp, C.c_uint32, _vp]),
     ("sgx_live_create", C.c_int, [_ctx, _sz, C.c_uint32, C.POINTER(_vp)]),
     ("sgx_live_destroy", None, [_vp]),

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <new>
 
+#include "sgx_fbank.hpp"
 #include "sgx_gradients.inc"
 #include "sgx_internal.hpp"
 
@@ -232,7 +233,8 @@ struct Route { Family family; bool fused, real_input; };
 // the CONTEXT's channel count (wg4096_can_fuse_*, mixed_can_fuse_* read c->C: the tables they test were built for it).  Only the batch entry
 // points ask for a column, and their channel count is the context's, so one `channels` serves both here; the queries (sgx_query,
 // sgx_bands_fused, sgx_bands_peak_fused) pass c->C.
-Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind)
+// `bank` (Out::kFbank): the filterbank of the call; its size decides with the context.
+Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank *bank = nullptr)
 {
     const bool mixed = c->stft_kernel == sgx::kKernelMixed || c->stft_kernel == sgx::kKernelW4800;
     // The W 2400 rows of one or two channels come from the 4800-point kernel, unless real-input mode takes the stream (a mono stream, every
@@ -279,6 +281,9 @@ Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind)
         break;
     case Out::kPeak:      // in one kernel where sgx_bands_batch runs the 4096-point kernels and the frames are not paired
         fused = stft_route(c, channels, Out::kBands).fused && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_peak(c, c->d_fast_wg);
+        break;
+    case Out::kFbank:     // in one kernel at W 2048 where every frame is its own transform and the bank is within the stated size
+        fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_fbank(c, bank);
         break;
     }
     rows.fused = fused;
@@ -559,6 +564,7 @@ void sgx_destroy(sgx_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     sgx::detach_views(c);
+    sgx::detach_fbanks(c);
     sgx::detach_images(c);   // views that outlive their context keep their own buffers and answer SGX_ERR_INVALID_ARG from now on
     sgx::wg4096_destroy(c->d_fast_wg);
     c->d_fast_wg = nullptr;
@@ -790,6 +796,118 @@ int sgx_bands_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fir
             return run_bands(c, "sgx_bands_batch", r, d_pcm, first_frame + done, m, total, d_bands + done * (size_t)c->pairs * c->R * 2);
         });
     if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+// ---- filterbanks: weighted sums of bin magnitudes or powers over sparse filters (sgx_fbank.hpp) ----------------------------------------
+
+int sgx_mel_weights(double sample_rate, uint32_t window_samples, uint32_t n_mels, double f_min, double f_max, uint32_t scale, uint32_t norm,
+                    uint32_t *h_first, uint32_t *h_count, float *h_weights, size_t *n_weights)
+{
+    return sgx::fbank::mel_weights(sample_rate, window_samples, n_mels, f_min, f_max, scale, norm, h_first, h_count, h_weights, n_weights);
+}
+
+int sgx_fbank_create(sgx_ctx *c, uint32_t n_filters, const uint32_t *h_first, const uint32_t *h_count, const float *h_weights, uint32_t power,
+                     void **out)
+{
+    if (out) *out = nullptr;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (!out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_fbank_create: null argument");
+    std::vector<sgx::fbank::Filter> table;
+    size_t n_weights = 0;
+    const char *why = "";
+    if (sgx::fbank::validate(c->M, n_filters, h_first, h_count, h_weights, power, &table, &n_weights, &why) != SGX_OK)
+        return fail(c, SGX_ERR_INVALID_ARG, std::string("sgx_fbank_create: ") + why);
+    sgx_fbank *fb = new (std::nothrow) sgx_fbank();
+    if (!fb) return fail(c, SGX_ERR_NOMEM, "sgx_fbank_create: out of host memory");
+    fb->ctx = c;
+    fb->n_filters = n_filters;
+    fb->power = power;
+    fb->n_weights = n_weights;
+    // The uploads go onto the context's stream, from copies the bank keeps: the calls that read the tables follow on the same stream, and
+    // nothing is waited for.
+    fb->h_filters = std::move(table);
+    fb->h_weights.assign(h_weights, h_weights + n_weights);
+    if (fb->h_weights.empty()) fb->h_weights.push_back(0.0f);
+    hipError_t e = hipSetDevice(c->device);
+    const size_t table_bytes = fb->h_filters.size() * sizeof(fb->h_filters[0]), weight_bytes = fb->h_weights.size() * sizeof(float);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&fb->d_filters), table_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&fb->d_weights), weight_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(fb->d_filters, fb->h_filters.data(), table_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fb->d_weights, fb->h_weights.data(), weight_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        if (fb->d_filters) (void)hipFree(fb->d_filters);
+        if (fb->d_weights) (void)hipFree(fb->d_weights);
+        delete fb;
+        return fail_hip(c, e, "sgx_fbank_create: table upload");
+    }
+    c->fbanks.push_back(fb);
+    *out = fb;
+    return SGX_OK;
+}
+
+void sgx_fbank_destroy(void *bank)
+{
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (!fb) return;
+    if (sgx_ctx *c = fb->ctx) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);   // a call that reads the tables may still be in flight
+        for (size_t i = 0; i < c->fbanks.size(); ++i)
+            if (c->fbanks[i] == fb) { c->fbanks.erase(c->fbanks.begin() + (long)i); break; }
+    }
+    if (fb->d_filters) (void)hipFree(fb->d_filters);
+    if (fb->d_weights) (void)hipFree(fb->d_weights);
+    delete fb;
+}
+
+uint32_t sgx_fbank_filters(const void *bank) { return bank ? static_cast<const sgx_fbank *>(bank)->n_filters : 0u; }
+
+int sgx_fbank_fused(const void *bank)
+{
+    const sgx_fbank *fb = static_cast<const sgx_fbank *>(bank);
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    return stft_route(fb->ctx, fb->ctx->C, Out::kFbank, fb).fused ? 1 : 0;
+}
+
+int sgx_fbank_mags(void *bank, const float *d_mags, size_t n_columns, float *d_out)
+{
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    sgx_ctx *c = fb->ctx;
+    if (n_columns == 0) return SGX_OK;
+    if (!d_mags || !d_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_fbank_mags: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = sgx::launch_fbank_stage(c, fb, d_mags, n_columns, d_out);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_mags: kernel launch");
+    return SGX_OK;
+}
+
+int sgx_fbank_batch(void *bank, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, float *d_out, size_t *n_out)
+{
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (n_out) *n_out = 0;
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    sgx_ctx *c = fb->ctx;
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_fbank_batch", n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    const Route r = stft_route(c, c->C, Out::kFbank, fb);
+    if (r.fused) {
+        // one kernel from PCM to the bank's sums: the magnitudes stay in LDS, 8 B per filter leave the kernel
+        const hipError_t e = launch_family(c, r.family, StftCall{d_pcm, c->C, c->pairs, first_frame, n, total, d_out, Out::kFbank, 0, fb});
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_batch: fused launch");
+    } else {
+        // two kernels: the rows of a chunk of frames in the bounded workspace, by the rows' own route, then the stage kernel over them
+        rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+            hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
+            if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_batch: stft launch");
+            e = sgx::launch_fbank_stage(c, fb, c->d_ws_mags, m * c->pairs, d_out + done * (size_t)c->pairs * fb->n_filters * 2);
+            return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_fbank_batch: filter launch");
+        });
+        if (rc != SGX_OK) return rc;
+    }
     if (n_out) *n_out = n;
     return SGX_OK;
 }

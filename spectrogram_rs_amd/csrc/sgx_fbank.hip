@@ -1,0 +1,72 @@
+// sgx_fbank.hip -- the filterbank stage on rows in device memory: [columns][M][2] magnitudes -> [columns][n_filters][2] weighted sums
+// (include/sgx.h: sgx_fbank_mags, and the second kernel of sgx_fbank_batch's workspace route).  The filter pass itself is
+// sgx_fbank.hpp's, shared with the fused modes of the 4096-point kernels.
+#include "sgx_fbank.hpp"
+
+namespace sgx {
+
+struct FbankStageParams {
+    const float *mags;             // [columns][M][2]
+    const fbank::Filter *filters;
+    const float *weights;
+    float *out;                    // [columns][n_filters][2]
+    uint32_t M, n_filters, square;
+};
+
+// One workgroup per column.  STAGED: the column goes through LDS once (overlapping filters read a bin several times); a column that no
+// LDS holds is read where it lies, as magnitude_in_kernel does.
+template <bool STAGED>
+__global__ void __launch_bounds__(256) fbank_stage_kernel(FbankStageParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float2 *stage = reinterpret_cast<float2 *>(smem_raw);
+    const uint32_t tid = threadIdx.x;
+    const size_t col = blockIdx.x;
+    const float2 *src = reinterpret_cast<const float2 *>(p.mags) + col * p.M;
+    if (STAGED) {
+        for (uint32_t i = tid; i < p.M; i += 256u) stage[i] = src[i];
+        __syncthreads();
+    }
+    float2 *dst = reinterpret_cast<float2 *>(p.out) + col * p.n_filters;
+    fbank::filter_pass<false>(STAGED ? stage : src, p.filters, p.weights, p.n_filters, p.square != 0, dst, dst, true, false, tid, 4u);
+}
+
+hipError_t launch_fbank_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_mags, size_t n_columns, float *d_out)
+{
+    if (n_columns == 0) return hipSuccess;
+    FbankStageParams p;
+    p.mags = d_mags;
+    p.filters = fb->d_filters;
+    p.weights = fb->d_weights;
+    p.out = d_out;
+    p.M = c->M;
+    p.n_filters = fb->n_filters;
+    p.square = fb->power == 2 ? 1u : 0u;
+    const size_t lds_cap = c->lds_optin < (size_t)160 * 1024 ? c->lds_optin : (size_t)160 * 1024;
+    const bool staged = (size_t)c->M * sizeof(float2) <= lds_cap;
+    const size_t lds = staged ? (size_t)c->M * sizeof(float2) : 0;
+    const auto kernel = staged ? fbank_stage_kernel<true> : fbank_stage_kernel<false>;
+    if (lds > 64 * 1024) {   // per launch: the attribute is per device, and a process may hold contexts on several
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const size_t max_chunk = 1u << 30;
+    for (size_t done = 0; done < n_columns; done += max_chunk) {
+        const size_t chunk = n_columns - done < max_chunk ? n_columns - done : max_chunk;
+        FbankStageParams q = p;
+        q.mags = d_mags + done * (size_t)c->M * 2;
+        q.out = d_out + done * (size_t)fb->n_filters * 2;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+void detach_fbanks(sgx_ctx *c)
+{
+    for (sgx_fbank *fb : c->fbanks) fb->ctx = nullptr;
+    c->fbanks.clear();
+}
+
+}  // namespace sgx

@@ -1,0 +1,147 @@
+// sgx_fbank.hpp -- the filter pass of the filterbank calls (include/sgx.h: sgx_fbank_batch, sgx_fbank_mags): one body for the stage kernel
+// (sgx_fbank.hip) and for the fused modes of the two 4096-point kernels (stft4096_wg.hip, stft4096_real.hip), so that a bank's output
+// is the same bits on every route.
+//
+// A wave per filter.  Lane l takes the filter's elements i = l, l + 64, l + 128, ... in ascending order into one fused-multiply-add
+// chain from +0; the 64 partial sums then meet in a halving tree (a[l] + a[l + 32], then + 16, 8, 4, 2, 1).  That order is the
+// definition (include/sgx.h) -- lanes read consecutive bins of the column (conflict-free in LDS, coalesced in memory) and consecutive
+// weights; the tree serves both components of the column at once (wave_tree2).
+#pragma once
+
+#include "fbank_host.hpp"
+#include "sgx_internal.hpp"
+
+// A bank: its tables on the device.  It belongs to its context (sgx_destroy detaches the banks still alive: their calls then answer
+// SGX_ERR_INVALID_ARG).
+struct sgx_fbank {
+    sgx_ctx *ctx = nullptr;
+    uint32_t n_filters = 0, power = 1;
+    size_t n_weights = 0;
+    sgx::fbank::Filter *d_filters = nullptr;   // [n_filters]
+    float *d_weights = nullptr;                // [n_weights] (one word where the bank has none)
+    std::vector<sgx::fbank::Filter> h_filters;   // what the asynchronous uploads read: the caller's arrays are the caller's again when
+    std::vector<float> h_weights;                // sgx_fbank_create returns
+};
+
+namespace sgx {
+
+hipError_t launch_fbank_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_mags, size_t n_columns, float *d_out);   // sgx_fbank.hip
+bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb);   // stft4096_wg.hip
+void detach_fbanks(sgx_ctx *c);   // sgx_fbank.hip
+
+#ifdef __HIPCC__
+namespace fbank {
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true)); }
+
+// The sums of the wave's 64 values of x and of y, each by the halving tree of the definition: for s = 32, 16, 8, 4, 2, 1 lane l < s takes
+// a[l] + a[l + s]; the sum is a[0].  One chain for both: the first level is a swap of register halves between x and y (gfx950's
+// v_permlane32_swap) and one add, after which lanes 0 .. 31 hold x's 32 sums and lanes 32 .. 63 y's; the level of 16 swaps rows of 16
+// lanes, the last four are DPP adds inside a row.  Both partners of a pair compute the same sum (x + y and y + x are the same bits), so
+// every lane of a half ends with the half's total.  All 64 lanes must be active.
+typedef unsigned int fbank_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void wave_tree2(float ax, float ay, float &sx, float &sy)
+{
+    const fbank_u32x2 h = __builtin_amdgcn_permlane32_swap(__float_as_uint(ax), __float_as_uint(ay), false, false);   // (x lo, y lo), (x hi, y hi)
+    float v = __uint_as_float(h.x) + __uint_as_float(h.y);                                                            // s = 32
+    const fbank_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);     // rows (0, 0, 2, 2), (1, 1, 3, 3)
+    v = __uint_as_float(r.x) + __uint_as_float(r.y);                                                                  // s = 16
+    v = v + dpp_f32<0x128>(v);   // row_ror:8        s = 8
+    v = v + dpp_f32<0x124>(v);   // row_ror:4        s = 4 (lanes l and l + 8 hold the same value by now)
+    v = v + dpp_f32<0x4E>(v);    // quad_perm [2, 3, 0, 1]   s = 2
+    v = v + dpp_f32<0xB1>(v);    // quad_perm [1, 0, 3, 2]   s = 1
+    sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+}
+
+// Every filter f = wave, wave + n_waves, ... of a 64 n_waves-thread workgroup over one column: col[j] = the (x, y) pair of stored bin j
+// (LDS or memory).  Both components are filtered.  DUP false: dst_a[f] = (out_x, out_y).  DUP true (two mono frames in one column):
+// dst_a[f] = (out_x, out_x) where have_a, dst_b[f] = (out_y, out_y) where have_b.  All lanes of the wave must be active.
+// A wave takes its filters eight at a time: the eight table entries are scalar loads (the tables are never written while a kernel
+// reads them: constant address space), the eight first chunks of weights and of the column are requested side by side, and only then
+// does the arithmetic start -- one memory latency per eight filters instead of two per filter (a mel filter is a few dozen bins: the
+// pass is latency, not arithmetic).  Results wait in lane k % 64 for the wave's k-th filter and leave 64 at a time.
+#ifndef SGX_FBANK_BATCH
+#define SGX_FBANK_BATCH 4   // filters a wave takes per trip (A/B)
+#endif
+typedef unsigned int fbank_u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) fbank_u32x4 *const_u4_ptr;
+template <bool DUP>
+__device__ __forceinline__ void filter_pass(const float2 *col, const Filter *filters, const float *weights, uint32_t n_filters, bool square,
+                                            float2 *dst_a, float2 *dst_b, bool have_a, bool have_b, uint32_t tid, uint32_t n_waves)
+{
+    constexpr uint32_t G = SGX_FBANK_BATCH;
+    static_assert(64 % G == 0, "a batch of results never straddles two groups of filters");
+    asm volatile("" : "+v"(tid));   // (opaque: inside a persistent kernel's loop over transforms the pass's lane offsets are not to be hoisted out of that loop -- they spill there)
+    const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t n_mine = n_filters > wave ? (n_filters - wave + n_waves - 1u) / n_waves : 0u;   // this wave's filters: wave + k n_waves, k < n_mine
+    const const_u4_ptr table = (const_u4_ptr)(unsigned long long)filters;
+    float kx = 0.0f, ky = 0.0f;
+    for (uint32_t k0 = 0; k0 < n_mine; k0 += G) {
+        uint32_t first[G], count[G], offset[G];
+        float w[G];
+        float2 v[G];
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            const bool valid = k0 + g < n_mine;
+            const fbank_u32x4 q = table[wave + (size_t)(valid ? k0 + g : k0) * n_waves];
+            first[g] = q.x;
+            count[g] = valid ? q.y : 0u;
+            offset[g] = q.z;
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            w[g] = 0.0f;
+            v[g] = make_float2(0.0f, 0.0f);
+            if (lane < count[g]) {
+                w[g] = weights[(size_t)offset[g] + lane];
+                v[g] = col[first[g] + lane];
+            }
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            float ax = 0.0f, ay = 0.0f;
+            if (lane < count[g]) {
+                float2 x = v[g];
+                if (square) {
+                    x.x = x.x * x.x;
+                    x.y = x.y * x.y;
+                }
+                ax = fmaf(w[g], x.x, ax);
+                ay = fmaf(w[g], x.y, ay);
+                for (uint32_t i = lane + 64u; i < count[g]; i += 64u) {   // filters of more than 64 bins: the lane's chain goes on
+                    const float wi = weights[(size_t)offset[g] + i];
+                    float2 xi = col[first[g] + i];
+                    if (square) {
+                        xi.x = xi.x * xi.x;
+                        xi.y = xi.y * xi.y;
+                    }
+                    ax = fmaf(wi, xi.x, ax);
+                    ay = fmaf(wi, xi.y, ay);
+                }
+            }
+            float sx, sy;
+            wave_tree2(ax, ay, sx, sy);
+            if (lane == ((k0 + g) & 63u)) { kx = sx; ky = sy; }
+        }
+        const uint32_t k_end = k0 + G < n_mine ? k0 + G : n_mine;
+        if ((k_end & 63u) == 0u || k_end == n_mine) {   // (wave-uniform) a full wave of results, or the last ones
+            const uint32_t k = ((k_end - 1u) & ~63u) + lane;   // this lane's filter of the wave
+            if (k < k_end) {
+                const size_t f = wave + (size_t)k * n_waves;
+                if (DUP) {
+                    if (have_a) dst_a[f] = make_float2(kx, kx);
+                    if (have_b) dst_b[f] = make_float2(ky, ky);
+                } else {
+                    dst_a[f] = make_float2(kx, ky);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace fbank
+#endif
+
+}  // namespace sgx

@@ -160,6 +160,7 @@ struct sgx_ctx {
     // objects that hold a pointer into this context (sgx_view): sgx_destroy detaches them, their calls then fail cleanly
     std::vector<struct sgx_view *> views;
     std::vector<struct sgx_image *> images;   // sgx_image.hip: the image rings created on this context
+    std::vector<struct sgx_fbank *> fbanks;   // sgx_fbank.hpp: the filterbanks created on this context
 
     std::string err;
 };
@@ -169,10 +170,12 @@ namespace sgx {
 // ---- one transform call, as every family's launcher takes it --------------------------------------------------------------
 // What the call writes: magnitude pairs [F][pairs][M][2] floats, the same as half pairs (4 B per bin), the complex rows of
 // sgx_stft_batch_complex [F][pairs][M][2][2] floats, or the fused column: RGBA pixels [F][pairs][R][4] bytes, the rows' (l, r) means as
-// float2 [F][pairs][R] (sgx_bands_batch), or those held as a maximum over groups of frames, float2 [ceil(F / group)][pairs][R].
-enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak };
+// float2 [F][pairs][R] (sgx_bands_batch), or those held as a maximum over groups of frames, float2 [ceil(F / group)][pairs][R]; or the
+// weighted sums of a filterbank over the magnitudes, float2 [F][pairs][n_filters] (sgx_fbank_batch).
+enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak, kFbank };
 // `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index).  channels and pairs are the CALL's, not the
-// context's: sgx_process_one runs a two-channel frame (2, 1) on a context of any channel count.  peak_group (kPeak): 1 .. n.
+// context's: sgx_process_one runs a two-channel frame (2, 1) on a context of any channel count.  peak_group (kPeak): 1 .. n.  bank (kFbank):
+// the filterbank whose sums the call writes.
 struct StftCall {
     const float *pcm;
     uint32_t channels, pairs;
@@ -180,11 +183,12 @@ struct StftCall {
     void *out;
     Out kind;
     size_t peak_group;
+    const struct sgx_fbank *bank = nullptr;
 };
 // Each launcher takes its tables from the context, returns hipSuccess or the launch error, and hipErrorInvalidValue for an Out (or a
 // channel count) its family has no kernel for.
 hipError_t launch_generic(const sgx_ctx *c, const StftCall &call);     // sgx_kernels.hip: kMags, kComplex
-hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call);      // stft4096_wg.hip (and stft4096_real.hip): every Out
+hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call);      // stft4096_wg.hip (and stft4096_real.hip): every Out (kFbank: where wg4096_can_fuse_fbank)
 hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call);      // stft16384_w.hip: kMags, kComplex
 hipError_t launch_w4800(const sgx_ctx *c, const StftCall &call);       // stft4800_wg.hip: kMags, kMagsF16, kComplex of one or two channels
 hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call);       // stft_mixed.hip: every Out but kPeak

@@ -106,6 +106,7 @@ __device__ __forceinline__ void fft8_half_zero(const float (&zr)[4], const float
 constexpr int kRowsF32 = 0, kRowsF16 = 1, kPixels = 2;   // what a launch writes: float rows, half-pair rows, RGBA columns (fused pixel path)
 constexpr int kBands = 3;   // the fused column's (l, r) row means as float2, no colour (sgx_bands_batch; PIX wg::kPixBandsCubic / kPixBandsCosine)
 constexpr int kPeak = 5;    // kBands held as a running maximum over groups of frames (sgx_bands_peak_batch; PIX wg::kPixPeakCubic / kPixPeakCosine)
+constexpr int kFbank = 6;   // a filterbank over the pair's columns (sgx_fbank_batch; PIX wg::kPixFbank): the column in LDS, one filter pass (sgx_fbank.hpp)
 constexpr int kRowsC64 = 4;   // complex rows (sgx_stft_batch_complex): (S, S) per bin, 16 bytes, every bin pair stored as soon as it is untangled
 
 // PIX (kPixels only): the pixel code of the instantiation, wg::kPixCubic / kPixCosine / kPixGeneric (stft4096_wg.hpp)
@@ -176,7 +177,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     uint2 *pal = reinterpret_cast<uint2 *>(tw2 + 256);          // kPixels only: [256] {threshold, RGBA} (wg::pixel_for)
     constexpr bool F16 = MODE == kRowsF16;
     constexpr bool C64 = MODE == kRowsC64;
-    constexpr bool FUSED = MODE == kPixels || MODE == kBands || MODE == kPeak;  // the column goes through LDS to the pixel passes
+    constexpr bool FUSED = MODE == kPixels || MODE == kBands || MODE == kPeak || MODE == kFbank;  // the column goes through LDS to the pixel passes (kFbank: to the filter pass)
 
     const int tid = threadIdx.x;
     const int t_p1 = TR ? (tid >> 4) + 16 * (tid & 15) : tid;     // pass-1 column of this thread
@@ -188,7 +189,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     const float4 *rd4_2 = reinterpret_cast<const float4 *>(plane + 280 * ((tid & 127) >> 3) + 68 * ((8 * (tid >> 7) + (tid & 7)) >> 2) + 16 * (tid & 3));
     tw2[tid] = p.tw2[tid];
     uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // FUSED: the table words of this thread's rows tid + 256 i
-    if (FUSED) {
+    if (FUSED && MODE != kFbank) {
         if (MODE == kPixels) pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -486,7 +487,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             // the sample pass's table words (nine per thread, the same in every iteration but eighteen registers nobody has to spare across
             // the transform) are requested as the column writes free m1 / m2, one word behind each pair of writes: their L1 / L2 latency
             // falls on the rest of the writes and on the barrier instead of on the head of the pass
-            constexpr bool kEarlyWords = SGX_SAMPLE_EARLY && PIX != wg::kPixGeneric;   // (the generic instantiation -- interpolator and LUT walk at run time -- has no register left: one spill)
+            constexpr bool kEarlyWords = SGX_SAMPLE_EARLY && PIX != wg::kPixGeneric && MODE != kFbank;   // (the generic instantiation -- interpolator and LUT walk at run time -- has no register left: one spill)
             wg::SampleWords sw;
             const __amdgpu_buffer_rsrc_t rt_words = wg::pcm_rsrc(reinterpret_cast<const float *>(p.samples));
             int tid_w = tid;
@@ -511,6 +512,16 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             SGX_STAMP(14)   // (pixels) column writes
             lds_barrier();
             SGX_STAMP(15)   // (pixels) barrier 7
+            if constexpr (MODE == kFbank) {
+                // one filter pass over the pair's column (frame A in .x, frame B in .y), a wave per filter: element j of a row is bin j + 1
+                float2 *sums = reinterpret_cast<float2 *>(p.rgba);
+                __builtin_amdgcn_s_setprio(3);
+                fbank::filter_pass<true>(mpair + 1, reinterpret_cast<const fbank::Filter *>(p.rows), reinterpret_cast<const float *>(p.samples), p.R,
+                                         p.interp == 2u, sums + la * (size_t)p.R, sums + lb * (size_t)p.R, true, have_b, (uint32_t)tid, 4u);
+                // the next iteration's load behind the pass, straight into L (dead since the slide): requested in front of it, it is two
+                // more registers alive through the pass and two spills
+                if (SLIDE) L = column(columns_from(128 * (fa + 2) + 1152), 0);
+            } else {
             if (kEarlyWords) wg::sample_pass_with<PIX>(p, mpair, vbuf, tid, sw);
             else wg::sample_pass<PIX>(p, mpair, vbuf, tid);
             // the fused pixel path requests the next iteration's load HERE, straight into L (dead since the slide): requested in front
@@ -538,6 +549,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             } else {
                 uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
                 wg::row_pass<true, PIX>(p, row_words, vbuf, rgba + la * (size_t)p.R, rgba + lb * (size_t)p.R, true, have_b, pal, tid);
+            }
             }
         }
         if (SLIDE && !FUSED) {
@@ -659,6 +671,8 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
         if (hold_peak) {
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCubic, S_>), grid, block, lds_rows, c->stream, p);
+        } else if (kind == Out::kFbank) {   // (no palette either)
+            hipLaunchKernelGGL((stft4096_real_kernel<kFbank, kPixFbank, S_>), grid, block, lds_rows, c->stream, p);
         } else if (kind == Out::kBands) {   // (no palette: the row-image LDS size)
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kBands, kPixBandsCubic, S_>), grid, block, lds_rows, c->stream, p);

@@ -103,6 +103,8 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     constexpr bool RENDER = PIX != kPixNone && PIX != kPixRowsF16 && !C64;   // the fused column: pixels, or (BANDS) its float means
     constexpr bool BANDS = pix_bands(PIX);
     constexpr bool F16 = PIX == kPixRowsF16;    // rows as (l, r) half pairs (compile-time: the row stores are straight-line code)
+    constexpr bool FBANK = PIX == kPixFbank;    // the column in LDS, then a filterbank over it (sgx_fbank_batch): no row tables, no palette
+    static_assert(!(FBANK && MONO), "paired mono frames take the workspace route of sgx_fbank_batch");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf = reinterpret_cast<float2 *>(smem_raw);
     float2 *tw2 = buf + kBufComplex;
@@ -124,7 +126,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     const float4 *rd4 = reinterpret_cast<const float4 *>(plane + 272 * (tid >> 4) + 68 * ((tid & 15) >> 2) + 16 * (tid & 3));   // TR: both read sides
     tw2[tid] = p.tw2[tid];
     uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // RENDER: the table words of this thread's rows tid + 256 i
-    if (RENDER) {
+    if (RENDER && !FBANK) {
         if (!BANDS) pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -539,6 +541,14 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
             }
 
             lds_barrier();
+            if constexpr (FBANK) {
+                // one filter pass over the column, a wave per filter (sgx_fbank.hpp): element j of a row is bin j + 1, slot j + 1 of the column
+                float2 *dst = reinterpret_cast<float2 *>(p.rgba) + ((size_t)f0 * p.pairs + p.pair) * (size_t)p.R;
+                __builtin_amdgcn_s_setprio(3);
+                fbank::filter_pass<false>(m2 + 1, reinterpret_cast<const fbank::Filter *>(p.rows), reinterpret_cast<const float *>(p.samples), p.R,
+                                          p.interp == 2u, dst, dst, true, false, (uint32_t)tid, 4u);
+                next_samples_are_here();
+            } else {
             sample_pass<PIX>(p, m2, vbuf, tid);
             // the fused pixel path waits for the next transform's samples HERE: the sample pass has just waited for its table words with
             // vmcnt(0), so they are there -- behind the row pass, whose pixel stores sit in a loop the compiler cannot count through,
@@ -569,6 +579,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
                 uchar4 *dst_b = rgba + ((size_t)f1 * p.pairs + p.pair) * (size_t)p.R;
                 __builtin_amdgcn_s_setprio(3);
                 row_pass<MONO, PIX>(p, row_words, vbuf, dst_a, dst_b, have_first, have_second, pal, tid);
+            }
             }
         }
         SGX_STAMP(13)   // row stores issued (fused pixel path: the pixel passes)
@@ -792,6 +803,8 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
     if (n_frames == 0) return hipSuccess;
     const auto *t = static_cast<const WgTables *>(c->d_fast_wg);
     const bool band_means = call.kind == Out::kBands || call.kind == Out::kPeak, column = band_means || call.kind == Out::kRgba;
+    const sgx_fbank *bank = call.kind == Out::kFbank ? call.bank : nullptr;
+    if (call.kind == Out::kFbank && !wg4096_can_fuse_fbank(c, bank)) return hipErrorInvalidValue;   // (the workspace route: stft_route)
     const size_t peak_group = call.kind == Out::kPeak ? call.peak_group : 0;
     if (call.kind == Out::kPeak && peak_group == 0) return hipErrorInvalidValue;
     // the partial columns of every persistent workgroup
@@ -818,7 +831,7 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
         p.tw1 = t->d_tw1;
         p.tw2 = t->d_tw2;
         p.window = c->d_window;
-        p.mags = column ? nullptr : static_cast<float *>(call.out);
+        p.mags = column || bank ? nullptr : static_cast<float *>(call.out);
         p.out_f16 = call.kind == Out::kMagsF16 ? 1u : 0u;
         p.first_frame = first_frame;
         p.n_frames = n_frames;
@@ -855,6 +868,14 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
                 p.peak_partial = t->d_peak_partial;
             }
         }
+        if (bank) {   // (in the words of the row and sample tables: see Params)
+            p.rows = reinterpret_cast<const uint32_t *>(bank->d_filters);
+            p.samples = reinterpret_cast<const PackedSample *>(bank->d_weights);
+            p.n_samples = (uint32_t)bank->n_weights;
+            p.R = bank->n_filters;
+            p.interp = bank->power;
+            p.rgba = static_cast<uint8_t *>(call.out);
+        }
         // A one-channel stream (include/sgx.h, "Mono streams"): by default every frame its own real-input transform
         // (stft4096_real.hip); SGX_FLAG_PAIRED_FRAMES: two frames per transform; SGX_FLAG_COMPLEX_MONO: every frame as its own (s, s)
         // transform
@@ -877,7 +898,7 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
         // the pixel code of the instantiation: the interpolator and the seed-only LUT search are compile-time (kPixCubic / kPixCosine);
         // SGX_FLAG_LUT_WALK and palettes whose seed proof fails run kPixGeneric
         const bool cosine = p.interp == SGX_INTERP_COSINE;
-        const int pix = call.kind == Out::kComplex ? kPixRowsC64 : call.kind == Out::kMagsF16 ? kPixRowsF16 : call.kind == Out::kMags ? kPixNone
+        const int pix = bank ? kPixFbank : call.kind == Out::kComplex ? kPixRowsC64 : call.kind == Out::kMagsF16 ? kPixRowsF16 : call.kind == Out::kMags ? kPixNone
                       : peak_group ? (cosine ? kPixPeakCosine : kPixPeakCubic) : band_means ? (cosine ? kPixBandsCosine : kPixBandsCubic)
                       : (!p.seed_pm1 ? kPixGeneric : (cosine ? kPixCosine : kPixCubic));
         auto launch = [&](auto mono_c, auto pairing_c, auto c2_c) {
@@ -889,6 +910,9 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
             PIX(kPixRowsC64) PIX(kPixRowsF16) PIX(kPixNone) PIX(kPixBandsCubic) PIX(kPixBandsCosine) PIX(kPixCubic) PIX(kPixCosine) PIX(kPixGeneric)
             case kPixPeakCubic: case kPixPeakCosine:   // (no peak instantiation pairs frames: refused above)
                 if constexpr (!M_) { if (pix == kPixPeakCubic) go(std::integral_constant<int, kPixPeakCubic>{}); else go(std::integral_constant<int, kPixPeakCosine>{}); }
+                break;
+            case kPixFbank:   // ((l, r) streams and pair planes only: can_fuse_fbank)
+                if constexpr (!M_ && C2_) go(std::integral_constant<int, kPixFbank>{});
                 break;
 #undef PIX
             }
@@ -912,6 +936,17 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// sgx_fbank_batch in one kernel: a bank within the stated size (include/sgx.h) on a stream whose frames are their own transforms -- the
+// real-input kernel (one channel) or the (l, r) kernel (two channels, pair planes); paired frames and the literal (s, s) transform take
+// the workspace route
+bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb)
+{
+    if (!fb || !c->d_fast_wg || c->stft_kernel != kKernelWg4096) return false;
+    if (fb->n_filters > fbank::kFusedMaxFilters || fb->n_weights > fbank::kFusedMaxWeights) return false;
+    if (c->C == 1) return !(c->cfg.flags & (SGX_FLAG_PAIRED_FRAMES | SGX_FLAG_COMPLEX_MONO)) && real4096_serves(c, nullptr, 1);
+    return true;
 }
 
 // sgx_bands_peak_batch in one kernel: every stream the bands column serves but paired mono frames (two frames of one transform may

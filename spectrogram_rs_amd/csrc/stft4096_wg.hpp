@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_fp16.h>
 
+#include "sgx_fbank.hpp"
 #include "sgx_internal.hpp"
 
 namespace sgx {
@@ -36,6 +37,9 @@ struct Params {
     const float2 *tw1;   // [16][256]  w_4096^{t q1}
     const float2 *tw2;   // [16][16]   w_256^{t0 q2} at [q2][t0]
     const float *window; // [2048]
+    // The filterbank mode (sgx_fbank_batch, kPixFbank) has no sample stage, no row tables and no palette either, and rides the same way:
+    // `rows` is the bank's filter table (fbank::Filter [n_filters]), `samples` its weights, `n_samples` their count, `R` the filter
+    // count, `interp` the power (1 or 2) and `rgba` the output, float2 [F][pairs][n_filters].
     // Peak-hold columns (sgx_bands_peak_batch, the kPixPeak* instantiations; `rgba` is then float2 [columns][pairs][R]) write no rows
     // and carry no palette: their three values ride in those words, so that the argument block of every other instantiation -- and
     // with it their code objects -- stays as it is.
@@ -229,6 +233,9 @@ constexpr int kPixPeakCubic = 8, kPixPeakCosine = 9;
 constexpr bool pix_peak(int pix) { return pix == kPixPeakCubic || pix == kPixPeakCosine; }
 constexpr bool pix_bands(int pix) { return pix == kPixBandsCubic || pix == kPixBandsCosine || pix_peak(pix); }
 constexpr bool pix_cosine(int pix) { return pix == kPixCosine || pix == kPixBandsCosine || pix == kPixPeakCosine; }   // the interpolator is compile-time
+// a filterbank over the column (sgx_fbank_batch): the magnitudes go to LDS as for the bands, then one filter pass (sgx_fbank.hpp) -- no sample
+// stage, no row pass; the bank's tables ride in the words of the row and sample tables (Params)
+constexpr int kPixFbank = 10;
 // no pixels: the complex rows of sgx_stft_batch_complex, (L, R) as 16 bytes per bin, stored inside the split (stft4096_wg.hip)
 constexpr int kPixRowsC64 = 7;
 //   // kPixGeneric: interpolator at run time, LUT seed + walk (SGX_FLAG_LUT_WALK / proof failed)

@@ -310,6 +310,24 @@ class SpectrogramEngine:
         """1 when bands_peak_batch runs one kernel from PCM to peak columns (plus a combine pass), 0 on the workspace route"""
         return self._check(self._lib.sgx_bands_peak_fused(self._ctx))
 
+    # ---- filterbanks ------------------------------------------------------------------------
+    def filterbank(self, first, count, weights, power: int = 2) -> "FilterBank":
+        """A bank of sparse filters over the M stored bins (include/sgx.h states the definition): filter f weighs the bins
+        first[f] .. first[f] + count[f] - 1 with the next count[f] entries of `weights`.  power 1: magnitudes, 2: powers."""
+        import weakref
+
+        fb = FilterBank(self, first, count, weights, power)
+        if not hasattr(self, "_rings"):
+            self._rings = []
+        self._rings = [r for r in self._rings if r() is not None] + [weakref.ref(fb)]
+        return fb
+
+    def mel_filterbank(self, n_mels: int = 128, f_min: float = 0.0, f_max: Optional[float] = None, scale: str = "htk",
+                       norm: Optional[str] = None, power: int = 2) -> "FilterBank":
+        """The triangular mel bank of mel_weights() over this engine's bins, as a FilterBank"""
+        first, count, weights = mel_weights(self.sample_rate, self.W, n_mels, f_min, f_max, scale, norm)
+        return self.filterbank(first, count, weights, power)
+
     def render_bands(self, bands, out=None):
         """[columns][R][2] float32 band columns (row 0 lowest: bands_batch, bands_peak_batch) -> [columns][R][4] uint8, image order."""
         import torch
@@ -527,6 +545,78 @@ class LiveRing:
         return int(got.value)
 
 
+class FilterBank:
+    """sgx_fbank: a bank's tables on the device.  batch(): PCM -> [frames][pairs][n_filters][2] float32 weighted sums of the bin
+    magnitudes (power 1) or powers (power 2), (l, r) per filter; apply(): the same from rows already on the device.  Both give the
+    same bits (include/sgx.h).  Closed by SpectrogramEngine.close() like the rings."""
+
+    def __init__(self, engine: SpectrogramEngine, first, count, weights, power: int = 2):
+        self.engine = engine
+        self._lib = engine._lib
+        self._h = C.c_void_p()
+        first = np.ascontiguousarray(first, np.uint32).reshape(-1)
+        count = np.ascontiguousarray(count, np.uint32).reshape(-1)
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        assert first.size == count.size, "first and count hold one entry per filter"
+        assert weights.size == int(count.sum(dtype=np.uint64)), "weights holds sum(count) entries"
+        if weights.size == 0:
+            weights = np.zeros(1, np.float32)   # (a non-null pointer for a bank of empty filters)
+        engine.use_current_stream()
+        engine._check(self._lib.sgx_fbank_create(engine._ctx, first.size, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+                                                 weights.ctypes.data_as(C.c_void_p), int(power), C.byref(self._h)))
+        self.power = int(power)
+        self._n_weights = int(count.sum(dtype=np.uint64))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.sgx_fbank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def n_filters(self) -> int:
+        return int(self._lib.sgx_fbank_filters(self._h))
+
+    @property
+    def fused(self) -> int:
+        """1 when batch() runs one kernel from PCM to sums, 0 on the workspace route (the STFT into a bounded workspace, then the
+        stage kernel)"""
+        return self.engine._check(self._lib.sgx_fbank_fused(self._h))
+
+    def batch(self, pcm, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [frames][pairs][n_filters][2] float32"""
+        import torch
+
+        e = self.engine
+        n_samples = pcm.numel() // e.channels
+        total = e.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        out = e._out(out, (n, e.pairs, self.n_filters, 2), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            e._check(self._lib.sgx_fbank_batch(self._h, e._dev_f32(pcm), n_samples, first_frame, n, C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return out
+
+    def apply(self, mags, out=None):
+        """[columns][M][2] float32 rows (stft_batch's, flattened over pairs) -> [columns][n_filters][2] float32"""
+        import torch
+
+        e = self.engine
+        n = mags.numel() // (e.M * 2)
+        out = e._out(out, (n, self.n_filters, 2), torch.float32)
+        if n:
+            e._check(self._lib.sgx_fbank_mags(self._h, e._dev_f32(mags), n, C.c_void_p(out.data_ptr())))
+        return out
+
+
 class ImageRing:
     """sgx_image: the width x rows RGBA Pixbuf of simple_spectrogram.rs:89-94 on the device, written one pixel column per frame at
     `offset` (:140-164) and read back as it lies or as the scrolling picture of :181-209."""
@@ -640,3 +730,28 @@ def builtin_gradient(name: str) -> np.ndarray:
     if lib.sgx_builtin_gradient(name.encode(), out.ctypes.data_as(C.c_void_p)) != 0:
         raise KeyError(name)
     return out
+
+
+_MEL_SCALES = {"htk": _lib.MEL_HTK, "slaney": _lib.MEL_SLANEY}
+_MEL_NORMS = {None: _lib.MEL_NORM_NONE, "none": _lib.MEL_NORM_NONE, "slaney": _lib.MEL_NORM_SLANEY}
+
+
+def mel_weights(sample_rate: float, window_samples: int, n_mels: int = 128, f_min: float = 0.0, f_max: Optional[float] = None,
+                scale: str = "htk", norm: Optional[str] = None):
+    """sgx_mel_weights: the triangular mel bank over the true bin frequencies k * sample_rate / (2 W), k = 1 .. W - 1, as
+    (first [n_mels] uint32, count [n_mels] uint32, weights [sum(count)] float32).  Host only: no device is touched.
+    f_max None: sample_rate / 2.  scale "htk" | "slaney"; norm None | "slaney"."""
+    lib = _lib.load()
+    if f_max is None:
+        f_max = sample_rate / 2.0
+    args = (C.c_double(sample_rate), int(window_samples), int(n_mels), C.c_double(f_min), C.c_double(f_max), _MEL_SCALES[scale], _MEL_NORMS[norm])
+    n = C.c_size_t(0)
+    rc = lib.sgx_mel_weights(*args, None, None, None, C.byref(n))
+    if rc != 0:
+        raise SgxError(rc, "sgx_mel_weights: invalid argument")
+    first, count = np.zeros(n_mels, np.uint32), np.zeros(n_mels, np.uint32)
+    weights = np.zeros(max(n.value, 1), np.float32)
+    rc = lib.sgx_mel_weights(*args, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), weights.ctypes.data_as(C.c_void_p), C.byref(n))
+    if rc != 0:
+        raise SgxError(rc, "sgx_mel_weights: invalid argument")
+    return first, count, weights[:n.value]
