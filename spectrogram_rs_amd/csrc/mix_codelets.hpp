@@ -1,5 +1,5 @@
 // mix_codelets.hpp -- in-register forward DFTs of 2, 3, 4, 5 and 7 points and of their products RA * RB (natural order in and out):
-// the butterflies of stft_mixed.hip (any smooth length) and stft4800_wg.hip (the application's 4800 points).
+// the butterflies of stft_mixed_kernels.hpp (any smooth length) and stft4800_wg.hip (the application's 4800 points).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -9,11 +9,10 @@
 #include "sgx_gradients.inc"
 #include "sgx_internal.hpp"
 
-#ifndef SGX_POW2_MIXED_MIN
-#define SGX_POW2_MIXED_MIN 512
-#endif
-
 namespace {
+
+// the shortest power-of-two window that rides the composite-radix stages (sgx_create): W 512 gains, W 256 and below lose
+constexpr uint32_t kPow2MixedMin = 512;
 
 thread_local std::string g_create_error;
 
@@ -517,7 +516,7 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     // powers of two from W = 512 on that have no tuned kernel ride the composite-radix stages too (compile-time plans 4 x 16 x 16,
     // 8 x 16 x 16, 4 x 8 x 16 x 16): same-device A/B against the radix-4 ladder of the generic kernel, mono / stereo:
     // W 512 +29 % / +44 %, W 1024 +48 % / +90 %, W 4096 +83 % / +117 %; W 256: -14 %, W 128: -53 % (run-time geometry)
-    const bool pow2_mixed = pow2 && c->W >= SGX_POW2_MIXED_MIN && c->W != 2048 && c->W != 8192 && sgx::mixed_supported(c->W) && !(cfg->flags & SGX_FLAG_FORCE_GENERIC);
+    const bool pow2_mixed = pow2 && c->W >= kPow2MixedMin && c->W != 2048 && c->W != 8192 && sgx::mixed_supported(c->W) && !(cfg->flags & SGX_FLAG_FORCE_GENERIC);
     if (large) {
         // no in-LDS kernel serves this length (SGX_FLAG_LARGE_TRANSFORM): four-step passes through a scratch allocated here
         e = sgx::large_init(c, &c->d_large);

@@ -58,20 +58,17 @@ __device__ __forceinline__ void wave_tree2(float ax, float ay, float &sx, float 
 // Every filter f = wave, wave + n_waves, ... of a 64 n_waves-thread workgroup over one column: col[j] = the (x, y) pair of stored bin j
 // (LDS or memory).  Both components are filtered.  DUP false: dst_a[f] = (out_x, out_y).  DUP true (two mono frames in one column):
 // dst_a[f] = (out_x, out_x) where have_a, dst_b[f] = (out_y, out_y) where have_b.  All lanes of the wave must be active.
-// A wave takes its filters eight at a time: the eight table entries are scalar loads (the tables are never written while a kernel
-// reads them: constant address space), the eight first chunks of weights and of the column are requested side by side, and only then
-// does the arithmetic start -- one memory latency per eight filters instead of two per filter (a mel filter is a few dozen bins: the
+// A wave takes its filters four at a time (G): the four table entries are scalar loads (the tables are never written while a kernel
+// reads them: constant address space), the four first chunks of weights and of the column are requested side by side, and only then
+// does the arithmetic start -- one memory latency per four filters instead of two per filter (a mel filter is a few dozen bins: the
 // pass is latency, not arithmetic).  Results wait in lane k % 64 for the wave's k-th filter and leave 64 at a time.
-#ifndef SGX_FBANK_BATCH
-#define SGX_FBANK_BATCH 4   // filters a wave takes per trip (A/B)
-#endif
 typedef unsigned int fbank_u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) fbank_u32x4 *const_u4_ptr;
 template <bool DUP>
 __device__ __forceinline__ void filter_pass(const float2 *col, const Filter *filters, const float *weights, uint32_t n_filters, bool square,
                                             float2 *dst_a, float2 *dst_b, bool have_a, bool have_b, uint32_t tid, uint32_t n_waves)
 {
-    constexpr uint32_t G = SGX_FBANK_BATCH;
+    constexpr uint32_t G = 4;   // filters a wave takes per trip (eight: inside the spreads of four, 106 scalar registers against 84 .. 89 -- profiles/fbank.txt)
     static_assert(64 % G == 0, "a batch of results never straddles two groups of filters");
     asm volatile("" : "+v"(tid));   // (opaque: inside a persistent kernel's loop over transforms the pass's lane offsets are not to be hoisted out of that loop -- they spill there)
     const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);

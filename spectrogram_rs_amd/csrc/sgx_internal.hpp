@@ -19,12 +19,6 @@ namespace sgx {
 typedef float sgx_f2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 cubic_pair(float2 y0, float2 y1, float2 y2, float2 y3, float mu, float mu2, float mu3)
 {
-#if defined(SGX_PK_PAIR) && !SGX_PK_PAIR   // (A/B: the scalar form)
-    float2 v;
-    { const float a0 = ((y3.x - y2.x) - y0.x) + y1.x, a1 = (y0.x - y1.x) - a0, a2 = y2.x - y0.x; v.x = ((a0 * mu3) + (a1 * mu2)) + ((a2 * mu) + y1.x); }
-    { const float a0 = ((y3.y - y2.y) - y0.y) + y1.y, a1 = (y0.y - y1.y) - a0, a2 = y2.y - y0.y; v.y = ((a0 * mu3) + (a1 * mu2)) + ((a2 * mu) + y1.y); }
-    return v;
-#endif
     const sgx_f2v Y0 = {y0.x, y0.y}, Y1 = {y1.x, y1.y}, Y2 = {y2.x, y2.y}, Y3 = {y3.x, y3.y};
     const sgx_f2v a0 = ((Y3 - Y2) - Y0) + Y1;
     const sgx_f2v a1 = (Y0 - Y1) - a0;
@@ -259,7 +253,7 @@ hipError_t mixed_length_tables(uint32_t n, void **out);   // the stage plan and 
 void mixed_destroy(void *tables);
 uint32_t mixed_fixed_plan(const void *tables);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
 bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode: a mono stream, every frame its own W-point transform
-// chirp-z through the composite stages of the mixed-radix kernel (stft_mixed.hip): L = 512 .. 16384, i.e. W = 86 .. 5461
+// chirp-z through the composite stages of the mixed-radix kernel (stft_mixed_kernels.hpp): L = 512 .. 16384, i.e. W = 86 .. 5461
 bool chirpz_supported(uint32_t W);
 hipError_t chirpz_init(sgx_ctx *c, void **out);
 void chirpz_destroy(void *tables);
@@ -306,11 +300,14 @@ hipError_t launch_checksum(const sgx_ctx *c, const uint32_t *d_words, size_t n_w
 // a (left, right) magnitude pair of an output row: written once, never read by the kernel
 __device__ __forceinline__ void st_stream(float2 *p, float a, float b)
 {
-#ifdef SGX_GEN_NT
-    typedef float f2s __attribute__((ext_vector_type(2)));
-    __builtin_nontemporal_store(f2s{a, b}, reinterpret_cast<f2s *>(p));
-#else
     *p = make_float2(a, b);
-#endif
 }
+
+// Diagnostic builds only (-DSGX_STAMPS=1: tools/k1_phases.py, k1r_phases.py, k16_phases.py): a kernel that keeps `st_acc[]` and `st_last` adds
+// the wave cycles since the previous stamp to phase i.  A default build compiles the stamps away.
+#if SGX_STAMPS
+#define SGX_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); st_acc[i] += now_ - st_last; st_last = now_; }
+#else
+#define SGX_STAMP(i)
+#endif
 #endif

@@ -1,15 +1,14 @@
-// stft16384_w_complex.hip -- the complex-row instantiations of the 16384-point kernel (sgx_stft_batch_complex): stft16384_w.hip's device
-// code with SGX_W16K_C64, in a namespace of its own so that the magnitude kernels there compile exactly as they did, and their launcher.
+// stft16384_w_complex.hip -- the complex-row instantiations of the 16384-point kernel (sgx_stft_batch_complex): the device code of
+// stft16384_w_kernels.hpp with SGX_W16K_C64, in a namespace of its own, and their launcher.
 #define SGX_W16K_C64 1
 #define SGX_W16K_NS w16kc
-#define SGX_W16K_KERNELS_ONLY 1
-#include "stft16384_w.hip"
+#include "stft16384_w_kernels.hpp"
 
 #include <cstring>
 
 namespace sgx {
 
-// params: stft16384_w.hip's w16k::Params, filled by launch_w16384 (the same definition, compiled into w16kc here)
+// params: the w16k::Params that launch_w16384 (stft16384_w.hip) filled (the same definition, compiled into w16kc here)
 hipError_t launch_w16384_complex(const void *params, size_t params_size, bool mono, bool slide, bool direct, dim3 grid, hipStream_t stream)
 {
     using namespace w16kc;

@@ -113,15 +113,6 @@ constexpr int kRowsC64 = 4;   // complex rows (sgx_stft_batch_complex): (S, S) p
 // SLIDE: H = 256, the window slides in registers (above).  Else: any hop (a frame starts on any sample): the eight columns of the
 // next frame pair are requested where the sliding form requests its one, straight into R -- dead since pass 1 -- and every sample is
 // fetched 2048 / H times, through L2.
-#ifndef SGX_K1R_INTERLEAVE
-#define SGX_K1R_INTERLEAVE 1
-#endif
-#ifndef SGX_SAMPLE_EARLY
-#define SGX_SAMPLE_EARLY 1   // fused pixels: the sample-table words requested in front of the column writes (stft4096_wg.hpp: sample_request)
-#endif
-#ifndef SGX_ADDTID_R
-#define SGX_ADDTID_R 1   // (0: the b64 transposes of the non-sliding instantiation, for A/B)
-#endif
 // TR (the sliding instantiation): the two LDS transposes as real / imaginary planes, written with ds_write_addtid_b32 and read back in
 // 16-byte pieces, as in stft4096_wg.hip (there: why pass 1 then runs column t = (tid >> 4) + 16 (tid & 15)).  Image 1: rows 8 F + q1 of 272
 // words; image 2: rows q2 of 280 words -- its readers are the threads (F, u = q1 + 8 q2), and with that lane order 280 is the stride whose
@@ -160,11 +151,8 @@ __device__ __forceinline__ void read_planes(const float4 *rd4, float (&xr)[16], 
 __device__ __forceinline__ float lane_xor8(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, true)); }   // row_ror:8
 
 #if SGX_STAMPS
-// diagnostic build only (tools/k1r_phases.py): per-phase wave cycles (s_memtime), summed over all waves and iterations
+// diagnostic build only (tools/k1r_phases.py): per-phase wave cycles (s_memtime), summed over all waves and iterations; SGX_STAMP: sgx_internal.hpp
 __device__ unsigned long long g_phase_cycles_r[24];
-#define SGX_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); st_acc[i] += now_ - st_last; st_last = now_; }
-#else
-#define SGX_STAMP(i)
 #endif
 
 template <int MODE, int PIX, bool SLIDE>
@@ -172,7 +160,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf = reinterpret_cast<float2 *>(smem_raw);
-    constexpr bool TR = SLIDE && SGX_ADDTID_R;
+    constexpr bool TR = SLIDE;
     float2 *tw2 = buf + (TR ? kBufComplexTR : kBufComplex);
     uint2 *pal = reinterpret_cast<uint2 *>(tw2 + 256);          // kPixels only: [256] {threshold, RGBA} (wg::pixel_for)
     constexpr bool F16 = MODE == kRowsF16;
@@ -410,9 +398,9 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
         // (fft.rs:81) -- on the self-paired bin 1024: Z = P = its register 8, twiddle -i (twu[0][0])
         const int pcol = F * 128 + (u == 0 ? 256 : 128 - u);
         float m1[8], m2[8];
-        // rows: every bin pair is stored as soon as it is computed (SGX_K1R_INTERLEAVE; stft4096_wg.hip does the same for (l, r) rows):
+        // rows: every bin pair is stored as soon as it is computed (stft4096_wg.hip does the same for (l, r) rows):
         // sixteen stores spread over the untangle instead of one burst behind it
-        constexpr bool kInterleave = (!FUSED && SLIDE && SGX_K1R_INTERLEAVE) || C64;   // (C64: at any hop -- four arrays of eight would stay live otherwise)   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
+        constexpr bool kInterleave = (!FUSED && SLIDE) || C64;   // (C64: at any hop -- four arrays of eight would stay live otherwise)   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
         const long long row = (long long)(F == 0 ? la : lb) * (long long)kM * kBin - kBin;      // byte of the (absent) bin 0
         const __amdgpu_buffer_rsrc_t r = out_rsrc(out, !FUSED ? row : 0, !FUSED && (F == 0 || have_b));
         const int l1 = kBin * u, l2 = kBin * (1152 - u);                                        // bins u + 128 q3 ; 2048 - u - 128 q3 = (1152 - u) + 128 (7 - q3)
@@ -487,7 +475,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
             // the sample pass's table words (nine per thread, the same in every iteration but eighteen registers nobody has to spare across
             // the transform) are requested as the column writes free m1 / m2, one word behind each pair of writes: their L1 / L2 latency
             // falls on the rest of the writes and on the barrier instead of on the head of the pass
-            constexpr bool kEarlyWords = SGX_SAMPLE_EARLY && PIX != wg::kPixGeneric && MODE != kFbank;   // (the generic instantiation -- interpolator and LUT walk at run time -- has no register left: one spill)
+            constexpr bool kEarlyWords = PIX != wg::kPixGeneric && MODE != kFbank;   // (the generic instantiation -- interpolator and LUT walk at run time -- has no register left: one spill)
             wg::SampleWords sw;
             const __amdgpu_buffer_rsrc_t rt_words = wg::pcm_rsrc(reinterpret_cast<const float *>(p.samples));
             int tid_w = tid;
@@ -667,7 +655,7 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
     const dim3 grid((unsigned)runs.blocks), block(256);
     auto launch = [&](auto slide_c) {
         constexpr bool S_ = decltype(slide_c)::value;
-        constexpr size_t lds_rows = (S_ && SGX_ADDTID_R) ? kLdsBytesR : kLdsBytes, lds_render = (S_ && SGX_ADDTID_R) ? kLdsBytesRenderR : kLdsBytesRender;
+        constexpr size_t lds_rows = S_ ? kLdsBytesR : kLdsBytes, lds_render = S_ ? kLdsBytesRenderR : kLdsBytesRender;
         if (hold_peak) {
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCubic, S_>), grid, block, lds_rows, c->stream, p);

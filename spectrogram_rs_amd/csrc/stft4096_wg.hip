@@ -40,25 +40,13 @@ __device__ __forceinline__ float2 cmulf(float2 a, float2 b)
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }
 
-#ifndef SGX_PRIO_A
-#define SGX_PRIO_A 1   // (l, r) / (s, s) transforms: wave priority from the end of pass 2 (A) and from the image-2 writes (B) on; 3 from the split on
-#define SGX_PRIO_B 2
-#endif
+constexpr int kPrioA = 1, kPrioB = 2;   // (l, r) / (s, s) transforms: wave priority from the end of pass 2 (A) and from the image-2 writes (B) on; 3 from the split on
 #if SGX_STAMPS
-// diagnostic build only (tools/k1_phases.py): per-phase wave cycles (s_memtime), summed over all waves and iterations
+// diagnostic build only (tools/k1_phases.py): per-phase wave cycles (s_memtime), summed over all waves and iterations; SGX_STAMP: sgx_internal.hpp
 __device__ unsigned long long g_phase_cycles[20];
-#define SGX_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); st_acc[i] += now_ - st_last; st_last = now_; }
-#else
-#define SGX_STAMP(i)
 #endif
 
 // PIX: kPixNone = rows (float or half pairs); else the fused pixel path with that pixel code (stft4096_wg.hpp)
-#ifndef SGX_ABL_LDS
-#define SGX_ABL_LDS 0
-#endif
-#ifndef SGX_ADDTID
-#define SGX_ADDTID 1   // (0: the (l, r) sliding kernel with the b64 transposes of every other instantiation, for A/B)
-#endif
 // rows q and q + 1 of the real and the imaginary plane, this wave's 64 words of each: LDS address = M0 + offset + 4 * lane
 // (M0 is set inside the statement.  It cannot be DECLARED clobbered: clang answers "inline asm clobber list contains reserved registers: m0 ...
 // may not be preserved" (ROCm 7.2) -- so that nothing of the compiler's may depend on M0 around these statements is checked on the ISA of
@@ -66,10 +54,6 @@ __device__ unsigned long long g_phase_cycles[20];
 // GWS, s_sendmsg, interpolation) in a kernel that issues add-TID stores)
 __device__ __forceinline__ void addtid_rows(float2 a, float2 b, uint32_t m0_wave, int q)
 {
-#if SGX_ABL_LDS & 1   // timing only (diagnostic builds): the values live, no LDS write
-    asm volatile("" ::"v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y));
-    return;
-#endif
     asm volatile("s_mov_b32 m0, %4\n\t"
                  "s_nop 0\n\t"            // one wait state between a scalar write of M0 and an add-TID LDS instruction (the compiler does not see into the statement)
                  "ds_write_addtid_b32 %0 offset:%5\n\t"
@@ -85,12 +69,7 @@ __device__ __forceinline__ void read_planes(const float4 *rd4, float (&xr)[16], 
 {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-#if SGX_ABL_LDS & 2   // timing only: no LDS read
-        float4 r = {1.0f, 2.0f, 3.0f, (float)c}, i = {4.0f, 3.0f, 2.0f, 1.0f};
-        asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w), "+v"(i.x), "+v"(i.y), "+v"(i.z), "+v"(i.w) : "v"(rd4));
-#else
         const float4 r = rd4[c], i = rd4[c + 1088];
-#endif
         xr[4 * c] = r.x; xr[4 * c + 1] = r.y; xr[4 * c + 2] = r.z; xr[4 * c + 3] = r.w;
         xi[4 * c] = i.x; xi[4 * c + 1] = i.y; xi[4 * c + 2] = i.z; xi[4 * c + 3] = i.w;
     }
@@ -119,7 +98,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     // and across the lane groups of ds_read_b128), so the 16 values a thread of the NEXT pass transforms must sit in 16 consecutive
     // threads of THIS one: pass 1 runs column t = (tid >> 4) + 16 (tid & 15) instead of t = tid.  Only the sliding window can afford
     // that: its one 8-byte load per transform is the only one whose lanes then stride 128 bytes.
-    constexpr bool TR = kSlide2 && SGX_ADDTID;
+    constexpr bool TR = kSlide2;
     const int t_p1 = TR ? (tid >> 4) + 16 * (tid & 15) : tid;     // pass-1 column of this thread
     float *plane = reinterpret_cast<float *>(smem_raw);           // TR: re [16][272], im [16][272] behind it (34 816 B, the images' bytes)
     const uint32_t m0_wave = __builtin_amdgcn_readfirstlane((uint32_t)(tid >> 6) * 272u);   // TR: byte offset of this wave inside a plane row
@@ -371,7 +350,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
             }
         }
         fft16(xr, xi);
-        if (!MONO) __builtin_amdgcn_s_setprio(RENDER ? 2 : SGX_PRIO_A);   // (fused (l, r) pixels: 2 / 2 measured 3 % ahead of 1 / 2, rows the other way round)
+        if (!MONO) __builtin_amdgcn_s_setprio(RENDER ? 2 : kPrioA);   // (fused (l, r) pixels: 2 / 2 measured 3 % ahead of 1 / 2, rows the other way round)
         SGX_STAMP(4)    // image-1 reads + FFT16
         lds_barrier();  // everyone has read image 1
         SGX_STAMP(5)    // barrier 2
@@ -391,7 +370,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
                 buf[t0_2 * kS2 + q1_2 + 16 * q2] = q2 == 0 ? v : cmulf(v, tw2[q2 * 16 + t0_2]);
             }
         }
-        if (!MONO) __builtin_amdgcn_s_setprio(SGX_PRIO_B);
+        if (!MONO) __builtin_amdgcn_s_setprio(kPrioB);
         SGX_STAMP(6)    // twiddles (LDS reads) + image-2 writes
         lds_barrier();
         SGX_STAMP(7)    // barrier 3
@@ -417,11 +396,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int pos = FFT16_OUT[8 + j];
-#if SGX_ABL_LDS & 1
-            asm volatile("" ::"v"(xr[pos]), "v"(xi[pos]));
-#else
             buf[j * 256 + col] = make_float2(xr[pos], xi[pos]);
-#endif
         }
         SGX_STAMP(10)   // partner writes
         lds_barrier();
@@ -436,25 +411,13 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         float2 pb[8] = {};
         if (kInterleave) {
 #pragma unroll
-            for (int q3 = 0; q3 < 8; ++q3) {
-#if SGX_ABL_LDS & 2
-                pb[q3] = make_float2((float)q3, 1.0f);
-                asm volatile("" : "+v"(pb[q3].x), "+v"(pb[q3].y) : "v"(pcol));
-#else
-                pb[q3] = buf[(7 - q3) * 256 + pcol];
-#endif
-            }
+            for (int q3 = 0; q3 < 8; ++q3) pb[q3] = buf[(7 - q3) * 256 + pcol];
         }
-#if SGX_ABL_STORES == 1   // timing only: every row lands in the first 64 rows
-        const long long f0_il = f0 & 63;
-#else
-        const long long f0_il = f0;
-#endif
         constexpr int kRowBin = C64 ? 16 : (F16 ? 4 : 8);   // bytes per output bin
         // (C64 frame pairs: r_il / r_il2 are the rows of frames f0 / f1, each dropped when outside the requested range)
         const __amdgpu_buffer_rsrc_t r_il = (C64 && MONO)
             ? row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)(have_first ? f0 : 0) * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin, have_first)
-            : row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)f0_il * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin);
+            : row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)f0 * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin);
         const __amdgpu_buffer_rsrc_t r_il2 = (C64 && MONO)
             ? row_rsrc(reinterpret_cast<char *>(p.mags), (long long)(((size_t)f1 * p.pairs + p.pair) * ((size_t)kM * kRowBin)) - kRowBin, have_second)
             : r_il;
@@ -487,9 +450,6 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
                     const __half2 h = __floats2half2_rn(ml[q3], mr[q3]);
                     __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t *>(&h), r_il, ((q3 == 0 && col == 0) ? (int)0x80000000 : col * 4) + 1024 * (q3 & 3), 4096 * (q3 >> 2), 0);
                 } else {
-#if SGX_ABL_STORES == 3     // timing only: every value computed and live, (practically) no store executed
-                    if (ml[q3] == 12345.678f)
-#endif
                     __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(ml[q3]), __float_as_uint(mr[q3])}, r_il, ((q3 == 0 && col == 0) ? (int)0x80000000 : col * 8) + 2048 * (q3 & 1), 4096 * (q3 >> 1), kAuxNt);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -712,8 +672,8 @@ hipError_t wg4096_init(sgx_ctx *c, void **out)
     };
     for (size_t i = 0; i < rows.size(); ++i) {
         const auto &r = c->tab.rows[i];
-        // (the row word holds 16 bits of count; only the SGX_ROW_BATCH row pass keeps a BYTE per block of 256 rows, block_max_cnt)
-        if (r.count >= (SGX_ROW_BATCH ? 256u : 65536u) || samples.size() >= 65536) fusable = false;
+        // (the row word holds 16 bits of count)
+        if (r.count >= 65536u || samples.size() >= 65536) fusable = false;
         rows[i] = ((uint32_t)samples.size() & 0xffffu) | ((r.count & 0xffffu) << 16);
         for (uint32_t j = 0; j < r.count; ++j) samples.push_back(packed(c->tab.samples[r.first + j]));
         if (r.count >= 4 && (r.count & 1u) == 0) samples.push_back(samples.back());   // the pad slot
@@ -729,7 +689,7 @@ hipError_t wg4096_init(sgx_ctx *c, void **out)
         if (single && 256 * blk < rows.size()) t->single_rows |= 1u << blk;
         uint32_t mx = 0;
         for (size_t i = 256 * blk; i < 256 * (blk + 1) && i < rows.size(); ++i) mx = mx > c->tab.rows[i].count ? mx : c->tab.rows[i].count;
-        t->block_max_cnt |= (mx > 255 ? 255u : mx) << (8 * blk);     // (a row of 256 samples or more: not fusable, below)
+        t->block_max_cnt |= (mx > 255 ? 255u : mx) << (8 * blk);     // (saturates at 255; no kernel reads it: Params)
     }
 
     auto up = [](auto **dst, const auto &v) {
@@ -924,10 +884,8 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
             else launch(T{}, std::integral_constant<int, kPairAdjacent>{}, F{});
         } else if (channels == 1) {   // every mono frame as its own (s, s) transform
             launch(F{}, std::integral_constant<int, kPairAdjacent>{}, F{});
-#ifndef SGX_NO_STEREO_SLIDE
         } else if (c->H == 256) {
             launch(F{}, std::integral_constant<int, kPairAdjacentRow>{}, T{});    // (l, r) at H = 256: sliding register window
-#endif
         } else {
             launch(F{}, std::integral_constant<int, kPairAdjacent>{}, T{});
         }

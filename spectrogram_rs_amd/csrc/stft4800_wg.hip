@@ -86,9 +86,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void *base)
 
 // MODE: 0 an (l, r) stream, one frame per transform; 1 a mono stream, frames (2j, 2j+1) per transform; 2 a mono stream, every
 // frame its own (s, s) transform (the default: the reference's dataflow)
-#ifndef W48_ABL
-#define W48_ABL 0   // ablation builds (profiles/r03_app_point.txt): 1 no row stores, 2 no sample loads, 4 / 8 no butterfly in pass 2 / 3
-#endif
 // MODE_X 4 + MODE: the complex rows of sgx_stft_batch_complex, (L, R) as float4 per bin (F16 false)
 template <int MODE_X, bool F16>
 __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4))) stft4800_wg_kernel(Params p)
@@ -158,7 +155,6 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         const int sec = j.data_second ? second_off : 0;
 #pragma unroll
         for (int a = 0; a < 8; ++a) {
-            if (W48_ABL & 2) { pl[a] = (float)(a + tl); pr[a] = (float)(tl - a); continue; }
             if (MODE == 0) {
                 const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, 8 * tl, 8 * kN1 * a, 0);
                 pl[a] = __uint_as_float(v.x); pr[a] = __uint_as_float(v.y);
@@ -230,7 +226,7 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
             const float2 *r2 = buf + (tid & 15) * kS1 + (tid >> 4);
 #pragma unroll
             for (int t1 = 0; t1 < 20; ++t1) x[t1] = r2[15 * t1];
-            if (!(W48_ABL & 4)) mix::dft_composite<5, 4>(x);
+            mix::dft_composite<5, 4>(x);
         }
         lds_barrier();  // everyone has read image 1
         if (const int tid = lane(); tid < kN2) {
@@ -245,7 +241,7 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         float2 y[15];
 #pragma unroll
         for (int t0 = 0; t0 < 15; ++t0) y[t0] = buf[t0 * kS2 + lane()];
-        if (!(W48_ABL & 8)) mix::dft_composite<5, 3>(y);
+        mix::dft_composite<5, 3>(y);
         // (the bins are FINISHED before the next transform's samples are requested: the compiler otherwise moves the request above the
         // butterfly, where the sixteen extra live registers do not fit)
 #pragma unroll
@@ -266,7 +262,7 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         const int pcol = tid == 0 ? kT : kT - tid;   // slot s of the partner at buf[s kT + (pcol mod kT)]: thread 0 reads one slot up
         // Every segment is stored as soon as its bins are split (order 1, 0, 2 .. 7: segment 0's dropped lane re-stores its segment-1 bin):
         // eight stores spread over the split instead of a burst of eight behind it -- a wave stalls at the issue of a store while the
-        // CU's vector-memory path drains the previous ones (profiles/r05_k1_stereo.txt; W48_BURST restores the burst for A/B).
+        // CU's vector-memory path drains the previous ones (profiles/r05_k1_stereo.txt).
         float ml[8], mr[8];
         float cl[8], cr[8];   // C64: the imaginary parts beside ml / mr, which then hold the real parts of L and R
         float2 pb[8];
@@ -321,7 +317,6 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 return;
             }
             float l = ml[q3], r = mr[q3];
-            if ((W48_ABL & 1) && l != -12345.0f) return;
             int lane_off = bin_bytes * (tid + kT);
             if (q3 == 0) { l = drop0 ? ml[1] : l; r = drop0 ? mr[1] : r; lane_off = drop0 ? bin_bytes * 2 * kT : lane_off; }
             if (q3 == 7) { l = drop7 ? ml[6] : l; r = drop7 ? mr[6] : r; lane_off = drop7 ? bin_bytes * tid : lane_off; }
@@ -339,12 +334,6 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 if (MODE == 1) __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(vb), __float_as_uint(vb)}, rb, lane_off, bin_bytes * kT * q3, 2);
             }
         };
-#ifdef W48_BURST
-#pragma unroll
-        for (int q3 = 0; q3 < 8; ++q3) split(q3);
-#pragma unroll
-        for (int q3 = 0; q3 < 8; ++q3) store(q3);
-#else
         split(1);
         split(0);
         store(1);
@@ -357,7 +346,6 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
             store(q3);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
         take(nxt.data_second);
     }
 }

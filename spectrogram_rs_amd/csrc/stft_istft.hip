@@ -7,7 +7,7 @@
 //   x[n] = sum_t w[m] f_t[m] / sum_t w[m]^2,  m = n - t H,  frames t of the call in ascending order; 0 where the envelope is 0
 //
 // One 2W-point complex inverse per frame carries both channels: Z[k] = L[k] + i R[k], Z[P - k] = conj L[k] + i conj R[k], Z[0] = Z[W] = 0;
-// Re z = g_l, Im z = g_r.  Two routes through the composite stages of stft_mixed.hip (run-time geometry, DynGeo):
+// Re z = g_l, Im z = g_r.  Two routes through the composite stages of stft_mixed_kernels.hpp (run-time geometry, DynGeo):
 //   route 1, 2W 2-3-5-7-smooth: Z at the digit-reversed positions of the 2W-point plan, stage_inv back to natural order; c_e, c_o from the
 //            padding half in the time domain;
 //   route 2, any other 2W with 3W - 1 <= 16384: chirp-z, z[n] = conj c[n] sum_k (Z[k] conj c[k]) c[n - k], c[n] = e^{-i pi n^2 / P}, as a
@@ -19,8 +19,7 @@
 // samples per channel; thread tid owns ring slots tid + i threads.  After frame t every sample below (t + 1) H has all its frames: block t
 // ([tH, tH + H)) is divided by its envelope, stored, and its slots are cleared.  Each sample's sum runs over its frames in ascending order
 // from zero in every workgroup and call, so the output is bit-identical however the sample range is split.  No atomics.
-#define SGX_MIXED_KERNELS_ONLY 1
-#include "stft_mixed.hip"
+#include "stft_mixed_kernels.hpp"
 
 #include <cmath>
 

@@ -1,9 +1,7 @@
 // stft_mixed_bands.hip -- the bands instantiations of the mixed-radix kernels' fused column (sgx_bands_batch): the same transforms and
 // pixel_passes' sample pass as the kernels that render pixels (stft_mixed.hip), then the rows' (l, r) means stored as float2 instead of
-// a colour.  A translation unit of its own so that these instantiations compile beside stft_mixed.hip's, not behind them; it takes the
-// device code of stft_mixed.hip and none of its host code.
-#define SGX_MIXED_KERNELS_ONLY 1
-#include "stft_mixed.hip"
+// a colour.  A translation unit of its own so that these instantiations compile beside stft_mixed.hip's, not behind them.
+#include "stft_mixed_kernels.hpp"
 
 namespace sgx {
 namespace mix {
@@ -23,7 +21,7 @@ __global__ void __launch_bounds__(F::NT, F::NT <= 256 ? 4 : 8) stft_mixed_fixed_
 {
     if constexpr (!kOwnText<F>) {
         fixed3_body<F, R0A, R0B, R1A, R1B, R2A, R2B, REAL, BandsColumn>(p);
-    } else {   // fixed3_body's text: see kOwnText in stft_mixed.hip
+    } else {   // fixed3_body's text: see kOwnText in stft_mixed_kernels.hpp
         extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
         float2 *s = reinterpret_cast<float2 *>(smem_raw);
         const uint32_t tid = threadIdx.x;
@@ -45,7 +43,7 @@ __global__ void __launch_bounds__(F::NT, F::NT == 256 ? 4 : (F::NT == 512 ? 8 : 
     fixed4_body<F, R0A, R0B, R1A, R1B, R2A, R2B, R3A, R3B, REAL, BandsColumn>(p);
 }
 
-// The body of stft_mixed_real2_render_kernel (stft_mixed.hip) with pixel_passes in its BANDS form.  (A copy: see fixed3_body there.)
+// The body of stft_mixed_real2_render_kernel (stft_mixed.hip) with pixel_passes in its BANDS form.  (A copy: see fixed3_body in stft_mixed_kernels.hpp.)
 template <typename F, int R0A, int R0B, int R1A, int R1B, int R2A, int R2B>
 __global__ void __launch_bounds__(2 * F::NT, real2_waves_per_simd<F>()) stft_mixed_real2_bands_kernel(Params p)
 {
@@ -86,15 +84,13 @@ __global__ void __launch_bounds__(2 * F::NT, real2_waves_per_simd<F>()) stft_mix
 
 // The instantiations are those launch_mixed's pixel path selects: real-input mode two frames per workgroup (MIX_REAL2_RENDER_PLANS) or
 // on a four-stage plan, every other stream on any compile-time plan.  (Real-input mode on a three-stage plan with one frame per
-// workgroup -- the 2048-point plan, or every plan in an SGX_KM_REAL1 build -- has none: the two-kernel route.)
+// workgroup -- the 2048-point plan -- has none: the two-kernel route.)
 bool bands_kernel_exists(int fixed, bool real, bool two_frames)
 {
     if (real && two_frames) {
-#ifndef SGX_KM_REAL1
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) if (fixed == Pn) return true;
         MIX_REAL2_RENDER_PLANS(X)
 #undef X
-#endif
         return false;
     }
 #define X(Pn, A0, B0, A1, B1, A2, B2, A3, B3, N) if (fixed == Pn) return true;
@@ -111,7 +107,6 @@ hipError_t launch_bands_kernel(const Params &p, int fixed, bool real, bool two_f
 {
     auto go = [&](auto kernel, unsigned nt, dim3 g) { return launch_kernel(kernel, p, nt, g, lds, stream); };
     if (real && two_frames) {
-#ifndef SGX_KM_REAL1
         switch (fixed) {
 #define X(Pn, A0, B0, A1, B1, A2, B2, N) \
     case Pn: return go(stft_mixed_real2_bands_kernel<Fixed3<Pn, A0, B0, A1, B1, A2, B2, N>, A0, B0, A1, B1, A2, B2>, 2 * N, dim3((grid.x + 1) / 2, 1));
@@ -119,7 +114,6 @@ hipError_t launch_bands_kernel(const Params &p, int fixed, bool real, bool two_f
 #undef X
         default: break;
         }
-#endif
         return hipErrorNotSupported;
     }
     switch (fixed) {

@@ -1,9 +1,7 @@
 // stft_mixed_complex.hip -- the complex-row instantiations of the mixed-radix and chirp-z kernels (sgx_stft_batch_complex): the same
 // transforms as stft_mixed.hip's row kernels, then the (l, r) split -- or real-input mode's untangle -- stored as complex spectra, (L, R) as
-// float4 per bin.  A translation unit of its own that takes stft_mixed.hip's device code and none of its host code, as
-// stft_mixed_bands.hip does.
-#define SGX_MIXED_KERNELS_ONLY 1
-#include "stft_mixed.hip"
+// float4 per bin.  A translation unit of its own, as stft_mixed_bands.hip is.
+#include "stft_mixed_kernels.hpp"
 
 namespace sgx {
 namespace mix {
@@ -41,7 +39,7 @@ __device__ __forceinline__ void split_store_c64(const Params &p, const float2 *s
     }
 }
 
-// Real-input mode (see untangle in stft_mixed.hip): S[k] = E[k] + w_2W^k O[k] and S[W - k] = conj(E[k] - w_2W^k O[k]); the row holds (S, S)
+// Real-input mode (see untangle in stft_mixed_kernels.hpp): S[k] = E[k] + w_2W^k O[k] and S[W - k] = conj(E[k] - w_2W^k O[k]); the row holds (S, S)
 __device__ __forceinline__ void untangle_store_c64(const Params &p, const float2 *s, long long row, uint32_t tid, uint32_t nt)
 {
     const uint32_t M = p.W - 1, K = p.W / 2;
@@ -68,7 +66,7 @@ __device__ __forceinline__ void untangle_store_c64(const Params &p, const float2
     }
 }
 
-// stft_mixed_kernel (run-time geometry) with the complex store.  (A copy, as the chirp-z kernels below: see fixed3_body in stft_mixed.hip.)
+// stft_mixed_kernel (run-time geometry) with the complex store.  (A copy, as the chirp-z kernels below: see fixed3_body in stft_mixed_kernels.hpp.)
 __global__ void __launch_bounds__(1024) stft_mixed_complex_kernel(Params p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];

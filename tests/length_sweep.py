@@ -30,7 +30,7 @@ from conftest import FLOOR_K16, FLOOR_WIDE, PEAK_FLOOR
 MIX_MAX_P = 20480            # mixed_supported: 2W <= 20480 (the transform lives in LDS)
 MIX_MAX_RADIX = 28           # kMaxRadix
 MIX_LDS_BYTES = 160 * 1024
-POW2_MIXED_MIN = 512         # SGX_POW2_MIXED_MIN: powers of two from here on ride the composite stages (but 2048: K1, 8192: K16)
+POW2_MIXED_MIN = 512         # kPow2MixedMin (sgx_api.hip): powers of two from here on ride the composite stages (but 2048: K1, 8192: K16)
 CHIRP_MAX_L = 16384          # bluestein_supported / chirpz_supported: 3W - 1 <= 16384
 CHIRP_STAGES_MIN_L = 512     # chirpz_supported: L = 512 .. 16384 run the composite stages, shorter ones the radix-4 ladder (W < 86)
 LARGE_MAX_W = 1 << 20        # large_plan.hpp: kMaxW
@@ -98,7 +98,7 @@ def mixed_pad_every(P: int, plan) -> int:
     return 0
 
 
-# MIX_FIXED_PLANS / MIX_FIXED4_PLANS of csrc/stft_mixed.hip: P -> the compile-time stages (tests/test_length_sweep.py holds this table to
+# MIX_FIXED_PLANS / MIX_FIXED4_PLANS of csrc/stft_mixed_kernels.hpp: P -> the compile-time stages (tests/test_length_sweep.py holds this table to
 # the macros' text).  render_path bit 2 is set when the run-time rule arrives at exactly this plan, with R_last's padding.
 MIX_FIXED = {
     4800: ((5, 4), (5, 3), (4, 4)), 4410: ((7, 3), (5, 3), (7, 2)), 3200: ((5, 4), (5, 2), (4, 4)), 1600: ((5, 4), (5, 1), (4, 4)),
@@ -110,8 +110,8 @@ MIX_FIXED = {
 
 
 def macro(name):
-    """the X(...) argument lists of a #define in csrc/stft_mixed.hip, continuation lines included (the tests hold the tables here to them)"""
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spectrogram_rs_amd", "csrc", "stft_mixed.hip")
+    """the X(...) argument lists of a #define in csrc/stft_mixed_kernels.hpp, continuation lines included (the tests hold the tables here to them)"""
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spectrogram_rs_amd", "csrc", "stft_mixed_kernels.hpp")
     m = re.search(r"#define " + name + r"\(X\)((?:.*\\\n)*.*)\n", open(src).read())
     assert m, name
     return [tuple(int(v) for v in args.split(",")) for args in re.findall(r"X\(([^)]*)\)", m.group(1))]
@@ -168,7 +168,7 @@ def is_pow2(n: int) -> bool:
 
 
 ALL_SMOOTH_W = [W for W in range(4, MIX_MAX_P // 2 + 1) if smooth7(2 * W)]
-# the windows another kernel runs by default: the generic power-of-two kernel below SGX_POW2_MIXED_MIN, K1 at 2048, K16 at 8192
+# the windows another kernel runs by default: the generic power-of-two kernel below kPow2MixedMin, K1 at 2048, K16 at 8192
 SMOOTH_EXCLUDED = [W for W in ALL_SMOOTH_W if is_pow2(W) and (W < POW2_MIXED_MIN or W in (2048, 8192))]
 
 

@@ -264,7 +264,7 @@ def wg_predicates(c: Config) -> dict:
 
 
 def wg_fusable(c: Config) -> bool:
-    """wg4096_init's `fusable` (SGX_ROW_BATCH 0: the row word's 16 bits of count)"""
+    """wg4096_init's `fusable` (`r.count >= 65536u || samples.size() >= 65536`: the row word's 16 bits of count)"""
     return all(wg_predicates(c).values())
 
 

@@ -65,10 +65,10 @@ def test_the_constants_and_thread_tables_are_the_sources():
     hpp = open(os.path.join(CSRC, "stft4096_wg.hpp")).read()
     ks1 = int(re.search(r"constexpr int kS1 = (\d+);", hpp).group(1))
     assert "kBufComplex = 16 * kS1" in hpp and "kColSlots = 2050" in hpp and 16 * ks1 - 2050 == pp.WG_MAX_SLOTS
-    assert "#define SGX_ROW_BATCH 0" in hpp
     assert "constexpr int kTCells = 512;" in open(os.path.join(CSRC, "sgx_internal.hpp")).read()
     wg = open(os.path.join(CSRC, "stft4096_wg.hip")).read()
     assert "c->tab.rows.size() <= 1024" in wg and "r.count >= 4 && (r.count & 1u) == 0" in wg
+    assert "if (r.count >= 65536u || samples.size() >= 65536) fusable = false;" in wg       # the row word's 16 bits of count: pp.wg_predicates
 
 
 def test_every_reachable_class_appears_under_three_palettes():
