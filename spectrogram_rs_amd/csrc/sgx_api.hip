@@ -46,16 +46,6 @@ uint32_t f32_as_u32(float v)
     return (uint32_t)v;
 }
 
-template <typename T>
-hipError_t upload(T **dst, const T *src, size_t n)
-{
-    if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-    if (n == 0) return hipSuccess;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), n * sizeof(T));
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice);
-}
-
 const unsigned char *builtin_gradient(const char *name)
 {
     if (!name) return nullptr;
@@ -188,10 +178,10 @@ int upload_palette(sgx_ctx *c)
     SGX_HIP(c, hipSetDevice(c->device));
     // ordering against kernels that may still read the old tables
     SGX_HIP(c, hipStreamSynchronize(c->stream));
-    SGX_HIP(c, upload(&c->d_lut_rgba, rgba.data(), rgba.size()));
-    SGX_HIP(c, upload(&c->d_lut_thr, c->pal.lut_thr.data(), c->pal.lut_thr.size()));
-    SGX_HIP(c, upload(&c->d_alpha_thr, c->pal.alpha_thr.data(), c->pal.alpha_thr.size()));
-    SGX_HIP(c, upload(&c->d_t_thr, c->pal.t_thr.data(), c->pal.t_thr.size()));
+    SGX_HIP(c, c->d_lut_rgba.upload(rgba));
+    SGX_HIP(c, c->d_lut_thr.upload(c->pal.lut_thr));
+    SGX_HIP(c, c->d_alpha_thr.upload(c->pal.alpha_thr));
+    SGX_HIP(c, c->d_t_thr.upload(c->pal.t_thr));
     c->pal.t_cell.clear();
     if (c->pal.segments && c->pal.stereo && c->pal.t_thr.size() < 65535) {
         // t_cell[c] = switch points in cells below c: a balance in cell c has passed at least t_cell[c] of them and at most t_cell[c + 1]
@@ -199,7 +189,7 @@ int upload_palette(sgx_ctx *c)
         for (double thr : c->pal.t_thr)
             for (int cell = sgx::sgx_t_cell(thr) + 1; cell <= sgx::kTCells; ++cell) ++c->pal.t_cell[cell];
     }
-    SGX_HIP(c, upload(&c->d_t_cell, c->pal.t_cell.data(), c->pal.t_cell.size()));
+    SGX_HIP(c, c->d_t_cell.upload(c->pal.t_cell));
     std::vector<uint2> seed;
     if (!c->pal.stereo && c->pal.n == 256 && c->pal.lut_thr.size() == 255) {
         seed.resize(256);
@@ -210,7 +200,7 @@ int upload_palette(sgx_ctx *c)
             seed[i] = make_uint2(thr_bits, word | 0xff000000u);
         }
     }
-    SGX_HIP(c, upload(&c->d_pal_seed, seed.data(), seed.size()));
+    SGX_HIP(c, c->d_pal_seed.upload(seed));   // (null where the palette has no seed table: fused_palette asks)
     ++c->palette_gen;
     return SGX_OK;
 }
@@ -238,7 +228,7 @@ Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank 
     const bool mixed = c->stft_kernel == sgx::kKernelMixed || c->stft_kernel == sgx::kKernelW4800;
     // The W 2400 rows of one or two channels come from the 4800-point kernel, unless real-input mode takes the stream (a mono stream, every
     // frame its own transform: 2400 points instead of 4800 on (s, s)); more channels run the mixed-radix kernels
-    const bool rows_from_w4800 = c->stft_kernel == sgx::kKernelW4800 && channels <= 2 && !sgx::mixed_real_serves(c, c->d_mix, channels);
+    const bool rows_from_w4800 = c->stft_kernel == sgx::kKernelW4800 && channels <= 2 && !sgx::mixed_real_serves(c, channels);
     Route rows{Family::kGeneric, true, false};
     switch (c->stft_kernel) {
     case sgx::kKernelW16384: rows.family = Family::kW16384; break;   // (a mono stream whose frames are not paired: as an (s, s) plane through the two-channel instantiation)
@@ -246,11 +236,11 @@ Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank 
     case sgx::kKernelW4800:
     case sgx::kKernelMixed:
         rows.family = rows_from_w4800 ? Family::kW4800 : Family::kMixed;
-        rows.real_input = sgx::mixed_real_serves(c, c->d_mix, channels);
+        rows.real_input = sgx::mixed_real_serves(c, channels);
         break;
     case sgx::kKernelChirp:
-        rows.family = c->d_chz ? Family::kChirpz : Family::kBluestein;
-        rows.real_input = sgx::chirpz_real_serves(c, c->d_chz, channels);
+        rows.family = c->chz ? Family::kChirpz : Family::kBluestein;
+        rows.real_input = sgx::chirpz_real_serves(c, channels);
         break;
     case sgx::kKernelWg4096:
         rows.family = Family::kWg4096;
@@ -267,19 +257,19 @@ Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank 
         fused = rows.family == Family::kWg4096 || rows.family == Family::kW4800 || rows.family == Family::kMixed;
         break;
     case Out::kRgba:      // (the pixels of a W 2400 stream come from the mixed-radix kernel whichever kernel its rows come from)
-        fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_render(c, c->d_fast_wg);
-        if (may_fuse && mixed && sgx::mixed_can_fuse_render(c, c->d_mix)) {
+        fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_render(c);
+        if (may_fuse && mixed && sgx::mixed_can_fuse_render(c)) {
             rows.family = Family::kMixed;
             fused = true;
         }
         break;
     case Out::kBands:     // Only the transform decides, not the palette: the column has no colour.  It must hold the bits of the context's rows, so
                           // a fused kernel serves only where the rows come from the same transform: not where they come from the 4800-point kernel
-        fused = may_fuse && ((rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_bands(c, c->d_fast_wg)) ||
-                             (rows.family == Family::kMixed && sgx::mixed_can_fuse_bands(c, c->d_mix)));
+        fused = may_fuse && ((rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_bands(c)) ||
+                             (rows.family == Family::kMixed && sgx::mixed_can_fuse_bands(c)));
         break;
     case Out::kPeak:      // in one kernel where sgx_bands_batch runs the 4096-point kernels and the frames are not paired
-        fused = stft_route(c, channels, Out::kBands).fused && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_peak(c, c->d_fast_wg);
+        fused = stft_route(c, channels, Out::kBands).fused && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_peak(c);
         break;
     case Out::kFbank:     // in one kernel at W 2048 where every frame is its own transform and the bank is within the stated size
         fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_fbank(c, bank);
@@ -323,7 +313,7 @@ size_t workspace_chunk(size_t bytes_per_frame, size_t n)
 
 int ensure_workspace(sgx_ctx *c, size_t frames)
 {
-    const hipError_t e = sgx::grow(c->stream, c->d_ws_mags, c->ws_frames, frames, frames * mags_bytes_per_frame(c));
+    const hipError_t e = c->d_ws_mags.grow(c->stream, frames * (mags_bytes_per_frame(c) / sizeof(float)));
     return e == hipSuccess ? SGX_OK : fail_hip(c, e, "hipMalloc(render workspace)");
 }
 
@@ -340,7 +330,7 @@ int in_workspace_chunks(sgx_ctx *c, size_t n, Body body)
 // The rows of frames [first, first + m) into the workspace (the caller has grown it to m frames), for the second kernel of a two-kernel route
 hipError_t rows_to_workspace(const sgx_ctx *c, const float *d_pcm, size_t first, size_t m, size_t total)
 {
-    return run_call(c, stft_route(c, c->C, Out::kMags), d_pcm, first, m, total, c->d_ws_mags, Out::kMags);
+    return run_call(c, stft_route(c, c->C, Out::kMags), d_pcm, first, m, total, c->d_ws_mags.get(), Out::kMags);
 }
 
 // What sgx_bands_batch runs on frames [first, first + m): the fused kernel of its route, or the rows into the workspace (m frames fit: the
@@ -355,7 +345,7 @@ int run_bands(sgx_ctx *c, const char *who, const Route &r, const float *d_pcm, s
     // two kernels, as sgx_render_batch
     hipError_t e = rows_to_workspace(c, d_pcm, first, m, total);
     if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": stft launch").c_str());
-    e = sgx::launch_magnitude_in(c, c->d_ws_mags, m * c->pairs, c->d_rows, c->d_samples, c->R, d_bands);
+    e = sgx::launch_magnitude_in(c, c->d_ws_mags.get(), m * c->pairs, c->d_rows.get(), c->d_samples.get(), c->R, d_bands);
     if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": magnitude_in launch").c_str());
     return SGX_OK;
 }
@@ -390,6 +380,10 @@ int stft_batch(sgx_ctx *c, const char *who, const float *d_pcm, size_t n_samples
 }
 
 }  // namespace
+
+// Every table, workspace and family struct is a member that frees itself: nothing is listed here.  (Out of line so that a translation unit
+// that only reads the context's layout needs neither the runtime nor the families' deleters.)
+sgx_ctx::~sgx_ctx() = default;
 
 extern "C" {
 
@@ -492,13 +486,13 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     }
 
     sgx::build_tables(c->W, c->R, c->sr_u32, cfg->f_min, cfg->f_max, cfg->interp, c->tab);
-    if ((e = upload(&c->d_window, c->tab.window.data(), c->tab.window.size())) != hipSuccess ||
-        (e = upload(&c->d_twiddle, c->tab.twiddle.data(), c->tab.twiddle.size())) != hipSuccess ||
-        (e = upload(&c->d_rows, c->tab.rows.data(), c->tab.rows.size())) != hipSuccess ||
-        (e = upload(&c->d_samples, c->tab.samples.data(), c->tab.samples.size())) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void **>(&c->d_one_in), (size_t)c->W * 2 * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void **>(&c->d_one_out), (size_t)c->M * 2 * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void **>(&c->d_cksum), sizeof(unsigned long long))) != hipSuccess)
+    if ((e = c->d_window.upload(c->tab.window)) != hipSuccess ||
+        (e = c->d_twiddle.upload(c->tab.twiddle)) != hipSuccess ||
+        (e = c->d_rows.upload(c->tab.rows)) != hipSuccess ||
+        (e = c->d_samples.upload(c->tab.samples)) != hipSuccess ||
+        (e = c->d_one_in.alloc((size_t)c->W * 2)) != hipSuccess ||
+        (e = c->d_one_out.alloc((size_t)c->M * 2)) != hipSuccess ||
+        (e = c->d_cksum.alloc(1)) != hipSuccess)
         return bail(SGX_ERR_HIP, std::string("sgx_create: table upload: ") + hipGetErrorString(e));
 
     // default palette: ColorScheme::new_mono(colorous::MAGMA, "magma"), simple_spectrogram.rs:95
@@ -519,37 +513,37 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     const bool pow2_mixed = pow2 && c->W >= kPow2MixedMin && c->W != 2048 && c->W != 8192 && sgx::mixed_supported(c->W) && !(cfg->flags & SGX_FLAG_FORCE_GENERIC);
     if (large) {
         // no in-LDS kernel serves this length (SGX_FLAG_LARGE_TRANSFORM): four-step passes through a scratch allocated here
-        e = sgx::large_init(c, &c->d_large);
+        e = sgx::large_init(c);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: multi-pass transform tables and scratch: ") + hipGetErrorString(e));
         c->stft_kernel = sgx::kKernelLarge;
     } else if (pow2_mixed || (!pow2 && sgx::mixed_supported(c->W) && !((cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::bluestein_supported(c->W)))) {
         // a length FFTW would factor: mixed-radix transform of exactly 2W points (SGX_FLAG_FORCE_GENERIC: chirp-z instead)
-        e = sgx::mixed_init(c, &c->d_mix);
+        e = sgx::mixed_init(c);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: mixed-radix tables: ") + hipGetErrorString(e));
         c->stft_kernel = sgx::kKernelMixed;
         if (!(cfg->flags & (SGX_FLAG_FORCE_GENERIC | SGX_FLAG_MIXED_GENERIC)) && sgx::w4800_supported(c)) {
-            e = sgx::w4800_init(c, &c->d_w4800);
+            e = sgx::w4800_init(c);
             if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: 4800-point kernel tables: ") + hipGetErrorString(e));
             c->stft_kernel = sgx::kKernelW4800;
         }
     } else if (!pow2) {
-        e = sgx::bluestein_init(c, &c->d_blu);
+        e = sgx::bluestein_init(c);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: Bluestein tables: ") + hipGetErrorString(e));
         if (!(cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::chirpz_supported(c->W)) {   // (SGX_FLAG_FORCE_GENERIC: the radix-4 ladder, the A/B reference)
-            e = sgx::chirpz_init(c, &c->d_chz);
+            e = sgx::chirpz_init(c);
             if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: chirp-z tables: ") + hipGetErrorString(e));
         }
         c->stft_kernel = sgx::kKernelChirp;
     } else if (!(cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::fast4096_supported(c)) {
-        e = sgx::wg4096_init(c, &c->d_fast_wg);
+        e = sgx::wg4096_init(c);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: tuned kernel tables: ") + hipGetErrorString(e));
         if (c->C == 1) {
-            e = sgx::real4096_init(c, &c->d_real);
+            e = sgx::real4096_init(c);
             if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: real-input kernel tables: ") + hipGetErrorString(e));
         }
         c->stft_kernel = sgx::kKernelWg4096;
     } else if (!(cfg->flags & SGX_FLAG_FORCE_GENERIC) && sgx::w16384_supported(c)) {
-        e = sgx::w16384_init(c, &c->d_w16k);
+        e = sgx::w16384_init(c);
         if (e != hipSuccess) return bail(SGX_ERR_HIP, std::string("sgx_create: 16384-point kernel tables: ") + hipGetErrorString(e));
         c->stft_kernel = sgx::kKernelW16384;
     }
@@ -557,6 +551,7 @@ int sgx_create(const sgx_config *cfg, sgx_ctx **out_ctx)
     return SGX_OK;
 }
 
+// The order holds the rule of device_buffer.hpp: the context's device current, its stream drained, and only then anything freed.
 void sgx_destroy(sgx_ctx *c)
 {
     if (!c) return;
@@ -565,27 +560,6 @@ void sgx_destroy(sgx_ctx *c)
     sgx::detach_views(c);
     sgx::detach_fbanks(c);
     sgx::detach_images(c);   // views that outlive their context keep their own buffers and answer SGX_ERR_INVALID_ARG from now on
-    sgx::wg4096_destroy(c->d_fast_wg);
-    c->d_fast_wg = nullptr;
-    sgx::real4096_destroy(c->d_real);
-    c->d_real = nullptr;
-    sgx::bluestein_destroy(c->d_blu);
-    c->d_blu = nullptr;
-    sgx::mixed_destroy(c->d_mix);
-    sgx::w4800_destroy(c->d_w4800);
-    c->d_mix = nullptr;
-    sgx::chirpz_destroy(c->d_chz);
-    c->d_chz = nullptr;
-    sgx::w16384_destroy(c->d_w16k);
-    c->d_w16k = nullptr;
-    sgx::large_destroy(c->d_large);
-    c->d_large = nullptr;
-    sgx::istft_destroy(c->d_istft);
-    c->d_istft = nullptr;
-    void *ptrs[] = {c->d_window, c->d_twiddle, c->d_rows, c->d_samples, c->d_lut_thr, c->d_alpha_thr,
-                    c->d_lut_rgba, c->d_pal_seed, c->d_t_thr, c->d_t_cell, c->d_band_rows, c->d_band_samples, c->d_levels, c->d_ws_mags, c->d_one_in, c->d_one_out, c->d_cksum};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     if (c->rebind_event) (void)hipEventDestroy(c->rebind_event);
     delete c;
 }
@@ -612,7 +586,7 @@ int sgx_query(const sgx_ctx *c, sgx_info *out)
     const Route rows = stft_route(c, c->C, Out::kMags), pixels = stft_route(c, c->C, Out::kRgba);
     out->render_path = 0;
     if (pixels.fused) out->render_path = pixels.family == Family::kMixed ? 3u : 1u | (sgx::wg4096_seed_is_within_one(c) ? 2u : 0u);
-    if (rows.family == Family::kChirpz || ((rows.family == Family::kMixed || rows.family == Family::kW4800) && sgx::mixed_fixed_plan(c->d_mix))) out->render_path |= 4u;
+    if (rows.family == Family::kChirpz || ((rows.family == Family::kMixed || rows.family == Family::kW4800) && sgx::mixed_fixed_plan(c))) out->render_path |= 4u;
     if (rows.real_input) out->render_path |= 8u;
     out->mags_bytes_per_frame = mags_bytes_per_frame(c);
     out->rgba_bytes_per_frame = (uint64_t)c->pairs * c->R * 4;
@@ -647,7 +621,7 @@ int sgx_set_cu_limit(sgx_ctx *c, uint32_t n)
         c->err = "sgx_set_cu_limit: more compute units than the device has";
         return SGX_ERR_INVALID_ARG;
     }
-    // Only grids and job splits read the count.  The one buffer sized by it, the 4096-point kernels' peak partials, is checked by grow() at
+    // Only grids and job splits read the count.  The one buffer sized by it, the 4096-point kernels' peak partials, is checked by DeviceBuffer::grow at
     // every launch: a limit raised again regrows it.
     c->n_cu = n ? (int)n : c->n_cu_device;
     return SGX_OK;
@@ -698,8 +672,8 @@ int sgx_istft_batch(sgx_ctx *c, const float *d_spec, size_t n_frames, size_t fir
     if (!d_spec || !d_pcm) return fail(c, SGX_ERR_INVALID_ARG, "sgx_istft_batch: null buffer");
     SGX_HIP(c, hipSetDevice(c->device));
     hipError_t e;
-    if (!c->d_istft && (e = sgx::istft_init(c, &c->d_istft)) != hipSuccess) return fail_hip(c, e, "sgx_istft_batch: tables");
-    e = sgx::launch_istft(c, c->d_istft, d_spec, n_frames, first_sample, first_sample + n, d_pcm);
+    if (!c->istft && (e = sgx::istft_init(c)) != hipSuccess) return fail_hip(c, e, "sgx_istft_batch: tables");
+    e = sgx::launch_istft(c, d_spec, n_frames, first_sample, first_sample + n, d_pcm);
     if (e != hipSuccess) return fail_hip(c, e, "sgx_istft_batch: kernel launch");
     if (n_out) *n_out = n;
     return SGX_OK;
@@ -722,7 +696,7 @@ int sgx_stft_batch_f16(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t 
         rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
             hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
             if (e == hipSuccess)
-                e = sgx::launch_to_half(c, c->d_ws_mags, static_cast<char *>(d_mags_f16) + done * per_frame * 4, m * per_frame);
+                e = sgx::launch_to_half(c, c->d_ws_mags.get(), static_cast<char *>(d_mags_f16) + done * per_frame * 4, m * per_frame);
             return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_stft_batch_f16: kernel launch");
         });
         if (rc != SGX_OK) return rc;
@@ -737,11 +711,11 @@ int sgx_process_one(sgx_ctx *c, const float *h_lr, size_t n_avail, float *h_out)
     if (n_avail < c->W) return 0;  // None (fft.rs:72)
     if (!h_lr || !h_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_process_one: null buffer");
     SGX_HIP(c, hipSetDevice(c->device));
-    SGX_HIP(c, hipMemcpyAsync(c->d_one_in, h_lr, (size_t)c->W * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SGX_HIP(c, hipMemcpyAsync(c->d_one_in.get(), h_lr, (size_t)c->W * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     // one (l, r) frame whatever the context's channel count: the family goes by the call's two channels (stft_route)
-    hipError_t e = launch_family(c, stft_route(c, 2, Out::kMags).family, StftCall{c->d_one_in, 2, 1, 0, 1, 1, c->d_one_out, Out::kMags, 0});
+    hipError_t e = launch_family(c, stft_route(c, 2, Out::kMags).family, StftCall{c->d_one_in.get(), 2, 1, 0, 1, 1, c->d_one_out.get(), Out::kMags, 0});
     if (e != hipSuccess) return fail_hip(c, e, "sgx_process_one: kernel launch");
-    SGX_HIP(c, hipMemcpyAsync(h_out, c->d_one_out, (size_t)c->M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SGX_HIP(c, hipMemcpyAsync(h_out, c->d_one_out.get(), (size_t)c->M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SGX_HIP(c, hipStreamSynchronize(c->stream));
     return 1;
 }
@@ -774,7 +748,7 @@ int sgx_render_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fi
         rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
             hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
             if (e != hipSuccess) return fail_hip(c, e, "sgx_render_batch: stft launch");
-            e = sgx::launch_render(c, c->d_ws_mags, m * c->pairs, d_rgba + done * (size_t)c->pairs * c->R * 4);
+            e = sgx::launch_render(c, c->d_ws_mags.get(), m * c->pairs, d_rgba + done * (size_t)c->pairs * c->R * 4);
             return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_render_batch: render launch");
         });
         if (rc != SGX_OK) return rc;
@@ -831,13 +805,11 @@ int sgx_fbank_create(sgx_ctx *c, uint32_t n_filters, const uint32_t *h_first, co
     if (fb->h_weights.empty()) fb->h_weights.push_back(0.0f);
     hipError_t e = hipSetDevice(c->device);
     const size_t table_bytes = fb->h_filters.size() * sizeof(fb->h_filters[0]), weight_bytes = fb->h_weights.size() * sizeof(float);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&fb->d_filters), table_bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&fb->d_weights), weight_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(fb->d_filters, fb->h_filters.data(), table_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fb->d_weights, fb->h_weights.data(), weight_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = fb->d_filters.alloc(fb->h_filters.size());
+    if (e == hipSuccess) e = fb->d_weights.alloc(fb->h_weights.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(fb->d_filters.get(), fb->h_filters.data(), table_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fb->d_weights.get(), fb->h_weights.data(), weight_bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {
-        if (fb->d_filters) (void)hipFree(fb->d_filters);
-        if (fb->d_weights) (void)hipFree(fb->d_weights);
         delete fb;
         return fail_hip(c, e, "sgx_fbank_create: table upload");
     }
@@ -856,8 +828,6 @@ void sgx_fbank_destroy(void *bank)
         for (size_t i = 0; i < c->fbanks.size(); ++i)
             if (c->fbanks[i] == fb) { c->fbanks.erase(c->fbanks.begin() + (long)i); break; }
     }
-    if (fb->d_filters) (void)hipFree(fb->d_filters);
-    if (fb->d_weights) (void)hipFree(fb->d_weights);
     delete fb;
 }
 
@@ -902,7 +872,7 @@ int sgx_fbank_batch(void *bank, const float *d_pcm, size_t n_samples, size_t fir
         rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
             hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
             if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_batch: stft launch");
-            e = sgx::launch_fbank_stage(c, fb, c->d_ws_mags, m * c->pairs, d_out + done * (size_t)c->pairs * fb->n_filters * 2);
+            e = sgx::launch_fbank_stage(c, fb, c->d_ws_mags.get(), m * c->pairs, d_out + done * (size_t)c->pairs * fb->n_filters * 2);
             return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_fbank_batch: filter launch");
         });
         if (rc != SGX_OK) return rc;
@@ -953,7 +923,7 @@ int sgx_bands_peak_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_
     const size_t ws_unit = mags_bytes_per_frame(c);   // (ensure_workspace counts frames of magnitudes)
     rc = ensure_workspace(c, (ws_bytes + ws_unit - 1) / ws_unit);
     if (rc != SGX_OK) return rc;
-    float *ws_bands = c->d_ws_mags + chunk * (mags_bytes / sizeof(float)), *ws_sub = ws_bands + chunk * col;
+    float *ws_bands = c->d_ws_mags.get() + chunk * (mags_bytes / sizeof(float)), *ws_sub = ws_bands + chunk * col;
     for (size_t done = 0; done < n;) {
         const size_t j = done / g;                       // the column this chunk starts in: at its first frame unless g > chunk
         size_t m = n - done < chunk ? n - done : chunk;
@@ -1010,18 +980,18 @@ int sgx_magnitude_in(sgx_ctx *c, const float *d_mags, size_t n_columns, const fl
     if (!d_mags || !h_ranges || !d_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_magnitude_in: null buffer");
     SGX_HIP(c, hipSetDevice(c->device));
     const std::vector<float> key(h_ranges, h_ranges + (size_t)n_ranges * 2);
-    if (key != c->bands_key || !c->d_band_rows) {
+    if (key != c->bands_key || !c->d_band_rows.get()) {
         std::vector<float> f0(n_ranges), f1(n_ranges);
         for (uint32_t i = 0; i < n_ranges; ++i) { f0[i] = h_ranges[2 * i]; f1[i] = h_ranges[2 * i + 1]; }
         std::vector<sgx::RowEntry> rows;
         std::vector<sgx::SampleEntry> samples;
         sgx::build_range_tables(c->W, c->sr_u32, c->cfg.interp, f0.data(), f1.data(), n_ranges, rows, samples);
         SGX_HIP(c, hipStreamSynchronize(c->stream));  // the previous range set may still be in use
-        SGX_HIP(c, upload(&c->d_band_rows, rows.data(), rows.size()));
-        SGX_HIP(c, upload(&c->d_band_samples, samples.data(), samples.size()));
+        SGX_HIP(c, c->d_band_rows.upload(rows));
+        SGX_HIP(c, c->d_band_samples.upload(samples));
         c->bands_key = key;
     }
-    hipError_t e = sgx::launch_magnitude_in(c, d_mags, n_columns, c->d_band_rows, c->d_band_samples, n_ranges, d_out);
+    hipError_t e = sgx::launch_magnitude_in(c, d_mags, n_columns, c->d_band_rows.get(), c->d_band_samples.get(), n_ranges, d_out);
     if (e != hipSuccess) return fail_hip(c, e, "sgx_magnitude_in: kernel launch");
     return SGX_OK;
 }
@@ -1151,14 +1121,14 @@ int sgx_checksum(sgx_ctx *c, const void *d_buf, size_t n_bytes, uint64_t base_wo
     if (!c || !h_out) return SGX_ERR_INVALID_ARG;
     if (n_bytes % 4) return fail(c, SGX_ERR_INVALID_ARG, "sgx_checksum: size must be a multiple of 4");
     SGX_HIP(c, hipSetDevice(c->device));
-    SGX_HIP(c, hipMemsetAsync(c->d_cksum, 0, sizeof(unsigned long long), c->stream));
+    SGX_HIP(c, hipMemsetAsync(c->d_cksum.get(), 0, sizeof(unsigned long long), c->stream));
     if (n_bytes) {
         if (!d_buf) return fail(c, SGX_ERR_INVALID_ARG, "sgx_checksum: null buffer");
-        hipError_t e = sgx::launch_checksum(c, static_cast<const uint32_t *>(d_buf), n_bytes / 4, base_word, c->d_cksum);
+        hipError_t e = sgx::launch_checksum(c, static_cast<const uint32_t *>(d_buf), n_bytes / 4, base_word, c->d_cksum.get());
         if (e != hipSuccess) return fail_hip(c, e, "sgx_checksum: kernel launch");
     }
     unsigned long long v = 0;
-    SGX_HIP(c, hipMemcpyAsync(&v, c->d_cksum, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    SGX_HIP(c, hipMemcpyAsync(&v, c->d_cksum.get(), sizeof(v), hipMemcpyDeviceToHost, c->stream));
     SGX_HIP(c, hipStreamSynchronize(c->stream));
     *h_out = v;
     return SGX_OK;

@@ -36,8 +36,8 @@ hipError_t launch_fbank_stage(const sgx_ctx *c, const sgx_fbank *fb, const float
     if (n_columns == 0) return hipSuccess;
     FbankStageParams p;
     p.mags = d_mags;
-    p.filters = fb->d_filters;
-    p.weights = fb->d_weights;
+    p.filters = fb->d_filters.get();
+    p.weights = fb->d_weights.get();
     p.out = d_out;
     p.M = c->M;
     p.n_filters = fb->n_filters;

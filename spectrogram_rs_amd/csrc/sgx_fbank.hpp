@@ -17,8 +17,8 @@ struct sgx_fbank {
     sgx_ctx *ctx = nullptr;
     uint32_t n_filters = 0, power = 1;
     size_t n_weights = 0;
-    sgx::fbank::Filter *d_filters = nullptr;   // [n_filters]
-    float *d_weights = nullptr;                // [n_weights] (one word where the bank has none)
+    sgx::DeviceBuffer<sgx::fbank::Filter> d_filters;   // [n_filters]
+    sgx::DeviceBuffer<float> d_weights;                // [n_weights] (one word where the bank has none)
     std::vector<sgx::fbank::Filter> h_filters;   // what the asynchronous uploads read: the caller's arrays are the caller's again when
     std::vector<float> h_weights;                // sgx_fbank_create returns
 };

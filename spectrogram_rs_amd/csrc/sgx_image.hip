@@ -17,7 +17,7 @@ struct sgx_image {
     sgx_ctx *ctx = nullptr;
     uint32_t width = 0, height = 0;   // height = the context's rows R (one column = one frame)
     uint32_t offset = 0;              // simple_spectrogram.rs:164
-    uchar4 *d_pixels = nullptr;       // [height][width] RGBA, rowstride 4 * width (gdk-pixbuf's layout for this size)
+    sgx::DeviceBuffer<uchar4> d_pixels;   // [height][width] RGBA, rowstride 4 * width (gdk-pixbuf's layout for this size)
 };
 
 namespace sgx {
@@ -94,8 +94,8 @@ int sgx_image_create(sgx_ctx *c, uint32_t width, sgx_image **out)
     im->height = c->R;
     const size_t bytes = (size_t)im->width * im->height * sizeof(uchar4);
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&im->d_pixels), bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(im->d_pixels, 0, bytes, c->stream);
+    if (e == hipSuccess) e = im->d_pixels.alloc((size_t)im->width * im->height);
+    if (e == hipSuccess) e = hipMemsetAsync(im->d_pixels.get(), 0, bytes, c->stream);
     if (e != hipSuccess) {
         const int rc = image_fail_hip(im, e, "sgx_image_create");
         sgx_image_destroy(im);
@@ -116,7 +116,6 @@ void sgx_image_destroy(sgx_image *im)
         for (size_t i = 0; i < v.size(); ++i)
             if (v[i] == im) { v.erase(v.begin() + (long)i); break; }
     }
-    if (im->d_pixels) (void)hipFree(im->d_pixels);
     delete im;
 }
 
@@ -134,7 +133,7 @@ int sgx_image_write_columns(sgx_image *im, const uint8_t *d_rgba, size_t n_colum
     if (n) {
         const dim3 grid((n + 31) / 32, (im->height + 31) / 32);
         hipLaunchKernelGGL(sgx::image_scatter_kernel, grid, dim3(256), 0, c->stream,
-                           reinterpret_cast<const uchar4 *>(d_rgba) + first * im->height, im->d_pixels, n, im->width, im->height, x_first);
+                           reinterpret_cast<const uchar4 *>(d_rgba) + first * im->height, im->d_pixels.get(), n, im->width, im->height, x_first);
         IMAGE_HIP(im, hipGetLastError());
     }
     im->offset = (uint32_t)((im->offset + n_columns) % im->width);
@@ -153,15 +152,15 @@ int sgx_image_read(sgx_image *im, int scrolled, uint8_t *d_out)
     if (!d_out) return image_fail(im, SGX_ERR_INVALID_ARG, "sgx_image_read: null buffer");
     IMAGE_HIP(im, hipSetDevice(c->device));
     if (!scrolled || im->offset == 0) {
-        IMAGE_HIP(im, hipMemcpyAsync(d_out, im->d_pixels, (size_t)im->width * im->height * sizeof(uchar4), hipMemcpyDeviceToDevice, c->stream));
+        IMAGE_HIP(im, hipMemcpyAsync(d_out, im->d_pixels.get(), (size_t)im->width * im->height * sizeof(uchar4), hipMemcpyDeviceToDevice, c->stream));
     } else {
         hipLaunchKernelGGL(sgx::image_scrolled_kernel, dim3((im->width + 255) / 256, im->height < 65535u ? im->height : 65535u), dim3(256), 0, c->stream,
-                           im->d_pixels, reinterpret_cast<uchar4 *>(d_out), im->width, im->height, im->offset);
+                           im->d_pixels.get(), reinterpret_cast<uchar4 *>(d_out), im->width, im->height, im->offset);
         IMAGE_HIP(im, hipGetLastError());
     }
     return SGX_OK;
 }
 
-const uint8_t *sgx_image_pixels(const sgx_image *im) { return im ? reinterpret_cast<const uint8_t *>(im->d_pixels) : nullptr; }
+const uint8_t *sgx_image_pixels(const sgx_image *im) { return im ? reinterpret_cast<const uint8_t *>(im->d_pixels.get()) : nullptr; }
 
 }  // extern "C"

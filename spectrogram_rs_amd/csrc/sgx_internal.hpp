@@ -5,10 +5,13 @@
 
 #include <cstdint>
 #include <array>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/sgx.h"
+#include "device_buffer.hpp"
+#include "unit_root.hpp"
 
 namespace sgx {
 
@@ -97,6 +100,32 @@ float bounded_db_host(float min_db, float max_db, float power);
 // tuned 16384 (32 x 32 x 16: stft16384_w.hip), multi-pass (stft_large.hip).  Retired numbers: docs/history/stft_kernel_numbers.md
 enum StftKernel : int { kKernelGeneric = 0, kKernelWg4096 = 2, kKernelChirp = 4, kKernelMixed = 6, kKernelW4800 = 9, kKernelW16384 = 10, kKernelLarge = 11 };
 
+// The table structs of the transform families, each defined in its family's translation unit (or the header its units share).  The
+// context owns one of each that it runs; `delete t` is defined where the type is complete.
+namespace wg { struct WgTables; }
+namespace wgr { struct RealTables; }
+namespace mix { struct MixTables; struct ChirpTables; }
+namespace w48 { struct W48Tables; }
+namespace blu { struct BluTables; }
+namespace w16k { struct TablesW; }
+namespace large { struct LargeTables; }
+namespace istft { struct ITables; }
+struct TablesDelete {
+    void operator()(wg::WgTables *t) const;       // stft4096_wg.hip
+    void operator()(wgr::RealTables *t) const;    // stft4096_real.hip
+    void operator()(mix::MixTables *t) const;     // stft_mixed.hip
+    void operator()(mix::ChirpTables *t) const;   // stft_mixed.hip
+    void operator()(w48::W48Tables *t) const;     // stft4800_wg.hip
+    void operator()(blu::BluTables *t) const;     // stft_bluestein.hip
+    void operator()(w16k::TablesW *t) const;      // stft16384_w.hip
+    void operator()(large::LargeTables *t) const; // stft_large.hip
+    void operator()(istft::ITables *t) const;     // stft_istft.hip
+};
+template <typename T> using TablesPtr = std::unique_ptr<T, TablesDelete>;
+
+// unit_root (unit_root.hpp) as the float2 the twiddle tables hold
+inline float2 unit_root2(unsigned long long e, unsigned long long n) { const UnitRoot w = unit_root(e, n); return make_float2(w.re, w.im); }
+
 }  // namespace sgx
 
 struct sgx_ctx {
@@ -111,37 +140,37 @@ struct sgx_ctx {
     sgx::Palette pal;
 
     // device tables
-    float *d_window = nullptr;
-    float2 *d_twiddle = nullptr;
-    sgx::RowEntry *d_rows = nullptr;
-    sgx::SampleEntry *d_samples = nullptr;
-    float *d_lut_thr = nullptr;    // [n-1]
-    float *d_alpha_thr = nullptr;  // [255]
-    uchar4 *d_lut_rgba = nullptr;  // [n]
-    uint2 *d_pal_seed = nullptr;   // [256] {threshold to leave level i (NaN for 255), RGBA of level i}: 256-level palettes, mono branch
-    double *d_t_thr = nullptr;     // [n-1], segment palettes with a diverging scheme only
-    uint16_t *d_t_cell = nullptr;  // [kTCells + 1] (or null)
-    void *d_fast_wg = nullptr;     // tables of the workgroup-per-transform kernel
-    void *d_blu = nullptr;         // tables of the Bluestein (non-power-of-two) kernel
-    void *d_mix = nullptr;         // tables of the mixed-radix (2, 3, 5, 7-smooth lengths) kernel
-    void *d_w4800 = nullptr;       // tables of the tuned 4800-point kernel (W = 2400: the application's window at 48 kHz)
-    void *d_real = nullptr;        // tables of the real-input 4096-point kernel (independent mono frames at W 2048 / H 256)
-    void *d_chz = nullptr;         // chirp-z through the mixed-radix kernel's stages (or null: the radix-4 ladder of stft_bluestein.hip)
-    void *d_w16k = nullptr;        // tables of the 16384-point kernel, 32 x 32 x 16 (stft16384_w.hip)
-    void *d_large = nullptr;       // plan, tables and scratch of the multi-pass transform (stft_large.hip)
-    void *d_istft = nullptr;       // tables of the inverse STFT (stft_istft.hip): built by the first sgx_istft_batch, not by sgx_create
+    sgx::DeviceBuffer<float> d_window;
+    sgx::DeviceBuffer<float2> d_twiddle;
+    sgx::DeviceBuffer<sgx::RowEntry> d_rows;
+    sgx::DeviceBuffer<sgx::SampleEntry> d_samples;
+    sgx::DeviceBuffer<float> d_lut_thr;    // [n-1]
+    sgx::DeviceBuffer<float> d_alpha_thr;  // [255]
+    sgx::DeviceBuffer<uchar4> d_lut_rgba;  // [n]
+    sgx::DeviceBuffer<uint2> d_pal_seed;   // [256] {threshold to leave level i (NaN for 255), RGBA of level i}: 256-level palettes, mono branch (else null)
+    sgx::DeviceBuffer<double> d_t_thr;     // [n-1], segment palettes with a diverging scheme only
+    sgx::DeviceBuffer<uint16_t> d_t_cell;  // [kTCells + 1] (or null)
+    // Each family's tables and scratch, or null where the context does not run the family.  The context's constness does not reach through
+    // these pointers: a family's scratch is working storage, which a launch on a `const sgx_ctx *` may regrow (DeviceBuffer::grow).
+    sgx::TablesPtr<sgx::wg::WgTables> wg;         // the workgroup-per-transform 4096-point kernel
+    sgx::TablesPtr<sgx::blu::BluTables> blu;      // the Bluestein (non-power-of-two) kernel
+    sgx::TablesPtr<sgx::mix::MixTables> mix;      // the mixed-radix (2, 3, 5, 7-smooth lengths) kernel
+    sgx::TablesPtr<sgx::w48::W48Tables> w4800;    // the tuned 4800-point kernel (W = 2400: the application's window at 48 kHz)
+    sgx::TablesPtr<sgx::wgr::RealTables> real;    // the real-input 4096-point kernel (independent mono frames at W 2048 / H 256)
+    sgx::TablesPtr<sgx::mix::ChirpTables> chz;    // chirp-z through the mixed-radix kernel's stages (or null: the radix-4 ladder of stft_bluestein.hip)
+    sgx::TablesPtr<sgx::w16k::TablesW> w16k;      // the 16384-point kernel, 32 x 32 x 16 (stft16384_w.hip)
+    sgx::TablesPtr<sgx::large::LargeTables> large;   // plan, tables and scratch of the multi-pass transform (stft_large.hip)
+    sgx::TablesPtr<sgx::istft::ITables> istft;    // the inverse STFT (stft_istft.hip): built by the first sgx_istft_batch, not by sgx_create
 
     // workspaces (grown on demand, kept)
-    float *d_ws_mags = nullptr;
-    size_t ws_frames = 0;
-    float *d_one_in = nullptr, *d_one_out = nullptr;
-    unsigned long long *d_cksum = nullptr;
+    sgx::DeviceBuffer<float> d_ws_mags;   // whole frames of magnitudes (ensure_workspace)
+    sgx::DeviceBuffer<float> d_one_in, d_one_out;
+    sgx::DeviceBuffer<unsigned long long> d_cksum;
     // cached tables of the last sgx_magnitude_in range set
     std::vector<float> bands_key;
-    sgx::RowEntry *d_band_rows = nullptr;
-    sgx::SampleEntry *d_band_samples = nullptr;
-    float *d_levels = nullptr;  // sgx_spectrum_levels: the bands' (l, r) means, grown on demand
-    uint32_t levels_cap = 0;
+    sgx::DeviceBuffer<sgx::RowEntry> d_band_rows;
+    sgx::DeviceBuffer<sgx::SampleEntry> d_band_samples;
+    sgx::DeviceBuffer<float> d_levels;  // sgx_spectrum_levels: the bands' (l, r) means, [n_bars][2], grown on demand
 
     unsigned long long palette_gen = 0;  // bumped by every palette upload (sgx_view rebuilds its palette texture on a change)
 
@@ -157,6 +186,8 @@ struct sgx_ctx {
     std::vector<struct sgx_fbank *> fbanks;   // sgx_fbank.hpp: the filterbanks created on this context
 
     std::string err;
+
+    ~sgx_ctx();   // sgx_api.hip: frees every buffer above.  sgx_destroy has set the device and waited for the stream.
 };
 
 namespace sgx {
@@ -179,8 +210,8 @@ struct StftCall {
     size_t peak_group;
     const struct sgx_fbank *bank = nullptr;
 };
-// Each launcher takes its tables from the context, returns hipSuccess or the launch error, and hipErrorInvalidValue for an Out (or a
-// channel count) its family has no kernel for.
+// Each X_init builds its family's tables into the context; on an error it leaves nothing behind.  Each launcher takes its tables from the
+// context, returns hipSuccess or the launch error, and hipErrorInvalidValue for an Out (or a channel count) its family has no kernel for.
 hipError_t launch_generic(const sgx_ctx *c, const StftCall &call);     // sgx_kernels.hip: kMags, kComplex
 hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call);      // stft4096_wg.hip (and stft4096_real.hip): every Out (kFbank: where wg4096_can_fuse_fbank)
 hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call);      // stft16384_w.hip: kMags, kComplex
@@ -208,27 +239,11 @@ inline RunSplit run_split(const sgx_ctx *c, unsigned long long n_jobs, unsigned 
     const unsigned long long blocks = (unsigned long long)c->n_cu * per_cu, per = (n_jobs + blocks - 1) / blocks;
     return runs_of(n_jobs, per < 1 ? 1 : per);
 }
-// A device buffer that launches on `stream` may still use grows to `want` units (`bytes` bytes): wait for the stream, free, allocate, record
-// the size.  A failed allocation leaves the buffer null and its size 0.
-template <typename T>
-hipError_t grow(hipStream_t stream, T *&buf, size_t &have, size_t want, size_t bytes)
-{
-    if (want <= have) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return e;
-    if (buf) { (void)hipFree(buf); buf = nullptr; have = 0; }
-    e = hipMalloc(reinterpret_cast<void **>(&buf), bytes);
-    if (e != hipSuccess) return e;
-    have = want;
-    return hipSuccess;
-}
-
 inline bool fast4096_supported(const sgx_ctx *c) { return c->W == 2048; }   // the tuned 4096-point kernels (stft4096_wg.hip)
-hipError_t wg4096_init(sgx_ctx *c, void **out);
-void wg4096_destroy(void *tables);
-bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables);
-bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables);   // the fused column without the colour (sgx_bands_batch): no palette condition
-bool wg4096_can_fuse_peak(const sgx_ctx *c, const void *tables);    // sgx_bands_peak_batch in one kernel (plus the combine pass)
+hipError_t wg4096_init(sgx_ctx *c);
+bool wg4096_can_fuse_render(const sgx_ctx *c);
+bool wg4096_can_fuse_bands(const sgx_ctx *c);   // the fused column without the colour (sgx_bands_batch): no palette condition
+bool wg4096_can_fuse_peak(const sgx_ctx *c);    // sgx_bands_peak_batch in one kernel (plus the combine pass)
 hipError_t launch_deinterleave_pairs(const sgx_ctx *c, const float *d_pcm, float *d_planes, size_t plane_floats, size_t first_sample, size_t n_samples,
                                      uint32_t channels, uint32_t pairs);   // deinterleave.hip
 bool wg4096_seed_is_within_one(const sgx_ctx *c);
@@ -236,44 +251,36 @@ void lut_seed_coefficients(const sgx_ctx *c, float &a, float &b);
 namespace wg { bool seed_within_one(const std::vector<float> &thr, double guess_a, double guess_b); }   // stft4096_wg.hip: is floor(log2(p + 1e-7) a + b) within one of the threshold count for every power?   // LUT level ~ floor(log2(power + 1e-7) a + b): the seed of the threshold count
 // stft16384_w.hip: W = 8192 as 32 x 32 x 16 in one 512-thread workgroup, 32 points per thread
 bool w16384_supported(const sgx_ctx *c);
-hipError_t w16384_init(sgx_ctx *c, void **out);
-void w16384_destroy(void *tables);
+hipError_t w16384_init(sgx_ctx *c);
 // stft4096_real.hip: independent mono frames at W 2048 / H 256 as 2048-point complex transforms of the real frame
-hipError_t real4096_init(sgx_ctx *c, void **out);
-void real4096_destroy(void *tables);
+hipError_t real4096_init(sgx_ctx *c);
 bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels);   // (launched from stft4096_wg.hip: launch_wg4096)
 // W = 2400 (48 kHz x 0.05 s): persistent 320-thread workgroups, 16 x 20 x 15 (stft4800_wg.hip); rows and half rows of one or two channels -- more
 // channels and the fused PCM-to-pixel path go to the composite-radix kernel, whose tables such a context carries too
 bool w4800_supported(const sgx_ctx *c);
-hipError_t w4800_init(sgx_ctx *c, void **out);
-void w4800_destroy(void *tables);
+hipError_t w4800_init(sgx_ctx *c);
 bool mixed_supported(uint32_t W);
-hipError_t mixed_init(sgx_ctx *c, void **out);
-hipError_t mixed_length_tables(uint32_t n, void **out);   // the stage plan and tables of an n-point transform alone (mixed_destroy frees them)
-void mixed_destroy(void *tables);
-uint32_t mixed_fixed_plan(const void *tables);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
-bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode: a mono stream, every frame its own W-point transform
+hipError_t mixed_init(sgx_ctx *c);
+hipError_t mixed_length_tables(uint32_t n, TablesPtr<mix::MixTables> &out);   // the stage plan and tables of an n-point transform alone, for a caller that keeps them itself (stft_istft.hip)
+uint32_t mixed_fixed_plan(const sgx_ctx *c);   // the length whose compile-time plan serves this context, or 0 (run-time geometry)
+bool mixed_real_serves(const sgx_ctx *c, uint32_t channels);   // real-input mode: a mono stream, every frame its own W-point transform
 // chirp-z through the composite stages of the mixed-radix kernel (stft_mixed_kernels.hpp): L = 512 .. 16384, i.e. W = 86 .. 5461
 bool chirpz_supported(uint32_t W);
-hipError_t chirpz_init(sgx_ctx *c, void **out);
-void chirpz_destroy(void *tables);
-bool chirpz_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels);   // real-input mode, as mixed_real_serves
-bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables);   // one kernel from PCM to pixels at this length, palette and row table
-bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables);    // one kernel from PCM to the rows' (l, r) means at this length and row table
+hipError_t chirpz_init(sgx_ctx *c);
+bool chirpz_real_serves(const sgx_ctx *c, uint32_t channels);   // real-input mode, as mixed_real_serves
+bool mixed_can_fuse_render(const sgx_ctx *c);   // one kernel from PCM to pixels at this length, palette and row table
+bool mixed_can_fuse_bands(const sgx_ctx *c);    // one kernel from PCM to the rows' (l, r) means at this length and row table
 bool bluestein_supported(uint32_t W);
-hipError_t bluestein_init(sgx_ctx *c, void **out);
-void bluestein_destroy(void *tables);
+hipError_t bluestein_init(sgx_ctx *c);
 // stft_large.hip: lengths no in-LDS kernel serves (SGX_FLAG_LARGE_TRANSFORM), W up to 2^20: four-step passes through a scratch the
 // context holds (allocated here, at create time), direct for a 2-3-5-7-smooth 2W, chirp-z otherwise
 bool large_supported(uint32_t W);
-hipError_t large_init(sgx_ctx *c, void **out);
-void large_destroy(void *tables);
+hipError_t large_init(sgx_ctx *c);
 // stft_istft.hip: the inverse of sgx_stft_batch_complex by weighted overlap-add; route 1 = the composite stages of 2W points,
 // 2 = chirp-z through a power-of-two plan, 0 = none (the lengths only kernel 11 serves)
 int istft_route(const sgx_ctx *c);
-hipError_t istft_init(sgx_ctx *c, void **out);
-void istft_destroy(void *tables);
-hipError_t launch_istft(const sgx_ctx *c, const void *tables, const float *d_spec, size_t n_frames, size_t s0, size_t s1, float *d_pcm);
+hipError_t istft_init(sgx_ctx *c);
+hipError_t launch_istft(const sgx_ctx *c, const float *d_spec, size_t n_frames, size_t s0, size_t s1, float *d_pcm);
 hipError_t launch_to_half(const sgx_ctx *c, const float *d_in, void *d_out, size_t n_pairs);
 hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns, uint8_t *d_rgba);
 hipError_t launch_magnitude_in(const sgx_ctx *c, const float *d_mags, size_t n_columns, const RowEntry *d_rows,

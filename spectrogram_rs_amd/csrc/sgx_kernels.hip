@@ -189,8 +189,8 @@ hipError_t launch_generic(const sgx_ctx *c, const StftCall &call)
     if (n_frames == 0) return hipSuccess;
     StftGenericParams p{};
     p.pcm = d_pcm;
-    p.window = c->d_window;
-    p.twiddle = c->d_twiddle;
+    p.window = c->d_window.get();
+    p.twiddle = c->d_twiddle.get();
     p.mags = d_mags;
     p.first_frame = first_frame;
     p.W = c->W;
@@ -671,11 +671,11 @@ hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns
     if (n_columns == 0) return hipSuccess;
     RenderParams p;
     p.mags = d_mags;
-    p.rows = c->d_rows;
-    p.samples = c->d_samples;
-    p.lut_thr = c->d_lut_thr;
-    p.alpha_thr = c->d_alpha_thr;
-    p.lut_rgba = c->d_lut_rgba;
+    p.rows = c->d_rows.get();
+    p.samples = c->d_samples.get();
+    p.lut_thr = c->d_lut_thr.get();
+    p.alpha_thr = c->d_alpha_thr.get();
+    p.lut_rgba = c->d_lut_rgba.get();
     p.rgba = d_rgba;
     p.M = c->M;
     p.R = c->R;
@@ -683,8 +683,8 @@ hipError_t launch_render(const sgx_ctx *c, const float *d_mags, size_t n_columns
     p.interp = c->cfg.interp;
     p.stereo = (uint32_t)c->pal.stereo;
     p.lut_mode = c->cfg.lut_index_mode;
-    p.t_thr = c->d_t_thr;
-    p.t_cell = (c->pal.segments && c->pal.stereo && !(c->cfg.flags & SGX_FLAG_LUT_WALK)) ? c->d_t_cell : nullptr;
+    p.t_thr = c->d_t_thr.get();
+    p.t_cell = (c->pal.segments && c->pal.stereo && !(c->cfg.flags & SGX_FLAG_LUT_WALK)) ? c->d_t_cell.get() : nullptr;
     p.segments = c->pal.segments ? 1u : 0u;
     p.nan_rgba = make_uchar4(c->pal.nan_rgb[0], c->pal.nan_rgb[1], c->pal.nan_rgb[2], 255);
     const size_t n_samples = c->tab.samples.size();
@@ -966,9 +966,9 @@ hipError_t launch_render_bands(const sgx_ctx *c, const float *d_bands, size_t n_
     p.mags = d_bands;
     p.rows = nullptr;
     p.samples = nullptr;
-    p.lut_thr = c->d_lut_thr;
-    p.alpha_thr = c->d_alpha_thr;
-    p.lut_rgba = c->d_lut_rgba;
+    p.lut_thr = c->d_lut_thr.get();
+    p.alpha_thr = c->d_alpha_thr.get();
+    p.lut_rgba = c->d_lut_rgba.get();
     p.rgba = d_rgba;
     p.M = c->M;
     p.R = c->R;
@@ -976,8 +976,8 @@ hipError_t launch_render_bands(const sgx_ctx *c, const float *d_bands, size_t n_
     p.interp = c->cfg.interp;
     p.stereo = (uint32_t)c->pal.stereo;
     p.lut_mode = c->cfg.lut_index_mode;
-    p.t_thr = c->d_t_thr;
-    p.t_cell = (c->pal.segments && c->pal.stereo && !(c->cfg.flags & SGX_FLAG_LUT_WALK)) ? c->d_t_cell : nullptr;
+    p.t_thr = c->d_t_thr.get();
+    p.t_cell = (c->pal.segments && c->pal.stereo && !(c->cfg.flags & SGX_FLAG_LUT_WALK)) ? c->d_t_cell.get() : nullptr;
     p.segments = c->pal.segments ? 1u : 0u;
     p.nan_rgba = make_uchar4(c->pal.nan_rgb[0], c->pal.nan_rgb[1], c->pal.nan_rgb[2], 255);
     p.guess_a = p.guess_b = 0.0f;

@@ -26,10 +26,9 @@ struct sgx_live {
     size_t capacity = 0;
     uint32_t flags = 0;
     float2 *h_ring = nullptr;        // pinned, [capacity]
-    float2 *d_cur = nullptr;         // [capacity] device image of the ring's unconsumed head
-    float2 *d_alt = nullptr;         // [capacity] compaction target (ping-pong)
-    void *d_out = nullptr;           // results of one tick
-    size_t out_bytes = 0;
+    sgx::DeviceBuffer<float2> d_cur;         // [capacity] device image of the ring's unconsumed head
+    sgx::DeviceBuffer<float2> d_alt;         // [capacity] compaction target (ping-pong)
+    sgx::DeviceBuffer<unsigned char> d_out;  // results of one tick, grown on demand
     sgx::LiveRingState ring;         // positions and the lock-free producer / consumer protocol (live_ring.hpp: host only, sanitizer-tested)
 };
 
@@ -78,8 +77,8 @@ int sgx_live_create(sgx_ctx *c, size_t capacity_pairs, uint32_t flags, sgx_live 
     l->flags = flags;
     hipError_t e = hipSetDevice(c->device);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&l->h_ring), capacity_pairs * sizeof(float2), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&l->d_cur), capacity_pairs * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&l->d_alt), capacity_pairs * sizeof(float2));
+    if (e == hipSuccess) e = l->d_cur.alloc(capacity_pairs);
+    if (e == hipSuccess) e = l->d_alt.alloc(capacity_pairs);
     if (e != hipSuccess) {
         const int rc = live_fail_hip(l, e, "sgx_live_create: allocation");
         sgx_live_destroy(l);
@@ -98,10 +97,7 @@ void sgx_live_destroy(sgx_live *l)
         (void)hipSetDevice(l->ctx->device);
         (void)hipStreamSynchronize(l->ctx->stream);
     }
-    if (l->h_ring) (void)hipHostFree(l->h_ring);
-    if (l->d_cur) (void)hipFree(l->d_cur);
-    if (l->d_alt) (void)hipFree(l->d_alt);
-    if (l->d_out) (void)hipFree(l->d_out);
+    if (l->h_ring) (void)hipHostFree(l->h_ring);   // (pinned host memory: the one allocation here that is no DeviceBuffer)
     delete l;
 }
 
@@ -162,7 +158,7 @@ static int live_tick(sgx_live *l, int what, void *h_out, sgx_view *view, sgx_ima
     // the samples that arrived since the last tick
     const sgx::LiveRingState::Upload up = l->ring.begin_tick();
     if (up.first) {
-        float2 *dst = l->d_cur + up.dst;
+        float2 *dst = l->d_cur.get() + up.dst;
         LIVE_HIP(l, hipMemcpyAsync(dst, l->h_ring + up.slot, up.first * sizeof(float2), hipMemcpyHostToDevice, c->stream));
         if (up.second)
             LIVE_HIP(l, hipMemcpyAsync(dst + up.first, l->h_ring, up.second * sizeof(float2), hipMemcpyHostToDevice, c->stream));
@@ -176,30 +172,26 @@ static int live_tick(sgx_live *l, int what, void *h_out, sgx_view *view, sgx_ima
     if (frames) {
         if (!h_out && !view && !image) return live_fail(l, SGX_ERR_INVALID_ARG, "sgx_live_tick: null output buffer");
         const size_t need = frames * frame_bytes;
-        if (need > l->out_bytes) {
-            LIVE_HIP(l, hipStreamSynchronize(c->stream));
-            if (l->d_out) { (void)hipFree(l->d_out); l->d_out = nullptr; l->out_bytes = 0; }
-            LIVE_HIP(l, hipMalloc(&l->d_out, need));
-            l->out_bytes = need;
-        }
+        LIVE_HIP(l, l->d_out.grow(c->stream, need));
+        void *d_out = l->d_out.get();
         const size_t n_samples = (frames - 1) * (size_t)c->H + c->W;
-        const float *pcm = reinterpret_cast<const float *>(l->d_cur);
+        const float *pcm = reinterpret_cast<const float *>(l->d_cur.get());
         size_t got = 0;
         int rc;
-        if (what == SGX_LIVE_MAGS) rc = sgx_stft_batch(c, pcm, n_samples, 0, frames, static_cast<float *>(l->d_out), &got);
-        else if (what == SGX_LIVE_MAGS_F16) rc = sgx_stft_batch_f16(c, pcm, n_samples, 0, frames, l->d_out, &got);
-        else if (what == SGX_LIVE_BANDS) rc = sgx_bands_batch(c, pcm, n_samples, 0, frames, static_cast<float *>(l->d_out), &got);
-        else rc = sgx_render_batch(c, pcm, n_samples, 0, frames, static_cast<uint8_t *>(l->d_out), &got);
+        if (what == SGX_LIVE_MAGS) rc = sgx_stft_batch(c, pcm, n_samples, 0, frames, static_cast<float *>(d_out), &got);
+        else if (what == SGX_LIVE_MAGS_F16) rc = sgx_stft_batch_f16(c, pcm, n_samples, 0, frames, d_out, &got);
+        else if (what == SGX_LIVE_BANDS) rc = sgx_bands_batch(c, pcm, n_samples, 0, frames, static_cast<float *>(d_out), &got);
+        else rc = sgx_render_batch(c, pcm, n_samples, 0, frames, static_cast<uint8_t *>(d_out), &got);
         if (rc != SGX_OK) return rc;
         if (got != frames) return live_fail(l, SGX_ERR_INVALID_ARG, "sgx_live_tick: frame count mismatch");
         if (view) {
-            rc = sgx_view_write_rows(view, l->d_out, frames, nullptr);
+            rc = sgx_view_write_rows(view, d_out, frames, nullptr);
             if (rc != SGX_OK) return rc;
         } else if (image) {
-            rc = sgx_image_write_columns(image, static_cast<const uint8_t *>(l->d_out), frames, nullptr);
+            rc = sgx_image_write_columns(image, static_cast<const uint8_t *>(d_out), frames, nullptr);
             if (rc != SGX_OK) return rc;
         } else {
-            LIVE_HIP(l, hipMemcpyAsync(h_out, l->d_out, need, hipMemcpyDeviceToHost, c->stream));
+            LIVE_HIP(l, hipMemcpyAsync(h_out, d_out, need, hipMemcpyDeviceToHost, c->stream));
         }
     }
 
@@ -207,10 +199,8 @@ static int live_tick(sgx_live *l, int what, void *h_out, sgx_view *view, sgx_ima
     const size_t skip = sgx::LiveRingState::skip_of(frames, c->H, (l->flags & SGX_LIVE_REFERENCE_SKIP) != 0, truncated, occupied);
     const size_t keep = occupied - skip;
     if (skip && keep) {
-        LIVE_HIP(l, hipMemcpyAsync(l->d_alt, l->d_cur + skip, keep * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
-        float2 *t = l->d_cur;
-        l->d_cur = l->d_alt;
-        l->d_alt = t;
+        LIVE_HIP(l, hipMemcpyAsync(l->d_alt.get(), l->d_cur.get() + skip, keep * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
+        std::swap(l->d_cur, l->d_alt);
     }
     // the pinned slots just uploaded are reusable only once the copies above have run
     LIVE_HIP(l, hipStreamSynchronize(c->stream));
@@ -243,20 +233,15 @@ int sgx_spectrum_levels(sgx_ctx *c, const float *d_column, uint32_t n_bars, doub
         prev = next;
     }
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess && n_bars > c->levels_cap) {
-        e = hipStreamSynchronize(c->stream);
-        if (c->d_levels) { (void)hipFree(c->d_levels); c->d_levels = nullptr; c->levels_cap = 0; }
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_levels), (size_t)n_bars * 2 * sizeof(float));
-        if (e == hipSuccess) c->levels_cap = n_bars;
-    }
+    if (e == hipSuccess) e = c->d_levels.grow(c->stream, (size_t)n_bars * 2);
     if (e != hipSuccess) {
         c->err = std::string("sgx_spectrum_levels: ") + hipGetErrorString(e);
         return SGX_ERR_HIP;
     }
-    int rc = sgx_magnitude_in(c, d_column, 1, ranges.data(), n_bars, c->d_levels);
+    int rc = sgx_magnitude_in(c, d_column, 1, ranges.data(), n_bars, c->d_levels.get());
     if (rc != SGX_OK) return rc;
     std::vector<float> lr((size_t)n_bars * 2);
-    e = hipMemcpyAsync(lr.data(), c->d_levels, lr.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    e = hipMemcpyAsync(lr.data(), c->d_levels.get(), lr.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         c->err = std::string("sgx_spectrum_levels: ") + hipGetErrorString(e);

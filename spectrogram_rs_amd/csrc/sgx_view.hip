@@ -23,8 +23,8 @@ struct sgx_view {
     sgx_ctx *ctx = nullptr;
     uint32_t rows = 0;           // VIEWPORT_FRAMES (texture height)
     uint32_t offset = 0;         // gpu_spectrogram.rs:67,274
-    __half2 *d_ring = nullptr;   // [rows][M] (l, r) half pairs
-    float4 *d_palette = nullptr; // [32][32] RGBA32F: texel (x = j, y = i) = lookup_table(32)[i][j]
+    sgx::DeviceBuffer<__half2> d_ring;   // [rows][M] (l, r) half pairs
+    sgx::DeviceBuffer<float4> d_palette; // [32][32] RGBA32F: texel (x = j, y = i) = lookup_table(32)[i][j]
     unsigned long long palette_gen = ~0ull;
 };
 
@@ -134,9 +134,9 @@ int sgx_view_create(sgx_ctx *c, uint32_t viewport_frames, sgx_view **out)
     v->ctx = c;
     v->rows = viewport_frames;
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&v->d_ring), (size_t)v->rows * c->M * sizeof(__half2));
-    if (e == hipSuccess) e = hipMemsetAsync(v->d_ring, 0, (size_t)v->rows * c->M * sizeof(__half2), c->stream);   // a fresh texture: zeros
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&v->d_palette), 32 * 32 * sizeof(float4));
+    if (e == hipSuccess) e = v->d_ring.alloc((size_t)v->rows * c->M);
+    if (e == hipSuccess) e = hipMemsetAsync(v->d_ring.get(), 0, (size_t)v->rows * c->M * sizeof(__half2), c->stream);   // a fresh texture: zeros
+    if (e == hipSuccess) e = v->d_palette.alloc(32 * 32);
     if (e != hipSuccess) {
         const int rc = view_fail_hip(v, e, "sgx_view_create");
         sgx_view_destroy(v);
@@ -157,9 +157,7 @@ void sgx_view_destroy(sgx_view *v)
         for (size_t i = 0; i < vs.size(); ++i)
             if (vs[i] == v) { vs.erase(vs.begin() + (long)i); break; }
     }
-    if (v->d_ring) (void)hipFree(v->d_ring);
-    if (v->d_palette) (void)hipFree(v->d_palette);
-    delete v;
+    delete v;   // (its buffers with it, whether or not the context is still there)
 }
 
 int sgx_view_write_rows(sgx_view *v, const void *d_rows_f16, size_t n_rows, uint32_t *offset_out)
@@ -173,7 +171,7 @@ int sgx_view_write_rows(sgx_view *v, const void *d_rows_f16, size_t n_rows, uint
     // gpu_spectrogram.rs:255-275: fill up to the top of the texture, wrap, go on
     while (n_rows > 0) {
         const size_t room = v->rows - v->offset, take = n_rows < room ? n_rows : room;
-        VIEW_HIP(v, hipMemcpyAsync(reinterpret_cast<char *>(v->d_ring) + (size_t)v->offset * row_bytes, src, take * row_bytes,
+        VIEW_HIP(v, hipMemcpyAsync(reinterpret_cast<char *>(v->d_ring.get()) + (size_t)v->offset * row_bytes, src, take * row_bytes,
                                    hipMemcpyDeviceToDevice, c->stream));
         v->offset = (uint32_t)((v->offset + take) % v->rows);
         src += take * row_bytes;
@@ -195,12 +193,12 @@ int sgx_view_draw(sgx_view *v, uint32_t width, uint32_t height, float *d_rgba_f3
         const int rc = sgx_lookup_table(c, 32, lut.data());
         if (rc != SGX_OK) return rc;
         VIEW_HIP(v, hipStreamSynchronize(c->stream));
-        VIEW_HIP(v, hipMemcpy(v->d_palette, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+        VIEW_HIP(v, hipMemcpy(v->d_palette.get(), lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
         v->palette_gen = c->palette_gen;
     }
     sgx::ViewParams p{};
-    p.ring = v->d_ring;
-    p.palette = v->d_palette;
+    p.ring = v->d_ring.get();
+    p.palette = v->d_palette.get();
     p.out = reinterpret_cast<float4 *>(d_rgba_f32);
     p.M = c->M;
     p.rows = v->rows;

@@ -24,38 +24,24 @@ bool w16384_supported(const sgx_ctx *c)
     return c->W == w16k::kW && (c->C == 1 || (c->C & 1) == 0) && c->lds_optin >= w16k::kLdsBytes;
 }
 
-hipError_t w16384_init(sgx_ctx *c, void **out)
+void TablesDelete::operator()(w16k::TablesW *t) const { delete t; }
+
+hipError_t w16384_init(sgx_ctx *c)
 {
     using namespace w16k;
-    auto *t = new TablesW();
-    auto unit = [](unsigned long long idx, unsigned long long N) {
-        idx %= N;
-        const double ang = -2.0 * M_PI * (double)idx / (double)N;
-        double cs = cos(ang), sn = sin(ang);
-        if (idx == 0) { cs = 1.0; sn = 0.0; }
-        if (4 * idx == N) { cs = 0.0; sn = -1.0; }
-        if (2 * idx == N) { cs = -1.0; sn = 0.0; }
-        if (4 * idx == 3 * N) { cs = 0.0; sn = 1.0; }
-        return make_float2((float)cs, (float)sn);
-    };
+    TablesPtr<TablesW> t(new TablesW());
     std::vector<float2> T1(32 * 512), tw2(512);
     std::vector<float> win16((size_t)kW);
     for (int q = 0; q < 32; ++q)
-        for (int cc = 0; cc < 512; ++cc) T1[q * 512 + cc] = unit((unsigned long long)q * cc, kP);
+        for (int cc = 0; cc < 512; ++cc) T1[q * 512 + cc] = unit_root2((unsigned long long)q * cc, kP);
     for (int c0 = 0; c0 < 16; ++c0)
-        for (int q2 = 0; q2 < 32; ++q2) tw2[c0 * 32 + q2] = unit((unsigned long long)q2 * c0, 512);
+        for (int q2 = 0; q2 < 32; ++q2) tw2[c0 * 32 + q2] = unit_root2((unsigned long long)q2 * c0, 512);
     // the scale (hypot / 2) * (2 / W) = 1 / W is a power of two and commutes with every rounding
     for (int a = 0; a < 16; ++a)
         for (int cc = 0; cc < 512; ++cc) win16[((size_t)(a >> 2) * 512 + cc) * 4 + (a & 3)] = c->tab.window[cc + 512 * a] * (1.0f / (float)kW);
-    auto up = [](float2 **dst, const std::vector<float2> &v) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(&t->d_T1, T1);
-    if (e == hipSuccess) e = up(&t->d_tw2, tw2);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_win16), win16.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(t->d_win16, win16.data(), win16.size() * sizeof(float), hipMemcpyHostToDevice);
+    hipError_t e = t->d_T1.upload(T1);
+    if (e == hipSuccess) e = t->d_tw2.upload(tw2);
+    if (e == hipSuccess) e = t->d_win16.upload(win16);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(stft16384_w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e == hipSuccess)
@@ -66,23 +52,8 @@ hipError_t w16384_init(sgx_ctx *c, void **out)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(stft16384_w_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(stft16384_w_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-    if (e != hipSuccess) {
-        w16384_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-void w16384_destroy(void *tables)
-{
-    auto *t = static_cast<w16k::TablesW *>(tables);
-    if (!t) return;
-    if (t->d_T1) (void)hipFree(t->d_T1);
-    if (t->d_tw2) (void)hipFree(t->d_tw2);
-    if (t->d_win16) (void)hipFree(t->d_win16);
-    if (t->d_planes) (void)hipFree(t->d_planes);
-    delete t;
+    if (e == hipSuccess) c->w16k = std::move(t);
+    return e;
 }
 
 // stft16384_w_complex.hip: the complex-row kernels, launched on this file's parameter block (the same struct there)
@@ -98,11 +69,11 @@ hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call)
     const uint32_t channels = call.channels, pairs = call.pairs;
     const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     if (n_frames == 0) return hipSuccess;
-    auto *t = static_cast<TablesW *>(c->d_w16k);
+    TablesW *t = c->w16k.get();   // (not const: the plane below is regrown)
     Params p{};
-    p.T1 = t->d_T1;
-    p.tw2 = t->d_tw2;
-    p.win16 = t->d_win16;
+    p.T1 = t->d_T1.get();
+    p.tw2 = t->d_tw2.get();
+    p.win16 = t->d_win16.get();
     p.mags = d_mags;
     p.first_frame = first_frame;
     p.n_frames = n_frames;
@@ -123,13 +94,13 @@ hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call)
         const size_t first_sample = first_frame * (size_t)c->H;
         const size_t n_samp = (n_frames - 1) * (size_t)c->H + kW;
         const size_t plane = (2 * n_samp + 63) & ~(size_t)63;  // floats
-        hipError_t e = grow(c->stream, t->d_planes, t->planes_floats, plane, plane * sizeof(float));   // (a previous launch may still read the old plane)
+        hipError_t e = t->d_planes.grow(c->stream, plane);   // (a previous launch may still read the old plane)
         if (e != hipSuccess) return e;
         const unsigned blocks = (unsigned)std::min<size_t>((n_samp + 255) / 256, (size_t)c->n_cu * 16);
-        hipLaunchKernelGGL(w16k::duplicate_mono_kernel, dim3(blocks), dim3(256), 0, c->stream, d_pcm, t->d_planes, first_sample, n_samp);
+        hipLaunchKernelGGL(w16k::duplicate_mono_kernel, dim3(blocks), dim3(256), 0, c->stream, d_pcm, t->d_planes.get(), first_sample, n_samp);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        p.pcm = t->d_planes;
+        p.pcm = t->d_planes.get();
         p.plane_floats = plane;
         p.sample_base = (long long)first_sample;
     } else {

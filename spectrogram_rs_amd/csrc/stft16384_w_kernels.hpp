@@ -546,10 +546,9 @@ __global__ void __launch_bounds__(512, 2) stft16384_w_kernel(Params p)
 }
 
 struct TablesW {
-    float2 *d_T1 = nullptr, *d_tw2 = nullptr;
-    float *d_win16 = nullptr;
-    float *d_planes = nullptr;   // the (s, s) plane of a mono stream whose frames are not paired, grown on demand
-    size_t planes_floats = 0;
+    DeviceBuffer<float2> d_T1, d_tw2;
+    DeviceBuffer<float> d_win16;
+    DeviceBuffer<float> d_planes;   // the (s, s) plane of a mono stream whose frames are not paired, grown on demand
 };
 
 }  // namespace SGX_W16K_NS

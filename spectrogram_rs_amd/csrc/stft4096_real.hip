@@ -559,7 +559,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
 }
 
 struct RealTables {
-    float2 *d_tw1 = nullptr, *d_tw2 = nullptr, *d_twu = nullptr;
+    DeviceBuffer<float2> d_tw1, d_tw2, d_twu;
 };
 
 }  // namespace wgr
@@ -576,59 +576,32 @@ extern "C" __attribute__((visibility("default"))) int sgx_debug_phase_cycles_r(u
 }
 #endif
 
-hipError_t real4096_init(sgx_ctx *c, void **out)
+void TablesDelete::operator()(wgr::RealTables *t) const { delete t; }
+
+hipError_t real4096_init(sgx_ctx *c)
 {
     using namespace wgr;
-    (void)c;
-    auto *t = new RealTables();
-    auto unit = [](unsigned long long e, unsigned long long n) {   // e^{-2 pi i e / n}, exact on the axes
-        e %= n;
-        if (e == 0) return make_float2(1.0f, 0.0f);
-        if (4 * e == n) return make_float2(0.0f, -1.0f);
-        if (2 * e == n) return make_float2(-1.0f, 0.0f);
-        if (4 * e == 3 * n) return make_float2(0.0f, 1.0f);
-        const double ang = -2.0 * M_PI * (double)e / (double)n;
-        return make_float2((float)cos(ang), (float)sin(ang));
-    };
+    TablesPtr<RealTables> t(new RealTables());
     std::vector<float2> tw1(8 * 256), tw2(256), twu(8 * 128);
     for (int q = 0; q < 8; ++q)
-        for (int tt = 0; tt < 256; ++tt) tw1[q * 256 + tt] = unit((unsigned long long)tt * q, 2048);
+        for (int tt = 0; tt < 256; ++tt) tw1[q * 256 + tt] = unit_root2((unsigned long long)tt * q, 2048);
     for (int q = 0; q < 16; ++q)
-        for (int t0 = 0; t0 < 16; ++t0) tw2[q * 16 + t0] = unit((unsigned long long)t0 * q, 256);
+        for (int t0 = 0; t0 < 16; ++t0) tw2[q * 16 + t0] = unit_root2((unsigned long long)t0 * q, 256);
     for (int q3 = 0; q3 < 8; ++q3)
-        for (int uu = 0; uu < 128; ++uu) twu[q3 * 128 + uu] = unit((unsigned long long)(uu + 128 * q3), 4096);
-    twu[0] = unit(1024, 4096);   // thread 0, q3 = 0: the self-paired bin 1024
-    auto up = [](float2 **dst, const std::vector<float2> &v) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(&t->d_tw1, tw1);
-    if (e == hipSuccess) e = up(&t->d_tw2, tw2);
-    if (e == hipSuccess) e = up(&t->d_twu, twu);
-    if (e != hipSuccess) {
-        real4096_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-void real4096_destroy(void *tables)
-{
-    auto *t = static_cast<wgr::RealTables *>(tables);
-    if (!t) return;
-    if (t->d_tw1) (void)hipFree(t->d_tw1);
-    if (t->d_tw2) (void)hipFree(t->d_tw2);
-    if (t->d_twu) (void)hipFree(t->d_twu);
-    delete t;
+        for (int uu = 0; uu < 128; ++uu) twu[q3 * 128 + uu] = unit_root2((unsigned long long)(uu + 128 * q3), 4096);
+    twu[0] = unit_root2(1024, 4096);   // thread 0, q3 = 0: the self-paired bin 1024
+    hipError_t e = t->d_tw1.upload(tw1);
+    if (e == hipSuccess) e = t->d_tw2.upload(tw2);
+    if (e == hipSuccess) e = t->d_twu.upload(twu);
+    if (e == hipSuccess) c->real = std::move(t);
+    return e;
 }
 
 // the streams this kernel serves: one channel, W = 2048 (H = 256 slides its window in registers)
 bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels)
 {
     (void)d_pcm;   // any hop, any (4-byte) alignment of the stream: see samples_from
-    return channels == 1 && c->d_real && c->W == (uint32_t)wgr::kW;
+    return channels == 1 && c->real && c->W == (uint32_t)wgr::kW;
 }
 
 namespace wg {
@@ -639,11 +612,11 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
 {
     using namespace wgr;
     if (p.n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const RealTables *>(c->d_real);
+    const RealTables *t = c->real.get();
     const bool hold_peak = kind == Out::kPeak;
-    p.tw1 = t->d_tw1;
-    p.tw2 = t->d_tw2;
-    p.twu = t->d_twu;
+    p.tw1 = t->d_tw1.get();
+    p.tw2 = t->d_tw2.get();
+    p.twu = t->d_twu.get();
     p.stream_samples = p.total_frames ? (p.total_frames - 1) * (unsigned long long)c->H + (unsigned long long)kW : 0;   // what the stream's frames cover (the caller may hold more)
     p.n_jobs = (p.n_frames + 1) / 2;
     RunSplit runs = run_split(c, p.n_jobs, 4);   // persistent workgroups, four per CU, each a contiguous run of frame pairs

@@ -634,25 +634,17 @@ extern "C" __attribute__((visibility("default"))) int sgx_debug_phase_cycles(uns
 }
 #endif
 
-hipError_t wg4096_init(sgx_ctx *c, void **out)
+void TablesDelete::operator()(wg::WgTables *t) const { delete t; }
+
+hipError_t wg4096_init(sgx_ctx *c)
 {
     using namespace wg;
-    auto *t = new WgTables();
+    TablesPtr<WgTables> t(new WgTables());
     std::vector<float2> tw1(16 * 256), tw2(256);
-    auto unit = [](int idx, int N) {
-        idx %= N;
-        const double ang = -2.0 * M_PI * (double)idx / (double)N;
-        double cs = cos(ang), sn = sin(ang);
-        if (idx == 0) { cs = 1.0; sn = 0.0; }
-        if (4 * idx == N) { cs = 0.0; sn = -1.0; }
-        if (2 * idx == N) { cs = -1.0; sn = 0.0; }
-        if (4 * idx == 3 * N) { cs = 0.0; sn = 1.0; }
-        return make_float2((float)cs, (float)sn);
-    };
     for (int q = 0; q < 16; ++q)
-        for (int tt = 0; tt < 256; ++tt) tw1[q * 256 + tt] = unit(tt * q, kP);
+        for (int tt = 0; tt < 256; ++tt) tw1[q * 256 + tt] = unit_root2(tt * q, kP);
     for (int q = 0; q < 16; ++q)
-        for (int t0 = 0; t0 < 16; ++t0) tw2[q * 16 + t0] = unit(t0 * q, 256);
+        for (int t0 = 0; t0 < 16; ++t0) tw2[q * 16 + t0] = unit_root2(t0 * q, 256);
 
     // packed tables of the fused pixel path: 4 B per row, 8 B per LDS slot (the kernel re-derives mu^2, mu^3 and 1 - o' with the
     // same single-rounded operations the host table holds).  Slots = the rows' samples in lin_space order; after a row whose
@@ -692,47 +684,24 @@ hipError_t wg4096_init(sgx_ctx *c, void **out)
         t->block_max_cnt |= (mx > 255 ? 255u : mx) << (8 * blk);     // (saturates at 255; no kernel reads it: Params)
     }
 
-    auto up = [](auto **dst, const auto &v) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(v[0]));
-        if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(&t->d_tw1, tw1);
-    if (e == hipSuccess) e = up(&t->d_tw2, tw2);
-    if (e == hipSuccess) e = up(&t->d_rows, rows);
-    if (e == hipSuccess) e = up(&t->d_samples, samples);
-    if (e != hipSuccess) {
-        wg4096_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
+    hipError_t e = t->d_tw1.upload(tw1);
+    if (e == hipSuccess) e = t->d_tw2.upload(tw2);
+    if (e == hipSuccess) e = t->d_rows.upload(rows);
+    if (e == hipSuccess) e = t->d_samples.upload(samples);
+    if (e == hipSuccess) c->wg = std::move(t);
+    return e;
 }
 
-void wg4096_destroy(void *tables)
+bool wg4096_can_fuse_render(const sgx_ctx *c)
 {
-    auto *t = static_cast<wg::WgTables *>(tables);
-    if (!t) return;
-    if (t->d_tw1) (void)hipFree(t->d_tw1);
-    if (t->d_tw2) (void)hipFree(t->d_tw2);
-    if (t->d_rows) (void)hipFree(t->d_rows);
-    if (t->d_samples) (void)hipFree(t->d_samples);
-    if (t->d_planes) (void)hipFree(t->d_planes);
-    if (t->d_peak_partial) (void)hipFree(t->d_peak_partial);
-    delete t;
-}
-
-bool wg4096_can_fuse_render(const sgx_ctx *c, const void *tables)
-{
-    const auto *t = static_cast<const wg::WgTables *>(tables);
+    const wg::WgTables *t = c->wg.get();
     // mono (sequential) colour schemes with a 256-entry ramp; diverging schemes take the two-kernel path
     return t && t->fusable && c->pal.n == 256 && !c->pal.stereo && !c->pal.segments;
 }
 
-bool wg4096_can_fuse_bands(const sgx_ctx *c, const void *tables)
+bool wg4096_can_fuse_bands(const sgx_ctx *c)
 {
-    (void)c;   // the column without the colour: only the row and sample tables have to fit
-    const auto *t = static_cast<const wg::WgTables *>(tables);
+    const wg::WgTables *t = c->wg.get();   // the column without the colour: only the row and sample tables have to fit
     return t && t->fusable;
 }
 
@@ -761,7 +730,7 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
     const uint32_t channels = call.channels, pairs = call.pairs;
     const size_t first_frame = call.first, n_frames = call.n;
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const WgTables *>(c->d_fast_wg);
+    WgTables *t = c->wg.get();   // (not const: the scratch below is regrown)
     const bool band_means = call.kind == Out::kBands || call.kind == Out::kPeak, column = band_means || call.kind == Out::kRgba;
     const sgx_fbank *bank = call.kind == Out::kFbank ? call.bank : nullptr;
     if (call.kind == Out::kFbank && !wg4096_can_fuse_fbank(c, bank)) return hipErrorInvalidValue;   // (the workspace route: stft_route)
@@ -769,8 +738,7 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
     if (call.kind == Out::kPeak && peak_group == 0) return hipErrorInvalidValue;
     // the partial columns of every persistent workgroup
     if (peak_group) {
-        const size_t partial_floats = (size_t)c->n_cu * 4 * 2 * c->R * 2;
-        const hipError_t e = grow(c->stream, t->d_peak_partial, t->peak_partial_floats, partial_floats, partial_floats * sizeof(float));
+        const hipError_t e = t->d_peak_partial.grow(c->stream, (size_t)c->n_cu * 4 * 2 * c->R);
         if (e != hipSuccess) return e;
     }
     // More than two channels: the (l, r) pairs are split into planes first and every pair runs the two-channel kernel on its
@@ -780,17 +748,17 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
     if (channels > 2) {
         const size_t first_sample = first_frame * (size_t)c->H, n_samp = (n_frames - 1) * (size_t)c->H + kW;
         plane_floats = (2 * n_samp + 63) & ~(size_t)63;
-        hipError_t e = grow(c->stream, t->d_planes, t->planes_floats, plane_floats * pairs, plane_floats * pairs * sizeof(float));   // (a previous launch may still read the old planes)
+        hipError_t e = t->d_planes.grow(c->stream, plane_floats * pairs);   // (a previous launch may still read the old planes)
         if (e != hipSuccess) return e;
-        e = launch_deinterleave_pairs(c, d_pcm, t->d_planes, plane_floats, first_sample, n_samp, channels, pairs);
+        e = launch_deinterleave_pairs(c, d_pcm, t->d_planes.get(), plane_floats, first_sample, n_samp, channels, pairs);
         if (e != hipSuccess) return e;
     }
     for (uint32_t pair = 0; pair < pairs; ++pair) {
         Params p{};
         p.pcm = d_pcm;
-        p.tw1 = t->d_tw1;
-        p.tw2 = t->d_tw2;
-        p.window = c->d_window;
+        p.tw1 = t->d_tw1.get();
+        p.tw2 = t->d_tw2.get();
+        p.window = c->d_window.get();
         p.mags = column || bank ? nullptr : static_cast<float *>(call.out);
         p.out_f16 = call.kind == Out::kMagsF16 ? 1u : 0u;
         p.first_frame = first_frame;
@@ -803,17 +771,17 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
         p.pair_l = channels == 1 ? 0 : 2 * pair;
         p.pair_r = channels == 1 ? 0 : 2 * pair + 1;
         if (channels > 2) {   // this pair's plane as a two-channel stream whose sample 0 is the call's first sample
-            p.pcm = t->d_planes + (size_t)pair * plane_floats - first_frame * (size_t)c->H * 2;
+            p.pcm = t->d_planes.get() + (size_t)pair * plane_floats - first_frame * (size_t)c->H * 2;
             p.C = 2;
             p.pair_l = 0;
             p.pair_r = 1;
         }
         if (column) {
-            p.rows = t->d_rows;
-            p.samples = t->d_samples;
+            p.rows = t->d_rows.get();
+            p.samples = t->d_samples.get();
             p.n_samples = t->n_samples;
-            p.lut_thr = c->d_lut_thr;
-            p.lut_rgba = c->d_lut_rgba;
+            p.lut_thr = c->d_lut_thr.get();
+            p.lut_rgba = c->d_lut_rgba.get();
             p.rgba = static_cast<uint8_t *>(call.out);
             p.R = c->R;
             p.interp = c->cfg.interp;
@@ -825,12 +793,12 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
             p.block_max_cnt = t->block_max_cnt;
             if (peak_group) {   // (in the words of the palette and the row pointer: see Params)
                 p.peak_group = peak_group;
-                p.peak_partial = t->d_peak_partial;
+                p.peak_partial = t->d_peak_partial.get();
             }
         }
         if (bank) {   // (in the words of the row and sample tables: see Params)
-            p.rows = reinterpret_cast<const uint32_t *>(bank->d_filters);
-            p.samples = reinterpret_cast<const PackedSample *>(bank->d_weights);
+            p.rows = reinterpret_cast<const uint32_t *>(bank->d_filters.get());
+            p.samples = reinterpret_cast<const PackedSample *>(bank->d_weights.get());
             p.n_samples = (uint32_t)bank->n_weights;
             p.R = bank->n_filters;
             p.interp = bank->power;
@@ -901,7 +869,7 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
 // the workspace route
 bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb)
 {
-    if (!fb || !c->d_fast_wg || c->stft_kernel != kKernelWg4096) return false;
+    if (!fb || !c->wg || c->stft_kernel != kKernelWg4096) return false;
     if (fb->n_filters > fbank::kFusedMaxFilters || fb->n_weights > fbank::kFusedMaxWeights) return false;
     if (c->C == 1) return !(c->cfg.flags & (SGX_FLAG_PAIRED_FRAMES | SGX_FLAG_COMPLEX_MONO)) && real4096_serves(c, nullptr, 1);
     return true;
@@ -909,9 +877,9 @@ bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb)
 
 // sgx_bands_peak_batch in one kernel: every stream the bands column serves but paired mono frames (two frames of one transform may
 // fall into different columns of different workgroups' bookkeeping: those contexts take the workspace route)
-bool wg4096_can_fuse_peak(const sgx_ctx *c, const void *tables)
+bool wg4096_can_fuse_peak(const sgx_ctx *c)
 {
-    return wg4096_can_fuse_bands(c, tables) && !paired_mono(c, c->C);
+    return wg4096_can_fuse_bands(c) && !paired_mono(c, c->C);
 }
 
 }  // namespace sgx

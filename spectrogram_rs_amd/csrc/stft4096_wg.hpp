@@ -94,18 +94,15 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind);   // kPeak: p.
 constexpr int kPairAdjacentRow = 0, kPairAdjacent = 1;
 
 struct WgTables {
-    float2 *d_tw1 = nullptr;
-    float2 *d_tw2 = nullptr;
-    uint32_t *d_rows = nullptr;        // packed row table for the fused pixel path
-    PackedSample *d_samples = nullptr;
+    DeviceBuffer<float2> d_tw1, d_tw2;
+    DeviceBuffer<uint32_t> d_rows;        // packed row table for the fused pixel path
+    DeviceBuffer<PackedSample> d_samples;
     uint32_t n_samples = 0;
     uint32_t single_rows = 0;          // Params::single_rows
     uint32_t block_max_cnt = 0;        // Params::block_max_cnt
     bool fusable = false;
-    mutable float *d_planes = nullptr;   // more than two channels: (l, r) pair planes of the sample range of a call, grown on demand
-    mutable size_t planes_floats = 0;
-    mutable float2 *d_peak_partial = nullptr;   // sgx_bands_peak_batch: [workgroups][2][R] partial columns (peak_dst), grown on demand
-    mutable size_t peak_partial_floats = 0;
+    DeviceBuffer<float> d_planes;          // more than two channels: (l, r) pair planes of the sample range of a call, grown on demand
+    DeviceBuffer<float2> d_peak_partial;   // sgx_bands_peak_batch: [workgroups][2][R] partial columns (peak_dst), grown on demand
 };
 
 __device__ __forceinline__ void lds_barrier()

@@ -56,8 +56,8 @@ __device__ __forceinline__ f2v cl_fma(f2v a, float c, f2v u) { return __builtin_
 using mix::cmul;
 
 struct W48Tables {
-    float2 *d_tw1 = nullptr;   // [8][320][2]  w_4800^{t q1} at [q1 / 2][t][q1 % 2]: a lane takes (q1, q1 + 1) as one 16-byte word
-    float2 *d_tw2 = nullptr;   // [15][20]   w_300^{t0 q2} at [t0][q2]
+    DeviceBuffer<float2> d_tw1;   // [8][320][2]  w_4800^{t q1} at [q1 / 2][t][q1 % 2]: a lane takes (q1, q1 + 1) as one 16-byte word
+    DeviceBuffer<float2> d_tw2;   // [15][20]   w_300^{t0 q2} at [t0][q2]
 };
 
 struct Params {
@@ -354,44 +354,21 @@ __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
 bool w4800_supported(const sgx_ctx *c) { return c->P == (uint32_t)w48::kP && c->W == (uint32_t)w48::kW; }
 
-hipError_t w4800_init(sgx_ctx *c, void **out)
+void TablesDelete::operator()(w48::W48Tables *t) const { delete t; }
+
+hipError_t w4800_init(sgx_ctx *c)
 {
     using namespace w48;
-    (void)c;
-    auto *t = new W48Tables();
+    TablesPtr<W48Tables> t(new W48Tables());
     std::vector<float2> tw1((size_t)16 * kT), tw2((size_t)15 * 20);
-    auto unit = [](unsigned long long e, unsigned long long n) {   // e^{-2 pi i e / n}, exact on the axes
-        e %= n;
-        if (e == 0) return make_float2(1.0f, 0.0f);
-        if (4 * e == n) return make_float2(0.0f, -1.0f);
-        if (2 * e == n) return make_float2(-1.0f, 0.0f);
-        if (4 * e == 3 * n) return make_float2(0.0f, 1.0f);
-        const double ang = -2.0 * M_PI * (double)e / (double)n;
-        return make_float2((float)cos(ang), (float)sin(ang));
-    };
     for (int q1 = 0; q1 < 16; ++q1)
-        for (int th = 0; th < kT; ++th) tw1[((size_t)(q1 / 2) * kT + th) * 2 + q1 % 2] = unit((unsigned long long)q1 * (th < kN1 ? th : 0), kP);
+        for (int th = 0; th < kT; ++th) tw1[((size_t)(q1 / 2) * kT + th) * 2 + q1 % 2] = unit_root2((unsigned long long)q1 * (th < kN1 ? th : 0), kP);
     for (int t0 = 0; t0 < 15; ++t0)
-        for (int q2 = 0; q2 < 20; ++q2) tw2[(size_t)t0 * 20 + q2] = unit((unsigned long long)t0 * q2, 300);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->d_tw1), tw1.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(t->d_tw1, tw1.data(), tw1.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_tw2), tw2.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(t->d_tw2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        w4800_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-void w4800_destroy(void *tables)
-{
-    auto *t = static_cast<w48::W48Tables *>(tables);
-    if (!t) return;
-    if (t->d_tw1) (void)hipFree(t->d_tw1);
-    if (t->d_tw2) (void)hipFree(t->d_tw2);
-    delete t;
+        for (int q2 = 0; q2 < 20; ++q2) tw2[(size_t)t0 * 20 + q2] = unit_root2((unsigned long long)t0 * q2, 300);
+    hipError_t e = t->d_tw1.upload(tw1);
+    if (e == hipSuccess) e = t->d_tw2.upload(tw2);
+    if (e == hipSuccess) c->w4800 = std::move(t);
+    return e;
 }
 
 hipError_t launch_w4800(const sgx_ctx *c, const StftCall &call)
@@ -402,12 +379,12 @@ hipError_t launch_w4800(const sgx_ctx *c, const StftCall &call)
     if (n_frames == 0) return hipSuccess;
     // (the caller sends more channels, and the fused columns, to the composite-radix kernel)
     if (channels > 2 || (call.kind != Out::kMags && call.kind != Out::kMagsF16 && call.kind != Out::kComplex)) return hipErrorInvalidValue;
-    const auto *t = static_cast<const W48Tables *>(c->d_w4800);
+    const W48Tables *t = c->w4800.get();
     Params p{};
     p.pcm = call.pcm;
-    p.tw1 = t->d_tw1;
-    p.tw2 = t->d_tw2;
-    p.window = c->d_window;
+    p.tw1 = t->d_tw1.get();
+    p.tw2 = t->d_tw2.get();
+    p.window = c->d_window.get();
     p.mags = static_cast<float *>(call.out);
     p.first_frame = first_frame;
     p.n_frames = n_frames;

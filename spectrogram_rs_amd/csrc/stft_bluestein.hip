@@ -22,9 +22,9 @@ namespace sgx {
 namespace blu {
 
 struct BluTables {
-    float2 *d_chirp = nullptr;  // [P]    c[n]
-    float2 *d_bhat = nullptr;   // [L]    FFT_L(b) / L at ldsfft::pos_of(k)
-    float2 *d_tw = nullptr;     // [L]    e^{-2 pi i j / L}
+    DeviceBuffer<float2> d_chirp;  // [P]    c[n]
+    DeviceBuffer<float2> d_bhat;   // [L]    FFT_L(b) / L at ldsfft::pos_of(k)
+    DeviceBuffer<float2> d_tw;     // [L]    e^{-2 pi i j / L}
     uint32_t L = 0, logL = 0;
 };
 
@@ -172,10 +172,12 @@ bool bluestein_supported(uint32_t W)
     return W >= 4 && 3ull * W - 1 <= 16384;
 }
 
-hipError_t bluestein_init(sgx_ctx *c, void **out)
+void TablesDelete::operator()(blu::BluTables *t) const { delete t; }
+
+hipError_t bluestein_init(sgx_ctx *c)
 {
     using namespace blu;
-    auto *t = new BluTables();
+    TablesPtr<BluTables> t(new BluTables());
     const uint32_t W = c->W, P = c->P;
     uint32_t L = 1, logL = 0;
     while (L < P + W - 1) { L <<= 1; ++logL; }
@@ -204,33 +206,14 @@ hipError_t bluestein_init(sgx_ctx *c, void **out)
         if (4 * j == 3 * L) { cs = 0.0; sn = 1.0; }
         tw[j] = make_float2((float)cs, (float)sn);
     }
-    auto up = [](float2 **dst, const std::vector<float2> &v) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(&t->d_chirp, chirp);
-    if (e == hipSuccess) e = up(&t->d_bhat, bhat);
-    if (e == hipSuccess) e = up(&t->d_tw, tw);
+    hipError_t e = t->d_chirp.upload(chirp);
+    if (e == hipSuccess) e = t->d_bhat.upload(bhat);
+    if (e == hipSuccess) e = t->d_tw.upload(tw);
     if (e == hipSuccess && (size_t)L * sizeof(float2) > 64 * 1024)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(stft_bluestein_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)L * sizeof(float2)));
-    if (e != hipSuccess) {
-        bluestein_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-void bluestein_destroy(void *tables)
-{
-    auto *t = static_cast<blu::BluTables *>(tables);
-    if (!t) return;
-    if (t->d_chirp) (void)hipFree(t->d_chirp);
-    if (t->d_bhat) (void)hipFree(t->d_bhat);
-    if (t->d_tw) (void)hipFree(t->d_tw);
-    delete t;
+    if (e == hipSuccess) c->blu = std::move(t);
+    return e;
 }
 
 hipError_t launch_bluestein(const sgx_ctx *c, const StftCall &call)
@@ -244,13 +227,13 @@ hipError_t launch_bluestein(const sgx_ctx *c, const StftCall &call)
     const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     const auto kernel = complex_rows ? stft_bluestein_complex_kernel : stft_bluestein_kernel;
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const BluTables *>(c->d_blu);
+    const BluTables *t = c->blu.get();
     Params p{};
     p.pcm = d_pcm;
-    p.window = c->d_window;
-    p.chirp = t->d_chirp;
-    p.bhat = t->d_bhat;
-    p.tw = t->d_tw;
+    p.window = c->d_window.get();
+    p.chirp = t->d_chirp.get();
+    p.bhat = t->d_bhat.get();
+    p.tw = t->d_tw.get();
     p.W = c->W;
     p.P = c->P;
     p.L = t->L;

@@ -241,10 +241,10 @@ __global__ void __launch_bounds__(512) istft_kernel(IParams p)
 }
 
 struct ITables {
-    mix::MixTables *plan = nullptr;   // the Q-point stage plan (route 1: Q = 2W, route 2: Q = L)
+    TablesPtr<mix::MixTables> plan;   // the Q-point stage plan (route 1: Q = 2W, route 2: Q = L)
     uint32_t route = 0, Q = 0, pos_w = 0;
-    float2 *d_chirp = nullptr, *d_bhat = nullptr;
-    float4 *d_parity = nullptr;
+    DeviceBuffer<float2> d_chirp, d_bhat;   // (route 2 only, as d_parity: else null)
+    DeviceBuffer<float4> d_parity;
     float k_e = 0.0f, k_o = 0.0f;
 };
 
@@ -303,35 +303,24 @@ int istft_route(const sgx_ctx *c)
     return 0;
 }
 
-void istft_destroy(void *tables)
-{
-    auto *t = static_cast<istft::ITables *>(tables);
-    if (!t) return;
-    mixed_destroy(t->plan);
-    if (t->d_chirp) (void)hipFree(t->d_chirp);
-    if (t->d_bhat) (void)hipFree(t->d_bhat);
-    if (t->d_parity) (void)hipFree(t->d_parity);
-    delete t;
-}
+void TablesDelete::operator()(istft::ITables *t) const { delete t; }
 
-hipError_t istft_init(sgx_ctx *c, void **out)
+hipError_t istft_init(sgx_ctx *c)
 {
     using namespace istft;
     const int route = istft_route(c);
     if (!route) return hipErrorInvalidValue;
     const uint32_t W = c->W, P = c->P;
-    auto *t = new ITables();
+    TablesPtr<ITables> t(new ITables());
     t->route = (uint32_t)route;
     uint32_t Q = P;
     if (route == 2) { Q = 1; while (Q < 3 * W - 1) Q <<= 1; }
     t->Q = Q;
-    void *plan = nullptr;
-    hipError_t e = mixed_length_tables(Q, &plan);
-    if (e != hipSuccess) { delete t; return e; }
-    t->plan = static_cast<mix::MixTables *>(plan);
+    hipError_t e = mixed_length_tables(Q, t->plan);
+    if (e != hipSuccess) return e;
     const uint32_t cnt_e = W / 2, cnt_o = W - W / 2;   // even / odd n in [W, 2W)
     if (route == 1) {
-        t->pos_w = digit_pos(t->plan, W);
+        t->pos_w = digit_pos(t->plan.get(), W);
         t->k_e = -1.0f / (float)cnt_e;
         t->k_o = -1.0f / (float)cnt_o;
     } else {
@@ -351,7 +340,7 @@ hipError_t istft_init(sgx_ctx *c, void **out)
         for (uint32_t d = 1; d < P; ++d) { br[Q - d] = cr[d]; bi[Q - d] = ci[d]; }
         fft_host(br, bi);
         std::vector<float2> bhat(t->plan->lds_points, make_float2(0.0f, 0.0f));
-        for (uint32_t K = 0; K < Q; ++K) bhat[digit_pos(t->plan, K)] = make_float2((float)(br[K] / (double)Q), (float)(bi[K] / (double)Q));
+        for (uint32_t K = 0; K < Q; ++K) bhat[digit_pos(t->plan.get(), K)] = make_float2((float)(br[K] / (double)Q), (float)(bi[K] / (double)Q));
         // E_S[k] = sum_{n in S} e^{i pi k n / W} over S = {n0, n0 + 2, ...} (cnt terms): e^{i pi k n0 / W} (1 - rho^cnt) / (1 - rho), rho = e^{2 i pi k / W}
         std::vector<float4> par(std::max<uint32_t>(W - 1, 1));
         auto weight = [&](uint32_t k, uint32_t n0, uint32_t cnt, float &tr, float &ti) {
@@ -372,27 +361,21 @@ hipError_t istft_init(sgx_ctx *c, void **out)
             weight(j + 1, n_odd, cnt_o, v.z, v.w);
             par[j] = v;
         }
-        auto up = [](auto **dst, const auto &v) {
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(v[0]));
-            if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-            return e;
-        };
-        e = up(&t->d_chirp, chirp);
-        if (e == hipSuccess) e = up(&t->d_bhat, bhat);
-        if (e == hipSuccess) e = up(&t->d_parity, par);
-        if (e != hipSuccess) { istft_destroy(t); return e; }
+        e = t->d_chirp.upload(chirp);
+        if (e == hipSuccess) e = t->d_bhat.upload(bhat);
+        if (e == hipSuccess) e = t->d_parity.upload(par);
     }
-    *out = t;
-    return hipSuccess;
+    if (e == hipSuccess) c->istft = std::move(t);
+    return e;
 }
 
-hipError_t launch_istft(const sgx_ctx *c, const void *tables, const float *d_spec, size_t n_frames, size_t s0, size_t s1, float *d_pcm)
+hipError_t launch_istft(const sgx_ctx *c, const float *d_spec, size_t n_frames, size_t s0, size_t s1, float *d_pcm)
 {
     using namespace istft;
-    const auto *t = static_cast<const ITables *>(tables);
-    const mix::MixTables *pl = t->plan;
+    const ITables *t = c->istft.get();
+    const mix::MixTables *pl = t->plan.get();
     IParams p{};
-    p.mp.tw = pl->d_tw;
+    p.mp.tw = pl->d_tw.get();
     p.mp.inv_pad = pl->pad_every ? 1.0f / (float)pl->pad_every : 0.0f;
     for (uint32_t i = 0; i < pl->n_stages; ++i) {
         p.mp.ra[i] = pl->ra[i];
@@ -405,11 +388,11 @@ hipError_t launch_istft(const sgx_ctx *c, const void *tables, const float *d_spe
     }
     p.spec = reinterpret_cast<const float4 *>(d_spec);
     p.out = d_pcm;
-    p.window = c->d_window;
-    p.split = pl->d_split;
-    p.chirp = t->d_chirp;
-    p.bhat = t->d_bhat;
-    p.parity = t->d_parity;
+    p.window = c->d_window.get();
+    p.split = pl->d_split.get();
+    p.chirp = t->d_chirp.get();
+    p.bhat = t->d_bhat.get();
+    p.parity = t->d_parity.get();
     p.n_frames = n_frames;
     p.s0 = s0;
     p.s1 = s1;

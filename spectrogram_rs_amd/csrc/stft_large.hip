@@ -67,8 +67,8 @@ struct Params {
 
 struct LargeTables {
     Plan pl;
-    float2 *d_roots1 = nullptr, *d_roots2 = nullptr, *d_tw = nullptr, *d_chirp = nullptr, *d_bt = nullptr;
-    float2 *d_scratch = nullptr;
+    DeviceBuffer<float2> d_roots1, d_roots2, d_tw, d_chirp, d_bt;   // (d_chirp, d_bt: null unless the plan is chirp-z)
+    DeviceBuffer<float2> d_scratch;
     uint32_t chunk = 0;   // transforms per chunk
     Geo g1{}, g2{};
 };
@@ -363,13 +363,6 @@ static void fft_f64(std::vector<double> &re, std::vector<double> &im)
     }
 }
 
-static hipError_t upload(float2 **dst, const std::vector<float2> &v)
-{
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice);
-    return e;
-}
-
 }  // namespace large
 
 bool large_supported(uint32_t W)
@@ -378,11 +371,13 @@ bool large_supported(uint32_t W)
     return large::make_plan(W, pl);
 }
 
-hipError_t large_init(sgx_ctx *c, void **out)
+void TablesDelete::operator()(large::LargeTables *t) const { delete t; }
+
+hipError_t large_init(sgx_ctx *c)
 {
     using namespace large;
-    auto *t = new LargeTables();
-    if (!make_plan(c->W, t->pl)) { delete t; return hipErrorInvalidValue; }
+    TablesPtr<LargeTables> t(new LargeTables());
+    if (!make_plan(c->W, t->pl)) return hipErrorInvalidValue;
     const Plan &pl = t->pl;
     const uint32_t N1 = pl.N1, N2 = pl.N2, L = pl.L, P = pl.P, W = pl.W;
     t->g1.N = N1;
@@ -395,9 +390,9 @@ hipError_t large_init(sgx_ctx *c, void **out)
             const double ang = -2.0 * M_PI * (double)(((uint64_t)k1 * n2) % L) / (double)L;
             tw[(size_t)k1 * N2 + n2] = make_float2((float)std::cos(ang), (float)std::sin(ang));
         }
-    hipError_t e = upload(&t->d_roots1, roots_of(N1, N1));
-    if (e == hipSuccess) e = upload(&t->d_roots2, roots_of(N2, N2));
-    if (e == hipSuccess) e = upload(&t->d_tw, tw);
+    hipError_t e = t->d_roots1.upload(roots_of(N1, N1));
+    if (e == hipSuccess) e = t->d_roots2.upload(roots_of(N2, N2));
+    if (e == hipSuccess) e = t->d_tw.upload(tw);
     if (e == hipSuccess && pl.chirp) {
         std::vector<double> cr(P), ci(P);
         std::vector<float2> chirp(P);
@@ -419,33 +414,20 @@ hipError_t large_init(sgx_ctx *c, void **out)
                 const size_t k = (size_t)k1 + (size_t)N1 * k2;
                 bt[(size_t)k1 * N2 + k2] = make_float2((float)(br[k] / (double)L), (float)(bi[k] / (double)L));
             }
-        e = upload(&t->d_chirp, chirp);
-        if (e == hipSuccess) e = upload(&t->d_bt, bt);
+        e = t->d_chirp.upload(chirp);
+        if (e == hipSuccess) e = t->d_bt.upload(bt);
     }
-    t->g1.roots = t->d_roots1;
-    t->g2.roots = t->d_roots2;
+    t->g1.roots = t->d_roots1.get();
+    t->g2.roots = t->d_roots2.get();
     // the scratch: as many transforms as fit kScratchBytes (at least one; 2 at 2W = 2^21)
     const size_t per = scratch_per_transform(pl);
     size_t chunk = kScratchBytes / per;
     if (chunk < 1) chunk = 1;
     if (chunk > 65535) chunk = 65535;
     t->chunk = (uint32_t)chunk;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_scratch), chunk * per);
-    if (e != hipSuccess) {
-        large_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-void large_destroy(void *tables)
-{
-    auto *t = static_cast<large::LargeTables *>(tables);
-    if (!t) return;
-    for (float2 *p : {t->d_roots1, t->d_roots2, t->d_tw, t->d_chirp, t->d_bt, t->d_scratch})
-        if (p) (void)hipFree(p);
-    delete t;
+    if (e == hipSuccess) e = t->d_scratch.alloc(chunk * per / sizeof(float2));   // (per: whole complex points)
+    if (e == hipSuccess) c->large = std::move(t);
+    return e;
 }
 
 hipError_t launch_large(const sgx_ctx *c, const StftCall &call)
@@ -459,16 +441,16 @@ hipError_t launch_large(const sgx_ctx *c, const StftCall &call)
     const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     (void)total_frames;   // every frame its own transform: no frame pairing
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const LargeTables *>(c->d_large);
+    const LargeTables *t = c->large.get();
     const Plan &pl = t->pl;
     Params p{};
     p.pcm = d_pcm;
-    p.window = c->d_window;
-    p.chirp = t->d_chirp;
-    p.tw = t->d_tw;
-    p.bt = t->d_bt;
-    p.scr = t->d_scratch;
-    p.nat = pl.chirp ? nullptr : t->d_scratch + (size_t)t->chunk * pl.L;
+    p.window = c->d_window.get();
+    p.chirp = t->d_chirp.get();
+    p.tw = t->d_tw.get();
+    p.bt = t->d_bt.get();
+    p.scr = t->d_scratch.get();
+    p.nat = pl.chirp ? nullptr : t->d_scratch.get() + (size_t)t->chunk * pl.L;
     p.mags = d_mags;
     p.g1 = t->g1;
     p.g2 = t->g2;

@@ -192,12 +192,12 @@ __global__ void __launch_bounds__(F::NT, 4) chirpz4_kernel(Params p)
 }
 
 struct ChirpTables {
-    float2 *d_chirp = nullptr, *d_bhat = nullptr, *d_tw = nullptr;
+    DeviceBuffer<float2> d_chirp, d_bhat, d_tw;
     uint32_t L = 0, lds_points = 0;
     // real-input mode (a mono stream, every frame its own transform): the chirp-z transform of W points over ceil(W / 2) sample pairs
     // -- a convolution of half the length -- and the untangling twiddles w_2W^k
-    ChirpTables *half = nullptr;
-    float2 *d_twr = nullptr;
+    TablesPtr<ChirpTables> half;
+    DeviceBuffer<float2> d_twr;
 };
 
 }  // namespace mix
@@ -277,13 +277,13 @@ static bool make_plan(uint32_t P, Plan &plan)
 
 // Tables of a P-point plan.  real: P is the WINDOW of real-input mode -- the split table pairs Z[k] with Z[P - k], k = 1 .. P / 2, and
 // the untangling twiddles w_2P^k come with it.  hipErrorInvalidValue: no plan for P (the caller of the real-input half goes without).
-static hipError_t build_tables(uint32_t P, bool real, mix::MixTables **out)
+static hipError_t build_tables(uint32_t P, bool real, TablesPtr<mix::MixTables> &out)
 {
     using namespace mix;
-    auto *t = new MixTables();
+    TablesPtr<MixTables> t(new MixTables());
     const uint32_t M = real ? P / 2 : P / 2 - 1;
     Plan plan;
-    if (!make_plan(P, plan)) { delete t; return hipErrorInvalidValue; }
+    if (!make_plan(P, plan)) return hipErrorInvalidValue;
     t->n_stages = (uint32_t)plan.stages.size();
     std::vector<uint32_t> radix(t->n_stages);
     std::vector<float2> tw;
@@ -297,16 +297,7 @@ static hipError_t build_tables(uint32_t P, bool real, mix::MixTables **out)
         t->tw_off[i] = (uint32_t)tw.size();
         if (t->m[i] > 1)
             for (uint32_t j = 0; j < t->m[i]; ++j)
-                for (uint32_t k = 1; k < radix[i]; ++k) {
-                    const unsigned long long e = ((unsigned long long)j * k) % ns;
-                    const double ang = -2.0 * M_PI * (double)e / (double)ns;
-                    double cs = cos(ang), sn = sin(ang);
-                    if (e == 0) { cs = 1.0; sn = 0.0; }
-                    if (4 * e == ns) { cs = 0.0; sn = -1.0; }
-                    if (2 * e == ns) { cs = -1.0; sn = 0.0; }
-                    if (4 * e == 3ull * ns) { cs = 0.0; sn = 1.0; }
-                    tw.push_back(make_float2((float)cs, (float)sn));
-                }
+                for (uint32_t k = 1; k < radix[i]; ++k) tw.push_back(unit_root2((unsigned long long)j * k, ns));
         ns = t->m[i];
     }
     // one point of padding per R_last points (see stage()) when R_last is even and the padding costs no resident
@@ -366,10 +357,8 @@ static hipError_t build_tables(uint32_t P, bool real, mix::MixTables **out)
     }
     std::vector<uint32_t> split(M);
     for (uint32_t j = 0; j < M; ++j) split[j] = pos[j + 1] | (pos[P - (j + 1)] << 16);   // positions < 21 120 < 2^16
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->d_split), (size_t)std::max<uint32_t>(M, 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(t->d_split, split.data(), (size_t)M * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_tw), std::max<size_t>(tw.size(), 1) * sizeof(float2));
-    if (e == hipSuccess && !tw.empty()) e = hipMemcpy(t->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
+    hipError_t e = t->d_split.upload_at_least_one(split);   // (the kernels take both pointers whatever the lengths)
+    if (e == hipSuccess) e = t->d_tw.upload_at_least_one(tw);
     if (e == hipSuccess && real) {
         std::vector<float2> twr(std::max<uint32_t>(M, 1));
         for (uint32_t j = 0; j < M; ++j) {
@@ -377,58 +366,36 @@ static hipError_t build_tables(uint32_t P, bool real, mix::MixTables **out)
             const double ang = -M_PI * (double)k / (double)P;
             twr[j] = 2 * k == P ? make_float2(0.0f, -1.0f) : make_float2((float)cos(ang), (float)sin(ang));
         }
-        e = hipMalloc(reinterpret_cast<void **>(&t->d_twr), twr.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(t->d_twr, twr.data(), twr.size() * sizeof(float2), hipMemcpyHostToDevice);
+        e = t->d_twr.upload(twr);
     }
-    if (e != hipSuccess) {
-        mixed_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-hipError_t mixed_init(sgx_ctx *c, void **out)
-{
-    mix::MixTables *t = nullptr;
-    hipError_t e = build_tables(c->P, false, &t);
-    if (e != hipSuccess) return e;
-    if (c->C == 1 && c->W >= 8) {   // a mono stream: the W-point plan of real-input mode, where W has one
-        e = build_tables(c->W, true, &t->half);
-        if (e != hipSuccess && e != hipErrorInvalidValue) {
-            mixed_destroy(t);
-            return e;
-        }
-    }
-    *out = t;
-    return hipSuccess;
-}
-
-hipError_t mixed_length_tables(uint32_t n, void **out)
-{
-    mix::MixTables *t = nullptr;
-    const hipError_t e = build_tables(n, false, &t);
-    if (e == hipSuccess) *out = t;
+    if (e == hipSuccess) out = std::move(t);
     return e;
 }
 
-uint32_t mixed_fixed_plan(const void *tables) { return tables ? (uint32_t)static_cast<const mix::MixTables *>(tables)->fixed : 0u; }
+void TablesDelete::operator()(mix::MixTables *t) const { delete t; }
+void TablesDelete::operator()(mix::ChirpTables *t) const { delete t; }
 
-void mixed_destroy(void *tables)
+hipError_t mixed_init(sgx_ctx *c)
 {
-    auto *t = static_cast<mix::MixTables *>(tables);
-    if (!t) return;
-    if (t->half) mixed_destroy(t->half);
-    if (t->d_split) (void)hipFree(t->d_split);
-    if (t->d_tw) (void)hipFree(t->d_tw);
-    if (t->d_twr) (void)hipFree(t->d_twr);
-    delete t;
+    TablesPtr<mix::MixTables> t;
+    hipError_t e = build_tables(c->P, false, t);
+    if (e != hipSuccess) return e;
+    if (c->C == 1 && c->W >= 8) {   // a mono stream: the W-point plan of real-input mode, where W has one
+        e = build_tables(c->W, true, t->half);
+        if (e != hipSuccess && e != hipErrorInvalidValue) return e;
+    }
+    c->mix = std::move(t);
+    return hipSuccess;
 }
 
+hipError_t mixed_length_tables(uint32_t n, TablesPtr<mix::MixTables> &out) { return build_tables(n, false, out); }
+
+uint32_t mixed_fixed_plan(const sgx_ctx *c) { return c->mix ? (uint32_t)c->mix->fixed : 0u; }
+
 // a mono stream whose frames each get their own transform (the default; SGX_FLAG_COMPLEX_MONO: as (s, s) through the 2W-point plan)
-bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels)
+bool mixed_real_serves(const sgx_ctx *c, uint32_t channels)
 {
-    const auto *t = static_cast<const mix::MixTables *>(tables);
+    const mix::MixTables *t = c->mix.get();
     return t && t->half && channels == 1 && !(c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && !(c->cfg.flags & SGX_FLAG_COMPLEX_MONO);
 }
 
@@ -437,7 +404,7 @@ bool mixed_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels)
 // (the palette conditions: the bands instantiations have no palette and fuse without them)
 static bool fused_palette(const sgx_ctx *c)
 {
-    return !c->pal.stereo && !c->pal.segments && c->pal.n == 256 && c->d_pal_seed && wg4096_seed_is_within_one(c);
+    return !c->pal.stereo && !c->pal.segments && c->pal.n == 256 && c->d_pal_seed.get() && wg4096_seed_is_within_one(c);
 }
 
 static bool real_two_frames(int fixed)   // real-input mode to pixels or bands: two frames per workgroup at this plan
@@ -482,19 +449,19 @@ static bool real_fuses_bands(const sgx_ctx *c, const mix::MixTables *t)
     return real_column_fits(c, t) && mix::bands_kernel_exists(t->half->fixed, true, real_two_frames(t->half->fixed));
 }
 
-bool mixed_can_fuse_render(const sgx_ctx *c, const void *tables)
+bool mixed_can_fuse_render(const sgx_ctx *c)
 {
-    const auto *t = static_cast<const mix::MixTables *>(tables);
+    const mix::MixTables *t = c->mix.get();
     // (a mono stream that real-input mode cannot take to pixels goes the two-kernel route on real-input ROWS, not through the 2W-point
     // plan as an (s, s) frame: the pixels of a context are those of its rows)
-    if (mixed_real_serves(c, tables, c->C)) return real_fuses_render(c, t);
+    if (mixed_real_serves(c, c->C)) return real_fuses_render(c, t);
     return fused_palette(c) && mixed_column_fits(c, t);
 }
 
-bool mixed_can_fuse_bands(const sgx_ctx *c, const void *tables)
+bool mixed_can_fuse_bands(const sgx_ctx *c)
 {
-    const auto *t = static_cast<const mix::MixTables *>(tables);
-    if (mixed_real_serves(c, tables, c->C)) return real_fuses_bands(c, t);
+    const mix::MixTables *t = c->mix.get();
+    if (mixed_real_serves(c, c->C)) return real_fuses_bands(c, t);
     return mixed_column_fits(c, t) && mix::bands_kernel_exists(t->fixed, false, false);
 }
 
@@ -538,7 +505,6 @@ static hipError_t launch_chunks(const sgx_ctx *c, mix::Params &p, float *d_mags,
 hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call)
 {
     if (call.kind == Out::kPeak) return hipErrorInvalidValue;
-    const void *tables = c->d_mix;
     const float *d_pcm = call.pcm;
     const uint32_t channels = call.channels, pairs = call.pairs;
     const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
@@ -547,10 +513,10 @@ hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call)
     float *d_mags = d_rgba ? nullptr : static_cast<float *>(call.out);
     using namespace mix;
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const MixTables *>(tables);
+    const MixTables *t = c->mix.get();
     // a mono stream, every frame its own transform (the default): real-input mode on the W-point plan, where there is one
-    const bool real = mixed_real_serves(c, tables, channels) && (!d_rgba || (band_means ? real_fuses_bands(c, t) : real_fuses_render(c, t)));
-    if (real) t = t->half;
+    const bool real = mixed_real_serves(c, channels) && (!d_rgba || (band_means ? real_fuses_bands(c, t) : real_fuses_render(c, t)));
+    if (real) t = t->half.get();
     Params p{};
     if (d_rgba) {
         p.render = 1;
@@ -558,19 +524,19 @@ hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call)
         p.R = c->R;
         p.n_samples = (uint32_t)c->tab.samples.size();
         p.interp = c->cfg.interp;
-        p.rows = c->d_rows;
-        p.samples = c->d_samples;
-        p.pal = c->d_pal_seed;
+        p.rows = c->d_rows.get();
+        p.samples = c->d_samples.get();
+        p.pal = c->d_pal_seed.get();
         if (!band_means) lut_seed_coefficients(c, p.guess_a, p.guess_b);
     }
     p.pcm = d_pcm;
-    p.window = c->d_window;
-    p.tw = t->d_tw;
-    p.split = t->d_split;
+    p.window = c->d_window.get();
+    p.tw = t->d_tw.get();
+    p.split = t->d_split.get();
     p.W = c->W;
     p.P = real ? c->W : c->P;
     p.real = real ? 1u : 0u;
-    p.twr = t->d_twr;
+    p.twr = t->d_twr.get();
     p.H = c->H;
     p.C = channels;
     p.pairs = pairs;
@@ -692,7 +658,7 @@ bool chirpz_supported(uint32_t W)
 
 // Tables of the chirp-z transform of P points out of nz non-zero inputs (2W and W for an (l, r) frame; real: W and ceil(W / 2) sample
 // pairs, with the untangling twiddles w_2P^k).  hipErrorInvalidValue: no plan for the convolution length.
-static hipError_t build_chirp(uint32_t P, uint32_t nz, bool real, mix::ChirpTables **out)
+static hipError_t build_chirp(uint32_t P, uint32_t nz, bool real, TablesPtr<mix::ChirpTables> &out)
 {
     using namespace mix;
     const uint32_t L = real ? conv_length(P, nz) : chirp_length(nz);
@@ -704,7 +670,7 @@ static hipError_t build_chirp(uint32_t P, uint32_t nz, bool real, mix::ChirpTabl
     CHIRP_PLANS4(X)
 #undef X
     if (radix.empty()) return hipErrorInvalidValue;
-    auto *t = new ChirpTables();
+    TablesPtr<ChirpTables> t(new ChirpTables());
     t->L = L;
     t->lds_points = L + L / 16;
     auto padpos = [](uint32_t i) { return i + i / 16; };
@@ -716,16 +682,7 @@ static hipError_t build_chirp(uint32_t P, uint32_t nz, bool real, mix::ChirpTabl
         ms[i] = ns / radix[i];
         if (ms[i] > 1)
             for (uint32_t j = 0; j < ms[i]; ++j)
-                for (uint32_t k = 1; k < radix[i]; ++k) {
-                    const unsigned long long e = ((unsigned long long)j * k) % ns;
-                    const double ang = -2.0 * M_PI * (double)e / (double)ns;
-                    double cs = cos(ang), sn = sin(ang);
-                    if (e == 0) { cs = 1.0; sn = 0.0; }
-                    if (4 * e == ns) { cs = 0.0; sn = -1.0; }
-                    if (2 * e == ns) { cs = -1.0; sn = 0.0; }
-                    if (4 * e == 3ull * ns) { cs = 0.0; sn = 1.0; }
-                    tw.push_back(make_float2((float)cs, (float)sn));
-                }
+                for (uint32_t k = 1; k < radix[i]; ++k) tw.push_back(unit_root2((unsigned long long)j * k, ns));
         ns = ms[i];
     }
     std::vector<float2> chirp(P), bhat(t->lds_points, make_float2(0.0f, 0.0f));
@@ -749,14 +706,9 @@ static hipError_t build_chirp(uint32_t P, uint32_t nz, bool real, mix::ChirpTabl
         }
         bhat[padpos(at)] = make_float2((float)(br[K] / (double)L), (float)(bi[K] / (double)L));
     }
-    auto up = [](float2 **dst, const std::vector<float2> &v) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(&t->d_chirp, chirp);
-    if (e == hipSuccess) e = up(&t->d_bhat, bhat);
-    if (e == hipSuccess) e = up(&t->d_tw, tw);
+    hipError_t e = t->d_chirp.upload(chirp);
+    if (e == hipSuccess) e = t->d_bhat.upload(bhat);
+    if (e == hipSuccess) e = t->d_tw.upload(tw);
     if (e == hipSuccess && real) {
         std::vector<float2> twr(std::max<uint32_t>(P / 2, 1));
         for (uint32_t j = 0; j < P / 2; ++j) {
@@ -764,48 +716,29 @@ static hipError_t build_chirp(uint32_t P, uint32_t nz, bool real, mix::ChirpTabl
             const double ang = -M_PI * (double)k / (double)P;
             twr[j] = 2 * k == P ? make_float2(0.0f, -1.0f) : make_float2((float)cos(ang), (float)sin(ang));
         }
-        e = up(&t->d_twr, twr);
+        e = t->d_twr.upload(twr);
     }
-    if (e != hipSuccess) {
-        chirpz_destroy(t);
-        return e;
-    }
-    *out = t;
-    return hipSuccess;
+    if (e == hipSuccess) out = std::move(t);
+    return e;
 }
 
-hipError_t chirpz_init(sgx_ctx *c, void **out)
+hipError_t chirpz_init(sgx_ctx *c)
 {
-    mix::ChirpTables *t = nullptr;
-    hipError_t e = build_chirp(c->P, c->W, false, &t);
+    TablesPtr<mix::ChirpTables> t;
+    hipError_t e = build_chirp(c->P, c->W, false, t);
     if (e != hipSuccess) return e;
     if (c->C == 1) {   // a mono stream: real-input mode
-        e = build_chirp(c->W, (c->W + 1) / 2, true, &t->half);
-        if (e != hipSuccess && e != hipErrorInvalidValue) {
-            chirpz_destroy(t);
-            return e;
-        }
+        e = build_chirp(c->W, (c->W + 1) / 2, true, t->half);
+        if (e != hipSuccess && e != hipErrorInvalidValue) return e;
     }
-    *out = t;
+    c->chz = std::move(t);
     return hipSuccess;
 }
 
-bool chirpz_real_serves(const sgx_ctx *c, const void *tables, uint32_t channels)
+bool chirpz_real_serves(const sgx_ctx *c, uint32_t channels)
 {
-    const auto *t = static_cast<const mix::ChirpTables *>(tables);
+    const mix::ChirpTables *t = c->chz.get();
     return t && t->half && channels == 1 && !(c->cfg.flags & SGX_FLAG_PAIRED_FRAMES) && !(c->cfg.flags & SGX_FLAG_COMPLEX_MONO);
-}
-
-void chirpz_destroy(void *tables)
-{
-    auto *t = static_cast<mix::ChirpTables *>(tables);
-    if (!t) return;
-    if (t->half) chirpz_destroy(t->half);
-    if (t->d_twr) (void)hipFree(t->d_twr);
-    if (t->d_chirp) (void)hipFree(t->d_chirp);
-    if (t->d_bhat) (void)hipFree(t->d_bhat);
-    if (t->d_tw) (void)hipFree(t->d_tw);
-    delete t;
 }
 
 hipError_t launch_chirpz(const sgx_ctx *c, const StftCall &call)
@@ -813,22 +746,21 @@ hipError_t launch_chirpz(const sgx_ctx *c, const StftCall &call)
     using namespace mix;
     if (call.kind != Out::kMags && call.kind != Out::kComplex) return hipErrorInvalidValue;
     const bool complex_rows = call.kind == Out::kComplex;
-    const void *tables = c->d_chz;
     const float *d_pcm = call.pcm;
     float *d_mags = static_cast<float *>(call.out);
     const uint32_t channels = call.channels, pairs = call.pairs;
     const size_t first_frame = call.first, n_frames = call.n, total_frames = call.total;
     if (n_frames == 0) return hipSuccess;
-    const auto *t = static_cast<const ChirpTables *>(tables);
-    const bool real = chirpz_real_serves(c, tables, channels);   // a mono stream, every frame its own transform (the default)
-    if (real) t = t->half;
+    const ChirpTables *t = c->chz.get();
+    const bool real = chirpz_real_serves(c, channels);   // a mono stream, every frame its own transform (the default)
+    if (real) t = t->half.get();
     Params p{};
     p.pcm = d_pcm;
-    p.window = c->d_window;
-    p.tw = t->d_tw;
-    p.chirp = t->d_chirp;
-    p.bhat = t->d_bhat;
-    p.twr = t->d_twr;
+    p.window = c->d_window.get();
+    p.tw = t->d_tw.get();
+    p.chirp = t->d_chirp.get();
+    p.bhat = t->d_bhat.get();
+    p.twr = t->d_twr.get();
     p.real = real ? 1u : 0u;
     p.W = c->W;
     p.P = real ? c->W : c->P;

@@ -50,14 +50,14 @@ constexpr int kMaxStages = 8;
 constexpr uint32_t kMaxRadix = 28;
 
 struct MixTables {
-    uint32_t *d_split = nullptr;  // [M] padded position of bin k | padded position of bin P - k << 16   (k = j + 1)
-    float2 *d_tw = nullptr;       // per stage: [m][R - 1] w_Ns^{j k}
+    DeviceBuffer<uint32_t> d_split;  // [M] padded position of bin k | padded position of bin P - k << 16   (k = j + 1)
+    DeviceBuffer<float2> d_tw;       // per stage: [m][R - 1] w_Ns^{j k}
     uint32_t n_stages = 0, pad_every = 0, lds_points = 0, threads = 0;
     int fixed = 0;                // P when the host's plan is the compile-time one of a fixed kernel (MIX_FIXED_PLANS), else 0
     // real-input mode (a mono stream, every frame its own transform): the plan of the W-point transform of z[m] = x[2m] + i x[2m+1]
     // with its own d_split ([W / 2]: positions of Z[k] and Z[W - k], k = j + 1) and the untangling twiddles w_2W^k
-    MixTables *half = nullptr;
-    float2 *d_twr = nullptr;
+    TablesPtr<MixTables> half;
+    DeviceBuffer<float2> d_twr;
     uint32_t ra[kMaxStages] = {}, rb[kMaxStages] = {}, m[kMaxStages] = {}, tw_off[kMaxStages] = {};
     uint32_t q_stride[kMaxStages] = {}, blk_stride[kMaxStages] = {};   // padded LDS positions: see stage()
     float inv_m[kMaxStages] = {};
