@@ -13,7 +13,7 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_fbank_batch, sgx_fbank_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
  *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -353,6 +353,46 @@ SGX_API int sgx_fbank_mags(void *fbank, const float *d_mags, size_t n_columns, f
  * SGX_FLAG_PAIRED_FRAMES, SGX_FLAG_COMPLEX_MONO or SGX_FLAG_FORCE_GENERIC, for banks of at most 1024 filters and 16384 weights (a 128-
  * or 256-filter mel bank has about 4000).  Every other window, flag and bank: the workspace route.  Same bits either way. */
 SGX_API int sgx_fbank_fused(const void *fbank);
+
+/* The cross sums of a bank: per band what a stereo analyser needs of an (l, r) pair, with the phase that magnitudes lose.
+ * For a bank on a context with at least two channels, per frame, (l, r) pair and stored bin j take a = L.re, b = L.im, c = R.re,
+ * d = R.im: exactly the float32 words that sgx_stft_batch_complex stores for that frame, pair and bin.  Then
+ *
+ *     x0 = rn(rn(a * a) + rn(b * b))      |L|^2
+ *     x1 = rn(rn(c * c) + rn(d * d))      |R|^2
+ *     x2 = rn(rn(a * c) + rn(b * d))      Re L conj R
+ *     x3 = rn(rn(b * c) - rn(a * d))      Im L conj R
+ *
+ * every product rounded to float32, then the sum or difference rounded once: no contraction into a fused multiply-add.  Bitwise-equal L
+ * and R therefore give x0 = x1 = x2 and x3 = +0 exactly, and float32 arithmetic on the host reproduces x bit for bit.  The output is
+ *
+ *     out[f][q] = sum_{i < count[f]} w[f][i] * x_q[first[f] + i],    q = 0 .. 3
+ *
+ * summed in the order defined above for sgx_fbank_batch (the 64 chains from +0, then the tree by halving).  The bank's power plays
+ * no part.  An empty filter gives four +0.0f.  The output is a pure function of the frame's complex row and the bank: bit-identical across
+ * routes, sub-ranges, chunk seams, compute-unit limits and streams (tests/test_gpu_fbank_cross.py).
+ * What a caller derives from the four sums of a band (none of it is computed here; the division by small band energies is the caller's to guard):
+ *   the inter-channel phase is atan2(out3, out2);
+ *   the correlation is out2 / sqrt(out0 * out1);
+ *   the coherence is (out2 * out2 + out3 * out3) / (out0 * out1);
+ *   the mid and side energies are out0 + out1 + 2 * out2 and out0 + out1 - 2 * out2.
+ *
+ * sgx_fbank_cross_batch: PCM to the four sums for every frame of the hop loop.
+ *   d_out [n_out][pairs][n_filters][4] float, 16-byte aligned.
+ * first_frame / max_frames / *n_out as sgx_fbank_batch: too few samples is *n_out = 0, not an error; a null buffer is
+ * SGX_ERR_INVALID_ARG; a bank whose context is gone answers SGX_ERR_INVALID_ARG.  On a mono context: SGX_ERR_UNSUPPORTED (there L = R
+ * and the answer is x0, x0, x0, 0).  Stream-ordered and asynchronous; nothing waits on the host.  Device memory beyond the caller's
+ * buffers is bounded as for sgx_fbank_batch (the complex rows take 16 B per bin: a chunk of the workspace route holds half as many frames). */
+SGX_API int sgx_fbank_cross_batch(void *fbank, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                                  float *d_out, size_t *n_out);
+/* The stage alone: d_spec [n_columns][M][2][2], what sgx_stft_batch_complex writes -> d_out [n_columns][n_filters][4] (both 16-byte
+ * aligned).  Every W the library accepts, every bank, any channel count: mono rows are served like any other. */
+SGX_API int sgx_fbank_cross_spec(void *fbank, const float *d_spec, size_t n_columns, float *d_out);
+/* 1: sgx_fbank_cross_batch runs one kernel from PCM to sums for this bank on its context; 0: the workspace route (the complex rows of a
+ * chunk of frames by their own route, then the stage kernel), and every mono context; < 0: error.
+ * One kernel: W = 2048 with 2 or 2k channels (any hop), without SGX_FLAG_NO_FUSED_RENDER or SGX_FLAG_FORCE_GENERIC, for banks within
+ * the size sgx_fbank_fused states.  Same bits either way. */
+SGX_API int sgx_fbank_cross_fused(const void *fbank);
 
 /* The triangular mel bank as sgx_fbank_create takes it.  Host only: no context, no device.
  * Over the TRUE bin frequencies f_k = k * sample_rate / (2W), k = 1 .. W - 1 (stored element j = k - 1) -- deliberately not the axis of

@@ -420,6 +420,23 @@ public:
         const int rc = sgx_fbank_mags(bank_, d_mags, n_columns, d_out);
         if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
     }
+    // The cross sums (sgx_fbank_cross_*): per band the sums of |L|^2, |R|^2, Re and Im of L conj R over the complex rows of an (l, r) pair.
+    bool cross_fused() const { return sgx_fbank_cross_fused(bank_) == 1; }
+    // device to device: PCM -> [frames][pairs][filters][4]; returns the frames written
+    std::size_t cross_batch(const float *d_pcm, std::size_t n_samples, float *d_out, std::size_t first_frame = 0,
+                            std::size_t max_frames = (std::size_t)-1)
+    {
+        std::size_t got = 0;
+        const int rc = sgx_fbank_cross_batch(bank_, d_pcm, n_samples, first_frame, max_frames, d_out, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
+        return got;
+    }
+    // the stage alone: [columns][M][2][2] complex rows -> [columns][filters][4]
+    void cross_apply(const float *d_spec, std::size_t n_columns, float *d_out)
+    {
+        const int rc = sgx_fbank_cross_spec(bank_, d_spec, n_columns, d_out);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
+    }
     sgx_fbank *raw() const { return bank_; }
 
 private:

@@ -222,7 +222,7 @@ struct Route { Family family; bool fused, real_input; };
 // the CONTEXT's channel count (wg4096_can_fuse_*, mixed_can_fuse_* read c->C: the tables they test were built for it).  Only the batch entry
 // points ask for a column, and their channel count is the context's, so one `channels` serves both here; the queries (sgx_query,
 // sgx_bands_fused, sgx_bands_peak_fused) pass c->C.
-// `bank` (Out::kFbank): the filterbank of the call; its size decides with the context.
+// `bank` (Out::kFbank, Out::kFbankCross): the filterbank of the call; its size decides with the context.
 Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank *bank = nullptr)
 {
     const bool mixed = c->stft_kernel == sgx::kKernelMixed || c->stft_kernel == sgx::kKernelW4800;
@@ -274,6 +274,9 @@ Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank 
     case Out::kFbank:     // in one kernel at W 2048 where every frame is its own transform and the bank is within the stated size
         fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_fbank(c, bank);
         break;
+    case Out::kFbankCross:   // likewise, on a stream of (l, r) pairs
+        fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_fbank_cross(c, bank);
+        break;
     }
     rows.fused = fused;
     return rows;
@@ -317,20 +320,22 @@ int ensure_workspace(sgx_ctx *c, size_t frames)
     return e == hipSuccess ? SGX_OK : fail_hip(c, e, "hipMalloc(render workspace)");
 }
 
-// n frames in chunks whose magnitudes fit the workspace: body(done, m) runs frames [done, done + m) of the call and returns an SGX code
+// n frames in chunks whose magnitudes fit the workspace: body(done, m) runs frames [done, done + m) of the call and returns an SGX code.
+// rows_per_frame 2: chunks whose complex rows fit (16 B per bin: two magnitude rows' bytes, half as many frames)
 template <typename Body>
-int in_workspace_chunks(sgx_ctx *c, size_t n, Body body)
+int in_workspace_chunks(sgx_ctx *c, size_t n, Body body, size_t rows_per_frame = 1)
 {
-    const size_t chunk = workspace_chunk(mags_bytes_per_frame(c), n);
-    int rc = ensure_workspace(c, chunk);
+    const size_t chunk = workspace_chunk(mags_bytes_per_frame(c) * rows_per_frame, n);
+    int rc = ensure_workspace(c, chunk * rows_per_frame);
     for (size_t done = 0; rc == SGX_OK && done < n; done += chunk) rc = body(done, n - done < chunk ? n - done : chunk);
     return rc;
 }
 
 // The rows of frames [first, first + m) into the workspace (the caller has grown it to m frames), for the second kernel of a two-kernel route
-hipError_t rows_to_workspace(const sgx_ctx *c, const float *d_pcm, size_t first, size_t m, size_t total)
+// (kind: Out::kMags, or Out::kComplex for the complex rows)
+hipError_t rows_to_workspace(const sgx_ctx *c, const float *d_pcm, size_t first, size_t m, size_t total, Out kind = Out::kMags)
 {
-    return run_call(c, stft_route(c, c->C, Out::kMags), d_pcm, first, m, total, c->d_ws_mags.get(), Out::kMags);
+    return run_call(c, stft_route(c, c->C, kind), d_pcm, first, m, total, c->d_ws_mags.get(), kind);
 }
 
 // What sgx_bands_batch runs on frames [first, first + m): the fused kernel of its route, or the rows into the workspace (m frames fit: the
@@ -875,6 +880,59 @@ int sgx_fbank_batch(void *bank, const float *d_pcm, size_t n_samples, size_t fir
             e = sgx::launch_fbank_stage(c, fb, c->d_ws_mags.get(), m * c->pairs, d_out + done * (size_t)c->pairs * fb->n_filters * 2);
             return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_fbank_batch: filter launch");
         });
+        if (rc != SGX_OK) return rc;
+    }
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+// ---- the cross sums of a bank: |L|^2, |R|^2, Re and Im of L conj R per band (sgx_fbank.hpp: cross_filter_pass) ---------------------------
+
+int sgx_fbank_cross_fused(const void *bank)
+{
+    const sgx_fbank *fb = static_cast<const sgx_fbank *>(bank);
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    return stft_route(fb->ctx, fb->ctx->C, Out::kFbankCross, fb).fused ? 1 : 0;
+}
+
+int sgx_fbank_cross_spec(void *bank, const float *d_spec, size_t n_columns, float *d_out)
+{
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    sgx_ctx *c = fb->ctx;
+    if (n_columns == 0) return SGX_OK;
+    if (!d_spec || !d_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_fbank_cross_spec: null buffer");
+    if (((uintptr_t)d_spec | (uintptr_t)d_out) & 15u) return fail(c, SGX_ERR_INVALID_ARG, "sgx_fbank_cross_spec: buffers must be 16-byte aligned");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = sgx::launch_fbank_cross_stage(c, fb, d_spec, n_columns, d_out);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_cross_spec: kernel launch");
+    return SGX_OK;
+}
+
+int sgx_fbank_cross_batch(void *bank, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, float *d_out, size_t *n_out)
+{
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (n_out) *n_out = 0;
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    sgx_ctx *c = fb->ctx;
+    if (c->C < 2) return fail(c, SGX_ERR_UNSUPPORTED, "sgx_fbank_cross_batch: a mono context has no (l, r) pair (L = R: the sums are x0, x0, x0, 0)");
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_fbank_cross_batch", n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    if ((uintptr_t)d_out & 15u) return fail(c, SGX_ERR_INVALID_ARG, "sgx_fbank_cross_batch: d_out must be 16-byte aligned");
+    const Route r = stft_route(c, c->C, Out::kFbankCross, fb);
+    if (r.fused) {
+        // one kernel from PCM to the four sums: L and R stay in registers, their products in LDS, 16 B per filter leave the kernel
+        const hipError_t e = launch_family(c, r.family, StftCall{d_pcm, c->C, c->pairs, first_frame, n, total, d_out, Out::kFbankCross, 0, fb});
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_cross_batch: fused launch");
+    } else {
+        // two kernels: the complex rows of a chunk of frames in the bounded workspace, by the rows' own route, then the cross stage over them
+        rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+            hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total, Out::kComplex);
+            if (e != hipSuccess) return fail_hip(c, e, "sgx_fbank_cross_batch: stft launch");
+            e = sgx::launch_fbank_cross_stage(c, fb, c->d_ws_mags.get(), m * c->pairs, d_out + done * (size_t)c->pairs * fb->n_filters * 4);
+            return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_fbank_cross_batch: filter launch");
+        }, 2);
         if (rc != SGX_OK) return rc;
     }
     if (n_out) *n_out = n;

@@ -1,6 +1,7 @@
 // sgx_fbank.hip -- the filterbank stage on rows in device memory: [columns][M][2] magnitudes -> [columns][n_filters][2] weighted sums
 // (include/sgx.h: sgx_fbank_mags, and the second kernel of sgx_fbank_batch's workspace route).  The filter pass itself is
-// sgx_fbank.hpp's, shared with the fused modes of the 4096-point kernels.
+// sgx_fbank.hpp's, shared with the fused modes of the 4096-point kernels.  The cross stage (sgx_fbank_cross_spec, and the second kernel of
+// sgx_fbank_cross_batch's workspace route): [columns][M][2][2] complex rows -> [columns][n_filters][4] sums of the (L, R) products.
 #include "sgx_fbank.hpp"
 
 namespace sgx {
@@ -56,6 +57,68 @@ hipError_t launch_fbank_stage(const sgx_ctx *c, const sgx_fbank *fb, const float
         FbankStageParams q = p;
         q.mags = d_mags + done * (size_t)c->M * 2;
         q.out = d_out + done * (size_t)fb->n_filters * 2;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+struct FbankCrossStageParams {
+    const float *spec;             // [columns][M][2][2]: (L.re, L.im, R.re, R.im) per bin
+    const fbank::Filter *filters;
+    const float *weights;
+    float *out;                    // [columns][n_filters][4]
+    uint32_t M, n_filters;
+};
+
+// One workgroup per column.  STAGED: the four products of every bin are formed once, on the way into two float2 columns in LDS; a column
+// that no LDS holds is read where it lies and the products are formed at every read.
+template <bool STAGED>
+__global__ void __launch_bounds__(256) fbank_cross_stage_kernel(FbankCrossStageParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float2 *c01 = reinterpret_cast<float2 *>(smem_raw), *c23 = c01 + p.M;
+    const uint32_t tid = threadIdx.x;
+    const size_t col = blockIdx.x;
+    const float4 *src = reinterpret_cast<const float4 *>(p.spec) + col * p.M;
+    float4 *dst = reinterpret_cast<float4 *>(p.out) + col * p.n_filters;
+    if (STAGED) {
+        for (uint32_t i = tid; i < p.M; i += 256u) {
+            const float4 s = src[i];
+            fbank::cross_terms(s.x, s.y, s.z, s.w, c01[i], c23[i]);
+        }
+        __syncthreads();
+        fbank::cross_filter_pass(fbank::CrossColumns{c01, c23}, p.filters, p.weights, p.n_filters, dst, tid, 4u);
+    } else {
+        fbank::cross_filter_pass(fbank::CrossRows{src}, p.filters, p.weights, p.n_filters, dst, tid, 4u);
+    }
+}
+
+hipError_t launch_fbank_cross_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_spec, size_t n_columns, float *d_out)
+{
+    if (n_columns == 0) return hipSuccess;
+    FbankCrossStageParams p;
+    p.spec = d_spec;
+    p.filters = fb->d_filters.get();
+    p.weights = fb->d_weights.get();
+    p.out = d_out;
+    p.M = c->M;
+    p.n_filters = fb->n_filters;
+    const size_t lds_cap = c->lds_optin < (size_t)160 * 1024 ? c->lds_optin : (size_t)160 * 1024;
+    const bool staged = (size_t)c->M * 2 * sizeof(float2) <= lds_cap;
+    const size_t lds = staged ? (size_t)c->M * 2 * sizeof(float2) : 0;
+    const auto kernel = staged ? fbank_cross_stage_kernel<true> : fbank_cross_stage_kernel<false>;
+    if (lds > 64 * 1024) {   // per launch: the attribute is per device, and a process may hold contexts on several
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const size_t max_chunk = 1u << 30;
+    for (size_t done = 0; done < n_columns; done += max_chunk) {
+        const size_t chunk = n_columns - done < max_chunk ? n_columns - done : max_chunk;
+        FbankCrossStageParams q = p;
+        q.spec = d_spec + done * (size_t)c->M * 4;
+        q.out = d_out + done * (size_t)fb->n_filters * 4;
         hipLaunchKernelGGL(kernel, dim3((unsigned)chunk), dim3(256), lds, c->stream, q);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

@@ -1,6 +1,7 @@
 // sgx_fbank.hpp -- the filter pass of the filterbank calls (include/sgx.h: sgx_fbank_batch, sgx_fbank_mags): one body for the stage kernel
 // (sgx_fbank.hip) and for the fused modes of the two 4096-point kernels (stft4096_wg.hip, stft4096_real.hip), so that a bank's output
-// is the same bits on every route.
+// is the same bits on every route.  The cross pass (sgx_fbank_cross_batch, sgx_fbank_cross_spec) is the same order over the four
+// products of a bin's (L, R) pair, one trip over the bank for all four.
 //
 // A wave per filter.  Lane l takes the filter's elements i = l, l + 64, l + 128, ... in ascending order into one fused-multiply-add
 // chain from +0; the 64 partial sums then meet in a halving tree (a[l] + a[l + 32], then + 16, 8, 4, 2, 1).  That order is the
@@ -27,6 +28,8 @@ namespace sgx {
 
 hipError_t launch_fbank_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_mags, size_t n_columns, float *d_out);   // sgx_fbank.hip
 bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb);   // stft4096_wg.hip
+hipError_t launch_fbank_cross_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_spec, size_t n_columns, float *d_out);   // sgx_fbank.hip
+bool wg4096_can_fuse_fbank_cross(const sgx_ctx *c, const sgx_fbank *fb);   // stft4096_wg.hip
 void detach_fbanks(sgx_ctx *c);   // sgx_fbank.hip
 
 #ifdef __HIPCC__
@@ -134,6 +137,101 @@ __device__ __forceinline__ void filter_pass(const float2 *col, const Filter *fil
                     dst_a[f] = make_float2(kx, ky);
                 }
             }
+        }
+    }
+}
+
+// ---- the cross pass: per band the sums of |L|^2, |R|^2, Re L conj R, Im L conj R (include/sgx.h: sgx_fbank_cross_batch) -----------------
+
+// The four products of one bin, L = (a, b), R = (c, d), as the header defines them: every product rounded, then one add or subtract --
+// never contracted into a fused multiply-add, whatever the build says.  (x0, x1) and (x2, x3) are the elements of the two columns.
+__device__ __forceinline__ void cross_terms(float a, float b, float c, float d, float2 &x01, float2 &x23)
+{
+#pragma clang fp contract(off)
+    x01.x = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));   // |L|^2
+    x01.y = __fadd_rn(__fmul_rn(c, c), __fmul_rn(d, d));   // |R|^2
+    x23.x = __fadd_rn(__fmul_rn(a, c), __fmul_rn(b, d));   // Re L conj R
+    x23.y = __fsub_rn(__fmul_rn(b, c), __fmul_rn(a, d));   // Im L conj R
+}
+
+// Where the cross pass reads element j from: two float2 columns of products (LDS), or the complex rows where they lie (a column no LDS
+// holds: the products are formed at every read -- the same bits, cross_terms is a pure function of the row's words)
+struct CrossColumns {
+    const float2 *c01, *c23;
+    __device__ __forceinline__ void operator()(uint32_t j, float2 &x01, float2 &x23) const { x01 = c01[j]; x23 = c23[j]; }
+};
+struct CrossRows {
+    const float4 *row;   // [M] (L.re, L.im, R.re, R.im)
+    __device__ __forceinline__ void operator()(uint32_t j, float2 &x01, float2 &x23) const
+    {
+        const float4 s = row[j];
+        cross_terms(s.x, s.y, s.z, s.w, x01, x23);
+    }
+};
+
+// filter_pass for the four components at once: one trip over the bank -- the table entries and the weights of a group of filters are
+// loaded once, the element comes from two float2 columns, two chain pairs run side by side and two trees close each filter.  Per
+// component the order is filter_pass's (64 chains from +0 over i = l, l + 64, ..., then wave_tree2's halving tree), so the bits are the
+// definition's.  dst[f] = (out0, out1, out2, out3).  All lanes of the wave must be active.
+template <typename Col>
+__device__ __forceinline__ void cross_filter_pass(const Col &col, const Filter *filters, const float *weights, uint32_t n_filters, float4 *dst,
+                                                  uint32_t tid, uint32_t n_waves)
+{
+    constexpr uint32_t G = 4;   // filters a wave takes per trip, as filter_pass
+    static_assert(64 % G == 0, "a batch of results never straddles two groups of filters");
+    asm volatile("" : "+v"(tid));   // (opaque, as in filter_pass)
+    const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t n_mine = n_filters > wave ? (n_filters - wave + n_waves - 1u) / n_waves : 0u;   // this wave's filters: wave + k n_waves, k < n_mine
+    const const_u4_ptr table = (const_u4_ptr)(unsigned long long)filters;
+    float4 kept = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (uint32_t k0 = 0; k0 < n_mine; k0 += G) {
+        uint32_t first[G], count[G], offset[G];
+        float w[G];
+        float2 v01[G], v23[G];
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            const bool valid = k0 + g < n_mine;
+            const fbank_u32x4 q = table[wave + (size_t)(valid ? k0 + g : k0) * n_waves];
+            first[g] = q.x;
+            count[g] = valid ? q.y : 0u;
+            offset[g] = q.z;
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            w[g] = 0.0f;
+            v01[g] = v23[g] = make_float2(0.0f, 0.0f);
+            if (lane < count[g]) {
+                w[g] = weights[(size_t)offset[g] + lane];
+                col(first[g] + lane, v01[g], v23[g]);
+            }
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+            if (lane < count[g]) {
+                a0 = fmaf(w[g], v01[g].x, a0);
+                a1 = fmaf(w[g], v01[g].y, a1);
+                a2 = fmaf(w[g], v23[g].x, a2);
+                a3 = fmaf(w[g], v23[g].y, a3);
+                for (uint32_t i = lane + 64u; i < count[g]; i += 64u) {   // filters of more than 64 bins: the lane's chains go on
+                    const float wi = weights[(size_t)offset[g] + i];
+                    float2 x01, x23;
+                    col(first[g] + i, x01, x23);
+                    a0 = fmaf(wi, x01.x, a0);
+                    a1 = fmaf(wi, x01.y, a1);
+                    a2 = fmaf(wi, x23.x, a2);
+                    a3 = fmaf(wi, x23.y, a3);
+                }
+            }
+            float s0, s1, s2, s3;
+            wave_tree2(a0, a1, s0, s1);
+            wave_tree2(a2, a3, s2, s3);
+            if (lane == ((k0 + g) & 63u)) kept = make_float4(s0, s1, s2, s3);
+        }
+        const uint32_t k_end = k0 + G < n_mine ? k0 + G : n_mine;
+        if ((k_end & 63u) == 0u || k_end == n_mine) {   // (wave-uniform) a full wave of results, or the last ones
+            const uint32_t k = ((k_end - 1u) & ~63u) + lane;   // this lane's filter of the wave
+            if (k < k_end) dst[wave + (size_t)k * n_waves] = kept;
         }
     }
 }

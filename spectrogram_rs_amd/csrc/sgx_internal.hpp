@@ -196,11 +196,12 @@ namespace sgx {
 // What the call writes: magnitude pairs [F][pairs][M][2] floats, the same as half pairs (4 B per bin), the complex rows of
 // sgx_stft_batch_complex [F][pairs][M][2][2] floats, or the fused column: RGBA pixels [F][pairs][R][4] bytes, the rows' (l, r) means as
 // float2 [F][pairs][R] (sgx_bands_batch), or those held as a maximum over groups of frames, float2 [ceil(F / group)][pairs][R]; or the
-// weighted sums of a filterbank over the magnitudes, float2 [F][pairs][n_filters] (sgx_fbank_batch).
-enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak, kFbank };
+// weighted sums of a filterbank over the magnitudes, float2 [F][pairs][n_filters] (sgx_fbank_batch), or over the four products of the
+// (L, R) pair, float4 [F][pairs][n_filters] (sgx_fbank_cross_batch).
+enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak, kFbank, kFbankCross };
 // `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index).  channels and pairs are the CALL's, not the
-// context's: sgx_process_one runs a two-channel frame (2, 1) on a context of any channel count.  peak_group (kPeak): 1 .. n.  bank (kFbank):
-// the filterbank whose sums the call writes.
+// context's: sgx_process_one runs a two-channel frame (2, 1) on a context of any channel count.  peak_group (kPeak): 1 .. n.  bank (kFbank,
+// kFbankCross): the filterbank whose sums the call writes.
 struct StftCall {
     const float *pcm;
     uint32_t channels, pairs;
@@ -213,7 +214,7 @@ struct StftCall {
 // Each X_init builds its family's tables into the context; on an error it leaves nothing behind.  Each launcher takes its tables from the
 // context, returns hipSuccess or the launch error, and hipErrorInvalidValue for an Out (or a channel count) its family has no kernel for.
 hipError_t launch_generic(const sgx_ctx *c, const StftCall &call);     // sgx_kernels.hip: kMags, kComplex
-hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call);      // stft4096_wg.hip (and stft4096_real.hip): every Out (kFbank: where wg4096_can_fuse_fbank)
+hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call);      // stft4096_wg.hip (and stft4096_real.hip): every Out (kFbank, kFbankCross: where wg4096_can_fuse_fbank / _cross)
 hipError_t launch_w16384(const sgx_ctx *c, const StftCall &call);      // stft16384_w.hip: kMags, kComplex
 hipError_t launch_w4800(const sgx_ctx *c, const StftCall &call);       // stft4800_wg.hip: kMags, kMagsF16, kComplex of one or two channels
 hipError_t launch_mixed(const sgx_ctx *c, const StftCall &call);       // stft_mixed.hip: every Out but kPeak

@@ -84,6 +84,8 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     constexpr bool F16 = PIX == kPixRowsF16;    // rows as (l, r) half pairs (compile-time: the row stores are straight-line code)
     constexpr bool FBANK = PIX == kPixFbank;    // the column in LDS, then a filterbank over it (sgx_fbank_batch): no row tables, no palette
     static_assert(!(FBANK && MONO), "paired mono frames take the workspace route of sgx_fbank_batch");
+    constexpr bool CROSS = PIX == kPixFbankCross;   // the four (L, R) products of every bin in two LDS columns, then a cross pass (sgx_fbank_cross_batch)
+    static_assert(!CROSS || (!MONO && C2), "the cross sums need a pair: (l, r) streams and pair planes only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf = reinterpret_cast<float2 *>(smem_raw);
     float2 *tw2 = buf + kBufComplex;
@@ -105,7 +107,7 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     const float4 *rd4 = reinterpret_cast<const float4 *>(plane + 272 * (tid >> 4) + 68 * ((tid & 15) >> 2) + 16 * (tid & 3));   // TR: both read sides
     tw2[tid] = p.tw2[tid];
     uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // RENDER: the table words of this thread's rows tid + 256 i
-    if (RENDER && !FBANK) {
+    if (RENDER && !FBANK && !CROSS) {
         if (!BANDS) pal[tid] = make_uint2(__float_as_uint(tid < 255 ? p.lut_thr[tid] : __builtin_nanf("")), *reinterpret_cast<const uint32_t *>(&p.lut_rgba[tid]));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -409,10 +411,14 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         // transform for the burst, profiles/r05_k1_stereo.txt; same device 5.10 -> 4.87 ms per 1e6 frames together with the sliding window)
         constexpr bool kInterleave = (!MONO && !RENDER) || C64;   // (C64: a frame pair's two rows too, sixteen stores as the burst has)
         float2 pb[8] = {};
-        if (kInterleave) {
+        if (kInterleave || CROSS) {
 #pragma unroll
             for (int q3 = 0; q3 < 8; ++q3) pb[q3] = buf[(7 - q3) * 256 + pcol];
         }
+        // (the cross sums: the products go straight from the split into their two columns, which overlie the partner rows -- every
+        // partner is in registers first, and everyone's are behind this barrier)
+        [[maybe_unused]] float2 *x01 = reinterpret_cast<float2 *>(buf), *x23 = x01 + kColSlots;   // [bin]: (|L|^2, |R|^2), (Re, Im) of L conj R
+        if constexpr (CROSS) lds_barrier();
         constexpr int kRowBin = C64 ? 16 : (F16 ? 4 : 8);   // bytes per output bin
         // (C64 frame pairs: r_il / r_il2 are the rows of frames f0 / f1, each dropped when outside the requested range)
         const __amdgpu_buffer_rsrc_t r_il = (C64 && MONO)
@@ -425,10 +431,21 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         for (int q3 = 0; q3 < 8; ++q3) {
             const int pos = FFT16_OUT[q3];
             // F[P-k]: thread 256-u holds it as q3' = 15 - q3 (row 7 - q3); thread 0 as q3' = 16 - q3
-            const float2 b = kInterleave ? pb[q3] : buf[(7 - q3) * 256 + pcol];
+            const float2 b = (kInterleave || CROSS) ? pb[q3] : buf[(7 - q3) * 256 + pcol];
             const float ar = xr[pos], ai = xi[pos];
             const float pr = ar + b.x, pi = ai - b.y;   // a + conj(b) = 2 L^
             const float qr = ar - b.x, qi = ai + b.y;   // a - conj(b) = 2i R^
+            if constexpr (CROSS) {
+                // L = (pr, pi) and R = (qi, -qr): the words the complex rows store (below).  Bin k = col + 256 q3 in slot k; k = 0 (DC) is
+                // not an output
+                float2 v01, v23;
+                fbank::cross_terms(pr, pi, qi, -qr, v01, v23);
+                if (q3 > 0 || col != 0) {
+                    x01[col + 256 * q3] = v01;
+                    x23[col + 256 * q3] = v23;
+                }
+                continue;
+            }
             if constexpr (C64) {
                 // L = (a + conj b) / 2 and R = (a - conj b) / (2i) = (qi, -qr) / 2, times 2 / W: the scale rides on the window.  Bin k =
                 // col + 256 q3 at byte 16 k of the row; k = 0 (DC) is not an output: thread 0's first stores fall outside the records
@@ -467,6 +484,14 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
                               : (MONO ? 16u : 8u);    // rows: eight store instructions per row in every wave, absent rows included (dropped by their descriptor)
         if (C64) {
             // (complex rows: stored inside the split)
+        } else if constexpr (CROSS) {
+            // one cross pass over the two product columns, a wave per filter (sgx_fbank.hpp): element j of a row is bin j + 1, slot j + 1
+            lds_barrier();
+            float4 *dst = reinterpret_cast<float4 *>(p.rgba) + ((size_t)f0 * p.pairs + p.pair) * (size_t)p.R;
+            __builtin_amdgcn_s_setprio(3);
+            fbank::cross_filter_pass(fbank::CrossColumns{x01 + 1, x23 + 1}, reinterpret_cast<const fbank::Filter *>(p.rows),
+                                     reinterpret_cast<const float *>(p.samples), p.R, dst, (uint32_t)tid, 4u);
+            next_samples_are_here();
         } else if (!RENDER) {
             // ---- store [F][pairs][M][2]: uniform row base (SGPR) + one 32-bit lane offset
             if (F16) {
@@ -732,8 +757,10 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
     if (n_frames == 0) return hipSuccess;
     WgTables *t = c->wg.get();   // (not const: the scratch below is regrown)
     const bool band_means = call.kind == Out::kBands || call.kind == Out::kPeak, column = band_means || call.kind == Out::kRgba;
-    const sgx_fbank *bank = call.kind == Out::kFbank ? call.bank : nullptr;
+    const bool cross = call.kind == Out::kFbankCross;
+    const sgx_fbank *bank = call.kind == Out::kFbank || cross ? call.bank : nullptr;
     if (call.kind == Out::kFbank && !wg4096_can_fuse_fbank(c, bank)) return hipErrorInvalidValue;   // (the workspace route: stft_route)
+    if (cross && (channels < 2 || !wg4096_can_fuse_fbank_cross(c, bank))) return hipErrorInvalidValue;   // (likewise)
     const size_t peak_group = call.kind == Out::kPeak ? call.peak_group : 0;
     if (call.kind == Out::kPeak && peak_group == 0) return hipErrorInvalidValue;
     // the partial columns of every persistent workgroup
@@ -826,7 +853,7 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
         // the pixel code of the instantiation: the interpolator and the seed-only LUT search are compile-time (kPixCubic / kPixCosine);
         // SGX_FLAG_LUT_WALK and palettes whose seed proof fails run kPixGeneric
         const bool cosine = p.interp == SGX_INTERP_COSINE;
-        const int pix = bank ? kPixFbank : call.kind == Out::kComplex ? kPixRowsC64 : call.kind == Out::kMagsF16 ? kPixRowsF16 : call.kind == Out::kMags ? kPixNone
+        const int pix = cross ? kPixFbankCross : bank ? kPixFbank : call.kind == Out::kComplex ? kPixRowsC64 : call.kind == Out::kMagsF16 ? kPixRowsF16 : call.kind == Out::kMags ? kPixNone
                       : peak_group ? (cosine ? kPixPeakCosine : kPixPeakCubic) : band_means ? (cosine ? kPixBandsCosine : kPixBandsCubic)
                       : (!p.seed_pm1 ? kPixGeneric : (cosine ? kPixCosine : kPixCubic));
         auto launch = [&](auto mono_c, auto pairing_c, auto c2_c) {
@@ -841,6 +868,9 @@ hipError_t launch_wg4096(const sgx_ctx *c, const StftCall &call)
                 break;
             case kPixFbank:   // ((l, r) streams and pair planes only: can_fuse_fbank)
                 if constexpr (!M_ && C2_) go(std::integral_constant<int, kPixFbank>{});
+                break;
+            case kPixFbankCross:   // (the same streams: can_fuse_fbank_cross)
+                if constexpr (!M_ && C2_) go(std::integral_constant<int, kPixFbankCross>{});
                 break;
 #undef PIX
             }
@@ -873,6 +903,14 @@ bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb)
     if (fb->n_filters > fbank::kFusedMaxFilters || fb->n_weights > fbank::kFusedMaxWeights) return false;
     if (c->C == 1) return !(c->cfg.flags & (SGX_FLAG_PAIRED_FRAMES | SGX_FLAG_COMPLEX_MONO)) && real4096_serves(c, nullptr, 1);
     return true;
+}
+
+// sgx_fbank_cross_batch in one kernel: a bank within the same size on a stream of (l, r) pairs -- a mono context has no pair (the call
+// answers SGX_ERR_UNSUPPORTED there)
+bool wg4096_can_fuse_fbank_cross(const sgx_ctx *c, const sgx_fbank *fb)
+{
+    if (!fb || !c->wg || c->stft_kernel != kKernelWg4096 || c->C < 2) return false;
+    return fb->n_filters <= fbank::kFusedMaxFilters && fb->n_weights <= fbank::kFusedMaxWeights;
 }
 
 // sgx_bands_peak_batch in one kernel: every stream the bands column serves but paired mono frames (two frames of one transform may

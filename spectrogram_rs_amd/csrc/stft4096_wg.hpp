@@ -203,6 +203,12 @@ constexpr bool pix_cosine(int pix) { return pix == kPixCosine || pix == kPixBand
 // a filterbank over the column (sgx_fbank_batch): the magnitudes go to LDS as for the bands, then one filter pass (sgx_fbank.hpp) -- no sample
 // stage, no row pass; the bank's tables ride in the words of the row and sample tables (Params)
 constexpr int kPixFbank = 10;
+// a filterbank over the four products of the (L, R) pair (sgx_fbank_cross_batch): the split's L and R never become magnitudes -- every
+// thread forms |L|^2, |R|^2, Re and Im of L conj R of its eight bins (fbank::cross_terms) into two float2 columns of kColSlots slots in
+// the transform's buffer (2 x 2050 x 8 B of its 34 816), then one cross pass (sgx_fbank.hpp).  The bank rides as for kPixFbank; `rgba`
+// is the output, float4 [F][pairs][n_filters].  (l, r) streams and pair planes only.
+constexpr int kPixFbankCross = 11;
+static_assert(2 * kColSlots <= kBufComplex, "the two product columns lie in the transform's buffer");
 // no pixels: the complex rows of sgx_stft_batch_complex, (L, R) as 16 bytes per bin, stored inside the split (stft4096_wg.hip)
 constexpr int kPixRowsC64 = 7;
 //   // kPixGeneric: interpolator at run time, LUT seed + walk (SGX_FLAG_LUT_WALK / proof failed)

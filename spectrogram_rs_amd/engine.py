@@ -616,6 +616,46 @@ class FilterBank:
             e._check(self._lib.sgx_fbank_mags(self._h, e._dev_f32(mags), n, C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- the cross sums: |L|^2, |R|^2, Re and Im of L conj R per band (include/sgx.h: sgx_fbank_cross_batch) ----
+    @property
+    def cross_fused(self) -> int:
+        """1 when cross_batch() runs one kernel from PCM to sums, 0 on the workspace route (the complex rows into a bounded
+        workspace, then the stage kernel) and on a mono engine"""
+        return self.engine._check(self._lib.sgx_fbank_cross_fused(self._h))
+
+    def cross_batch(self, pcm, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [frames][pairs][n_filters][4] float32: per band the weighted sums of |L|^2, |R|^2, Re L conj R and Im L conj R.
+        The phase is atan2(out3, out2), the correlation out2 / sqrt(out0 out1), the coherence (out2^2 + out3^2) / (out0 out1), the
+        mid and side energies out0 + out1 +- 2 out2: all the caller's.  An engine of at least two channels."""
+        import torch
+
+        e = self.engine
+        n_samples = pcm.numel() // e.channels
+        total = e.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        out = e._out(out, (n, e.pairs, self.n_filters, 4), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            e._check(self._lib.sgx_fbank_cross_batch(self._h, e._dev_f32(pcm), n_samples, first_frame, n, C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return out
+
+    def cross_apply(self, spec, out=None):
+        """[columns][M][2][2] float32 complex rows (stft_batch_complex's, flattened over pairs; or its complex64 [columns][M][2]) ->
+        [columns][n_filters][4] float32"""
+        import torch
+
+        e = self.engine
+        if spec.dtype == torch.complex64:
+            spec = torch.view_as_real(spec)
+        n = spec.numel() // (e.M * 4)
+        out = e._out(out, (n, self.n_filters, 4), torch.float32)
+        if n:
+            e._check(self._lib.sgx_fbank_cross_spec(self._h, e._dev_f32(spec), n, C.c_void_p(out.data_ptr())))
+        return out
+
 
 class ImageRing:
     """sgx_image: the width x rows RGBA Pixbuf of simple_spectrogram.rs:89-94 on the device, written one pixel column per frame at
