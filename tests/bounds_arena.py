@@ -96,7 +96,31 @@ def bands_chunk(W: int, pairs: int) -> int:
     return render_chunk(W, pairs)
 
 
-PEAK_SUB_NUM, PEAK_SUB_DEN = 9, 64   # sgx_bands_peak_batch: kSubNum / kSubDen of a column per frame for the two-level reduction
+def fbank_chunk(W: int, pairs: int) -> int:
+    """frames per chunk of sgx_fbank_batch on the workspace route: the same workspace, the same magnitudes"""
+    return render_chunk(W, pairs)
+
+
+def fbank_cross_chunk(W: int, pairs: int) -> int:
+    """frames per chunk of sgx_fbank_cross_batch on the workspace route: a frame's complex rows are two magnitude rows' bytes
+    (in_workspace_chunks with rows_per_frame = 2), at least 1"""
+    return max(WORKSPACE_BYTES // (2 * mags_bytes_per_frame(W, pairs)), 1)
+
+
+N_BANK_FILTERS = 263            # fbank_reference.edge_bank: the bank of the bounds sweep
+FUSED_BANK_KERNEL = 2           # info.stft_kernel of the 4096-point kernels, the only ones with a fused bank mode
+
+
+def fbank_fused(route, cross: bool = False) -> int:
+    """what sgx_fbank_fused / sgx_fbank_cross_fused must answer on a row of edge_signals.ROUTES for a bank within the fused size
+    (include/sgx.h): the 4096-point kernels, not on frame pairs, not on the complex mono transform; the cross sums need an (l, r) pair"""
+    fused = route.kernel == FUSED_BANK_KERNEL and not route.paired and "complex_mono" not in route.flags
+    if cross:
+        fused = fused and route.channels >= 2
+    return 1 if fused else 0
+
+
+PEAK_SUB_NUM, PEAK_SUB_DEN = 9, 64  # sgx_bands_peak_batch: kSubNum / kSubDen of a column per frame for the two-level reduction
 
 
 def peak_per_frame(W: int, pairs: int, R: int, two_kernel: bool) -> int:

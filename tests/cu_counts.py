@@ -413,6 +413,26 @@ def branches(case: Case, limit: int, device_cu: int) -> set:
     return out
 
 
+def bank_kinds(r: es.Route) -> tuple:
+    """the filterbank calls a forward case runs besides its other entry points: on the 4096-point kernels sgx_fbank_batch and, with an
+    (l, r) pair, sgx_fbank_cross_batch.  Their fused modes (bounds_arena.fbank_fused) are instantiations of the same persistent kernels
+    behind the same launcher: forward_split is their split as well, and on the workspace route (frame pairs, the complex mono transform)
+    it is the split of the rows they read."""
+    if r.kernel != 2:
+        return ()
+    return ("fbank", "fbank_cross") if r.channels >= 2 else ("fbank",)
+
+
+LAST_JOB_ONE_FRAME = "run_split: a last job without its second frame"
+
+
+def bank_cases_with_a_last_job_of_one_frame(device_cu: int) -> list:
+    """[(case name, limit)] at which a FUSED bank call meets a run whose last job lacks its second frame: the real-input kernel holds two
+    frames' magnitudes in one column there, and its filter pass must write one frame's sums only"""
+    return [(c.name, limit) for c in TABLE if c.kind == "forward" and bank_kinds(route_of(c)) and ba.fbank_fused(route_of(c))
+            for limit in LIMITS if LAST_JOB_ONE_FRAME in branches(c, limit, device_cu)]
+
+
 def more_than_one_job(case: Case, limit: int, device_cu: int, family: str) -> bool:
     """does a workgroup of the `family` ("run_split" / "k16") launch of (case, limit) run more than one job, in either of its calls --
     the cases an omit-only variant library of that family must fail"""

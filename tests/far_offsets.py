@@ -228,12 +228,30 @@ def hop_cases():
 
 
 # ---- part 4: outputs past 2^31 and 2^32 bytes --------------------------------------------------------------------------------------------
-OUTPUT_KINDS = ["stft", "f16", "complex", "render", "bands", "peak_2"]
+OUTPUT_KINDS = ["stft", "f16", "complex", "render", "bands", "peak_2", "fbank", "fbank_cross"]
 OUTPUT_FAMILIES = [f for f in FAMILIES if f != "mixed_runtime_real"]   # (its run-time geometry and real-input mode: mixed_runtime, mixed_real)
 ROWS_DEFAULT, ROWS_MAX = 1024, 65536
+# the filterbank calls: the fused route (the 4096-point kernel on (l, r)) and one workspace family with a short hop.  The bank is the
+# largest the fused route takes, 1024 filters (include/sgx.h: sgx_fbank_fused), of one bin each: 8 KiB and 16 KiB of sums per frame, the
+# most a frame of input can be made to write -- nothing smaller crosses the marks.
+BANK_KINDS = ("fbank", "fbank_cross")
+BANK_OUTPUT_FAMILIES = ("k1_lr", "k48_lr")
+BANK_FILTERS = 1024
+
+
+def far_bank(M: int):
+    """(first, count, weights): 1024 filters of one bin each, scattered over the M bins (bin 0 and bin M - 1 among them), weights of both
+    signs with magnitudes in [2^-6, 1]"""
+    rng = np.random.default_rng([0xFA2, M])
+    first = (np.arange(BANK_FILTERS, dtype=np.int64) * 2039 % M).astype(np.uint32)
+    first[1] = M - 1
+    weights = (np.exp2(rng.uniform(-6.0, 0.0, BANK_FILTERS)) * rng.choice([-1.0, 1.0], BANK_FILTERS)).astype(np.float32)
+    return first, np.ones(BANK_FILTERS, np.uint32), weights
 
 
 def out_row_bytes(r: es.Route, kind: str, R: int) -> int:
+    if kind in BANK_KINDS:
+        return r.pairs * BANK_FILTERS * (8 if kind == "fbank" else 16)
     if kind in ("stft", "f16", "complex"):
         return r.pairs * (r.W - 1) * {"stft": 8, "f16": 4, "complex": 16}[kind]
     return r.pairs * R * (4 if kind == "render" else 8)
@@ -304,7 +322,7 @@ def output_case(family: str, kind: str) -> OutputCase:
 
 
 def output_cases():
-    return [output_case(f, k) for f in OUTPUT_FAMILIES for k in OUTPUT_KINDS]
+    return [output_case(f, k) for f in OUTPUT_FAMILIES for k in OUTPUT_KINDS if k not in BANK_KINDS or f in BANK_OUTPUT_FAMILIES]
 
 
 # ---- what the method is for: one address computation, truncated --------------------------------------------------------------------------
@@ -437,3 +455,48 @@ PIXEL_CASES = [
     # together are 3 (2^32 bytes + 2 columns) -- the least such a call can be, a few KiB above the 12 GiB of the batch cases)
     PixelCase("render_bands_r128", "render_bands_kernel", "render_bands", 64, 128),
 ]
+
+
+# ---- part 4, the filterbank stages alone: sgx_fbank_mags and sgx_fbank_cross_spec with an output past 2^32 bytes ------------------------
+@dataclass(frozen=True)
+class BankStageCase:
+    name: str
+    entry: str           # fbank_mags, fbank_cross_spec
+    W: int               # the shortest columns a context of the generic kernel takes: the case is its output
+    n_filters: int = BANK_FILTERS
+
+    @property
+    def id(self):
+        return self.name
+
+    @property
+    def M(self):
+        return self.W - 1
+
+    @property
+    def in_col_bytes(self):
+        return self.M * (8 if self.entry == "fbank_mags" else 16)
+
+    @property
+    def out_col_bytes(self):
+        return self.n_filters * (8 if self.entry == "fbank_mags" else 16)
+
+    @property
+    def cols(self):
+        return rows_for(self.out_col_bytes)
+
+    def probes(self):
+        """the columns whose sums hold a mark of the output, their neighbours, the first and the last"""
+        out = {0, self.cols - 1}
+        for m in OUTPUT_MARKS:
+            k = m // self.out_col_bytes
+            out.update((k - 1, k, k + 1))
+        return sorted(out)
+
+    def pieces(self):
+        """[(first column, columns)]: the output of every piece below PIECE_LIMIT bytes"""
+        per = (PIECE_LIMIT - 1) // self.out_col_bytes
+        return [(a, min(per, self.cols - a)) for a in range(0, self.cols, per)]
+
+
+BANK_STAGE_CASES = [BankStageCase("fbank_mags_w64", "fbank_mags", 64), BankStageCase("fbank_cross_spec_w64", "fbank_cross_spec", 64)]

@@ -10,18 +10,21 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import bounds_arena as ba
 import edge_signals as es
 
 PEAK_GROUP = 3
 # the order of the calls: the batch entry points, then the calls that consume what those just made
-BATCH = ("stft", "f16", "complex", "render", "bands", "peak_3")
-STAGE = ("render_mags", "magnitude_in", "render_bands", "checksum_add")
+BATCH = ("stft", "f16", "complex", "render", "bands", "peak_3", "fbank", "fbank_cross")
+STAGE = ("render_mags", "magnitude_in", "render_bands", "checksum_add", "fbank_mags", "fbank_cross_spec")
 ENTRIES = BATCH + ("istft",) + STAGE
 SYMBOL = {"stft": "sgx_stft_batch", "f16": "sgx_stft_batch_f16", "complex": "sgx_stft_batch_complex", "render": "sgx_render_batch",
           "bands": "sgx_bands_batch", "peak_3": "sgx_bands_peak_batch", "istft": "sgx_istft_batch", "render_mags": "sgx_render_mags",
-          "magnitude_in": "sgx_magnitude_in", "render_bands": "sgx_render_bands", "checksum_add": "sgx_checksum_add"}
+          "magnitude_in": "sgx_magnitude_in", "render_bands": "sgx_render_bands", "checksum_add": "sgx_checksum_add",
+          "fbank": "sgx_fbank_batch", "fbank_cross": "sgx_fbank_cross_batch", "fbank_mags": "sgx_fbank_mags", "fbank_cross_spec": "sgx_fbank_cross_spec"}
 # what a call reads that another call of the same run wrote: a wrong input makes a wrong output whatever the call itself does
-READS = {"istft": "complex", "render_mags": "stft", "magnitude_in": "stft", "render_bands": "bands", "checksum_add": "stft"}
+READS = {"istft": "complex", "render_mags": "stft", "magnitude_in": "stft", "render_bands": "bands", "checksum_add": "stft",
+         "fbank_mags": "stft", "fbank_cross_spec": "complex"}
 # entry points that wait on the host in their steady state, with the reason (include/sgx.h's conventions name them): none
 HOST_WAITS: dict = {}
 
@@ -45,8 +48,13 @@ def peak_fused(r: es.Route) -> int:
     return int(r.kernel == 2 and not r.paired)
 
 
+def fbank_cross_served(r: es.Route) -> bool:
+    """sgx_fbank_cross_batch: a context with an (l, r) pair (a mono context answers SGX_ERR_UNSUPPORTED); the stage serves every context"""
+    return r.channels >= 2
+
+
 def entries_served(r: es.Route) -> tuple:
-    return tuple(e for e in ENTRIES if e != "istft" or istft_served(r))
+    return tuple(e for e in ENTRIES if (e != "istft" or istft_served(r)) and (e != "fbank_cross" or fbank_cross_served(r)))
 
 
 @dataclass(frozen=True)
@@ -71,7 +79,7 @@ def by_row() -> dict:
 
 # ---- the helper passes -------------------------------------------------------------------------------------------------------------------
 HELPERS = ("deinterleave", "k16_plane", "to_half", "workspace", "workspace_render", "workspace_magnitude_in", "workspace_peak",
-           "peak_combine", "ladder", "large_passes", "inverse")
+           "peak_combine", "ladder", "large_passes", "inverse", "workspace_fbank", "workspace_fbank_cross")
 
 
 def family(r: es.Route) -> str:
@@ -117,6 +125,12 @@ def helpers(r: es.Route, entry: str, render_fused: bool, bands_fused: bool) -> s
         return helpers(r, "bands", render_fused, bands_fused) | {"workspace", "workspace_peak"}
     if entry == "istft":
         return {"inverse"}
+    if entry in ("fbank", "fbank_cross"):
+        # the bank of the sweep lies within the fused size (bounds_arena.fbank_fused): one kernel behind the rows' own helpers -- the
+        # de-interleave pass of 4 and 8 channels -- or the rows (magnitudes, complex) into the workspace and the stage kernel over them
+        if ba.fbank_fused(r, cross=entry == "fbank_cross"):
+            return rows
+        return rows | {"workspace", "workspace_" + entry}
     return set()
 
 
@@ -176,4 +190,7 @@ REBIND_CASES = [
     ("seam_bands", dict(window_samples=8192, hop_samples=16, channels=2), "bands_batch"),
     ("seam_render", dict(window_samples=8192, hop_samples=16, channels=2), "render_batch"),
     ("k16_mono_bands", dict(window_samples=8192, hop_samples=512, channels=1), "bands_batch"),
+    # a bank created while the context is bound to the first stream (sgx_fbank_create's uploads go there), used from the second: the method
+    # is the FilterBank's
+    ("seam_fbank", dict(window_samples=8192, hop_samples=16, channels=2), "fbank_batch"),
 ]

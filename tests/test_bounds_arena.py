@@ -82,6 +82,27 @@ def test_chunk_sizes_w8192_r1024():
     assert ba.peak_chunk(2048, 1, 1024, 10 ** 6, 10 ** 6, two_kernel=False) == 21544
 
 
+def test_fbank_chunk_sizes():
+    # W 8192, (l, r): the magnitude rows of 3072 frames fill the workspace (above); a frame's complex rows are 2 * 65528 = 131056 bytes,
+    # 1536 of them are 201 302 016 <= 201 326 592 and 1537 are not
+    assert ba.fbank_chunk(8192, 1) == 3072 and ba.fbank_cross_chunk(8192, 1) == 1536
+    # W 2400, (l, r): 2399 * 8 = 19192 bytes; 201326592 / 19192 = 10490.1, / 38384 = 5245.06
+    assert ba.fbank_chunk(2400, 1) == 10490 and ba.fbank_cross_chunk(2400, 1) == 5245
+    # W 2^20, (l, r): 8388600 bytes a frame: 24 frames of magnitudes (201326400), 12 of complex rows, one bin short of 25 and of 13
+    assert ba.fbank_chunk(1 << 20, 1) == 24 and ba.fbank_cross_chunk(1 << 20, 1) == 12
+    # four pairs at W 8192: 262112 bytes; 768.09 -> 768, 384.04 -> 384
+    assert ba.fbank_chunk(8192, 4) == 768 and ba.fbank_cross_chunk(8192, 4) == 384
+    # a frame larger than the workspace: one frame per chunk
+    assert ba.fbank_cross_chunk(1 << 20, 16) == 1 and 2 * ba.mags_bytes_per_frame(1 << 20, 16) > ba.WORKSPACE_BYTES
+
+
+def test_fbank_fused_rule():
+    fused = {r.name: (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)) for r in es.ROUTES}
+    assert {n for n, v in fused.items() if v[0]} == {"k1r_h256", "k1r_h100", "k1r_h256_align4", "k1_lr_h256", "k1_lr_h58", "k1_ch4", "k1_ch8"}
+    assert {n for n, v in fused.items() if v[1]} == {"k1_lr_h256", "k1_lr_h58", "k1_ch4", "k1_ch8"}
+    assert fused["k1_complex_mono"] == (0, 0) and fused["k1_paired_mono"] == (0, 0) and fused["generic_w2048_lr"] == (0, 0)
+
+
 def test_peak_chunk_loop():
     # one column over three chunks
     assert ba.peak_chunks(8192, 1, 1024, 6000, 6000) == [(0, 2688, 0, False), (2688, 2688, 0, True), (5376, 624, 0, True)]

@@ -119,6 +119,20 @@ def test_gpu_table_reaches_every_branch():
     assert not set(cc.REQUIRED_BRANCHES) - reached, sorted(set(cc.REQUIRED_BRANCHES) - reached)
 
 
+def test_the_bank_kinds_reach_a_last_job_without_its_second_frame():
+    """the filterbank calls ride the forward cases of the 4096-point kernels; the fused ones on the real-input rows meet, at low limits, a run
+    of several jobs whose last job holds one frame (the split is the rows' own launcher's: proved above for every case and limit)"""
+    assert {c.name: cc.bank_kinds(cc.route_of(c)) for c in cc.TABLE if c.kind == "forward" and cc.bank_kinds(cc.route_of(c))} == {
+        "k1r_h256": ("fbank",), "k1r_h100": ("fbank",), "k1r_h256_align4": ("fbank",), "k1_complex_mono": ("fbank",), "k1_paired_mono": ("fbank",),
+        "k1_lr_h256": ("fbank", "fbank_cross"), "k1_lr_h58": ("fbank", "fbank_cross"), "k1_ch4": ("fbank", "fbank_cross"),
+        "k1_ch8": ("fbank", "fbank_cross")}
+    reached = cc.bank_cases_with_a_last_job_of_one_frame(cc.CPU_DEVICE_CU)
+    assert {name for name, _ in reached} == {"k1r_h256", "k1r_h100", "k1r_h256_align4"}
+    # 75 frames are 38 jobs, the last of one frame; the sub-range from frame 3 is 72 frames: no such job.  At limits 1 .. 8 the last workgroup
+    # runs that job behind others
+    assert {limit for name, limit in reached if name == "k1r_h256"} >= {1, 2, 3, 5, 8}
+
+
 @pytest.mark.parametrize("n_cu", N_CU)
 def test_sweep_16384_point_walk(n_cu):
     big = n_cu > 40

@@ -117,7 +117,16 @@ def test_tables_reach_every_row_and_family():
     assert list(fo.FAMILIES) == named
     assert {c.family for c in HOPS} == set(named) and len(HOPS) == len(named) * 4 * 2
     assert {c.family for c in OUTPUTS} == set(named) - {"mixed_runtime_real"}
-    assert {(c.family, c.kind) for c in OUTPUTS} == {(f, k) for f in fo.OUTPUT_FAMILIES for k in fo.OUTPUT_KINDS}
+    # every family through every kind but the filterbank calls; those on the fused family and on one workspace family with a short hop
+    assert fo.OUTPUT_KINDS[-2:] == list(fo.BANK_KINDS) == ["fbank", "fbank_cross"]
+    assert {(c.family, c.kind) for c in OUTPUTS} == ({(f, k) for f in fo.OUTPUT_FAMILIES for k in fo.OUTPUT_KINDS[:-2]}
+                                                     | {(f, k) for f in ("k1_lr", "k48_lr") for k in fo.BANK_KINDS})
+    banks = {(c.family, c.kind): c for c in OUTPUTS if c.kind in fo.BANK_KINDS}
+    assert {k: (c.row_bytes, c.rows) for k, c in banks.items()} == {
+        ("k1_lr", "fbank"): (8192, 524290), ("k48_lr", "fbank"): (8192, 524290),                   # 2^32 / 8 KiB = 524288 rows, and two
+        ("k1_lr", "fbank_cross"): (16384, 262146), ("k48_lr", "fbank_cross"): (16384, 262146)}     # 2^32 / 16 KiB = 262144 rows, and two
+    assert all(c.input_bytes + c.output_bytes <= fo.CASE_CAP_BYTES and c.R == fo.ROWS_DEFAULT for c in banks.values())
+    assert fo.family_route("k1_lr").kernel == 2 and fo.family_route("k48_lr").kernel == 9 and fo.family_route("k48_lr").H == 93
     # the family rows are what their names say (edge_signals' route bits)
     R4, R8 = es.R4, es.R8
     fam = fo.family_route
@@ -243,6 +252,35 @@ def test_pixel_case(case):
     assert case.large == pp.needs_large(case.W) and case.R <= fo.ROWS_MAX and 2 <= case.n_lut <= 65536
     assert fo.pixel_body(case.entry, case.M, pp.row_table(cfg).n_samples, case.n_lut, fo.LDS_CAP) == case.body
     assert fo.LDS_CAP == pp.LDS_CAP
+
+
+@pytest.mark.parametrize("case", fo.BANK_STAGE_CASES, ids=lambda c: c.id)
+def test_bank_stage_case(case):
+    """sgx_fbank_mags / sgx_fbank_cross_spec: the column index times n_filters (the stage kernels' `col * p.n_filters`) passes 2^31 and 2^32
+    bytes of output; the columns are as short as a context takes, so the case is its output and a sixteenth of it"""
+    assert case.n_filters == fo.BANK_FILTERS == 1024 and case.W == 64
+    assert (case.in_col_bytes, case.out_col_bytes) == {"fbank_mags": (63 * 8, 8192), "fbank_cross_spec": (63 * 16, 16384)}[case.entry]
+    n_in, n_out = case.cols * case.in_col_bytes, case.cols * case.out_col_bytes
+    assert (1 << 32) + 2 * case.out_col_bytes <= n_out < (1 << 32) + 3 * case.out_col_bytes
+    assert n_in + n_out <= fo.CASE_CAP_BYTES and n_in < fo.PIECE_LIMIT
+    probes = set(case.probes())
+    for m in fo.OUTPUT_MARKS:
+        k = m // case.out_col_bytes
+        assert k * case.out_col_bytes <= m < (k + 1) * case.out_col_bytes and {k - 1, k, k + 1} <= probes and k + 1 <= case.cols - 1
+        # the element index the kernel forms, col * n_filters float2s (float4s), passes 2^28 and 2^29 there: bytes 2^31 and 2^32
+        assert k * case.n_filters * (case.out_col_bytes // case.n_filters) == m
+    assert {0, case.cols - 1} <= probes
+    at = 0
+    for a, n in case.pieces():
+        assert a == at and n >= 1 and n * case.out_col_bytes < fo.PIECE_LIMIT
+        at += n
+    assert at == case.cols and len(case.pieces()) >= 3
+    first, count, weights = fo.far_bank(case.W - 1)
+    assert len(first) == 1024 and (count == 1).all() and first[0] == 0 and first[1] == case.W - 2 and int(first.max()) < case.W - 1
+    assert weights.dtype == np.float32 and (np.abs(weights) >= 2.0 ** -6).all() and (np.abs(weights) <= 1.0).all() and (weights < 0).any()
+    for M in (2047, 2399):                                   # the banks of the batch cases: within the fused size, bins all over the column
+        f, c, w = fo.far_bank(M)                             # (bin M - 1, put in by hand, may repeat one of the scattered ones)
+        assert len(set(f.tolist())) >= 1023 and int(f.max()) == M - 1 and int(c.sum()) == 1024 <= 16384
 
 
 def test_pixel_cases_reach_every_body():

@@ -10,6 +10,10 @@ frame, one channel or one row too generous gives correct results wherever the ca
      columns, kernel 11's scratch, the inverse's tables);
   D  the pixel-stage entry points (render_mags, render_bands, magnitude_in) get the same arenas;
   E  the chunk loops over the 192 MiB workspace are crossed, a peak column accumulating over several chunks included.
+The filterbank calls (sgx_fbank_batch, sgx_fbank_cross_batch; the stages sgx_fbank_mags, sgx_fbank_cross_spec under D) run through all of
+it with one bank per context, fbank_reference.edge_bank at power 2: their baselines equal the stage over the baseline's own rows and, on
+three frames, the header's definition as tests/fbank_reference.py computes it, bit for bit.  sgx_fbank_cross_batch asks for 16 bytes: its
+8-modulo-16 variant asserts the refusal and an untouched arena.
 All of it is bit for bit against a clean baseline (the whole stream through a fresh engine on fresh, exact-size tensors), and the
 baseline's rows are held to the float64 truth on three frames at the bound the project holds white noise to.  No skips: a (row, entry
 point) pair is left out only through EXPECTED_UNSUPPORTED, and the library must refuse exactly those.  Run with -m gpu on an MI355X."""
@@ -21,6 +25,7 @@ import pytest
 
 import bounds_arena as ba
 import edge_signals as es
+import fbank_reference as fr
 import oracle
 from conftest import chirpz_bound, mags_error
 from spectrogram_rs_amd import SpectrogramEngine, _lib
@@ -30,13 +35,20 @@ pytestmark = pytest.mark.gpu
 
 ROWS = [r.name for r in es.ROUTES]
 VARIANTS = ["aligned", "odd"]
-KINDS = ["stft", "f16", "complex", "render", "bands", "peak_1", "peak_3", "peak_n", "peak_n5"]
+KINDS = ["stft", "f16", "complex", "render", "bands", "peak_1", "peak_3", "peak_n", "peak_n5", "fbank", "fbank_cross"]
 ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "istft": "f32", "magnitude_in": "f32",
-        "render_mags": "u8", "render_bands": "u8"}
+        "render_mags": "u8", "render_bands": "u8", "fbank": "f32", "fbank_cross": "f32", "fbank_mags": "f32", "fbank_cross_spec": "f32"}
 # the only (row, entry point) pairs this file leaves out: the library must answer SGX_ERR_UNSUPPORTED / istft_supported() == 0 for
 # exactly these (test_expected_unsupported), any other refusal fails the test that meets it
-EXPECTED_UNSUPPORTED = {(r.name, "istft") for r in es.ROUTES if r.kernel == 11}
+EXPECTED_UNSUPPORTED = {(r.name, "istft") for r in es.ROUTES if r.kernel == 11} | {(r.name, "fbank_cross") for r in es.ROUTES if r.channels == 1}
 INVERSE_ROWS = [n for n in ROWS if (n, "istft") not in EXPECTED_UNSUPPORTED]
+SERVED = [(n, k) for k in KINDS for n in ROWS if (n, k) not in EXPECTED_UNSUPPORTED]      # (row, kind) of the sweeps over KINDS
+
+
+def kinds_of(name):
+    return [k for k in KINDS if (name, k) not in EXPECTED_UNSUPPORTED]
+
+
 # the rows whose column of magnitudes no LDS holds ((M + 1) * 8 bytes against the 160 KB of a workgroup): the pixel and bands stages read
 # them from global memory, in instantiations of their own (render_kernel<false>, magnitude_in_kernel<false>)
 # (the launchers compare with min(the device's opt-in LDS, 160 KB), and launch_render adds its threshold tables, (n_lut + 255) * 4
@@ -82,7 +94,17 @@ def rows_of(kind, n):
     return -(-n // group_of(kind, n)) if kind.startswith("peak") else n
 
 
+def bank_of(eng):
+    """the engine's bank of the sweep, made once per context: fbank_reference.edge_bank over its bins, power 2"""
+    if getattr(eng, "_bounds_bank", None) is None:
+        eng._bounds_bank = eng.filterbank(*fr.edge_bank(eng.M), power=2)
+        assert eng._bounds_bank.n_filters == ba.N_BANK_FILTERS
+    return eng._bounds_bank
+
+
 def row_bytes(eng, kind):
+    if kind in ("fbank", "fbank_cross"):
+        return eng.pairs * ba.N_BANK_FILTERS * (8 if kind == "fbank" else 16)
     if kind in ("stft", "f16", "complex"):
         return eng.pairs * eng.M * {"stft": 8, "f16": 4, "complex": 16}[kind]
     return eng.pairs * eng.R * (4 if kind == "render" else 8)
@@ -99,6 +121,10 @@ def run(eng, kind, dev, first, n, out=None):
         return eng.render_batch(dev, first, n, out=out)
     if kind == "bands":
         return eng.bands_batch(dev, first, n, out=out)
+    if kind == "fbank":
+        return bank_of(eng).batch(dev, first, n, out=out)
+    if kind == "fbank_cross":
+        return bank_of(eng).cross_batch(dev, first, n, out=out)
     return eng.bands_peak_batch(dev, group_of(kind, n), first, n, out=out)
 
 
@@ -166,10 +192,15 @@ def case(torch, name):
     pcm = (oracle.white_noise(N * Cn, seed=0x5EED0900 + ROWS.index(name)) * np.float32(0.25)).reshape(N, Cn)
     dev = to_dev(torch, r, pcm)
     cs = SimpleNamespace(r=r, eng=eng, F=F, N=N, pcm=pcm, dev=dev, base={}, flat={})
-    for kind in ("stft", "f16", "complex", "render", "bands"):
+    fb = bank_of(eng)
+    assert (fb.fused, fb.cross_fused) == (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)), (name, fb.fused, fb.cross_fused)
+    for kind in ("stft", "f16", "complex", "render", "bands", "fbank", "fbank_cross"):
+        if (name, kind) in EXPECTED_UNSUPPORTED:
+            continue
         cs.base[kind] = run(eng, kind, dev, 0, F)
         cs.flat[kind] = words(torch, cs.base[kind])
         assert cs.base[kind].shape[0] == F
+    anchor_banks(torch, cs, fb)
     # the anchor of every bit-identity below: the baseline's rows against the float64 truth on the first, the middle and the last frame
     got = cs.base["stft"].cpu().numpy()
     bound = chirpz_bound(W) if r.kernel == 4 else 1.0
@@ -197,6 +228,29 @@ def case(torch, name):
     torch.cuda.synchronize()
     _cache[name] = cs
     return cs
+
+
+def anchor_banks(torch, cs, fb):
+    """The anchor of the bank kinds: the baseline equals the stage over the baseline's own rows bit for bit, and on the first, the middle
+    and the last frame (all three on every row: the W 2^20 row's take about two seconds of CPU per kind) the header's definition as
+    tests/fbank_reference.py computes it, bit for bit."""
+    eng, F, name = cs.eng, cs.F, cs.r.name
+    bank = fr.edge_bank(eng.M)
+    probe = [0, F // 2, F - 1]
+    rows = cs.base["stft"]
+    assert torch.equal(words(torch, fb.apply(rows.reshape(-1, eng.M, 2))), cs.flat["fbank"]), (name, "sgx_fbank_batch differs from sgx_fbank_mags of the rows")
+    want = fr.bank_sums(rows[probe].cpu().numpy(), bank, 2)
+    got = cs.base["fbank"][probe].cpu().numpy()
+    assert got.shape == want.shape == (3, eng.pairs, ba.N_BANK_FILTERS, 2)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, "sgx_fbank_batch differs from the definition")
+    if "fbank_cross" not in cs.base:
+        return
+    spec = torch.view_as_real(cs.base["complex"]).contiguous()
+    assert torch.equal(words(torch, fb.cross_apply(spec.reshape(-1, eng.M, 2, 2))), cs.flat["fbank_cross"]), (name, "sgx_fbank_cross_batch differs from sgx_fbank_cross_spec of the rows")
+    want = fr.cross_sums(spec[probe].cpu().numpy(), bank)
+    got = cs.base["fbank_cross"][probe].cpu().numpy()
+    assert got.shape == want.shape == (3, eng.pairs, ba.N_BANK_FILTERS, 4)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, "sgx_fbank_cross_batch differs from the definition")
 
 
 def calls_of(cs):
@@ -234,8 +288,21 @@ def check_arena(arena, prefill, what):
 
 def test_expected_unsupported(torch_cuda):
     torch = torch_cuda
-    assert {k for _, k in EXPECTED_UNSUPPORTED} == {"istft"}
+    assert {k for _, k in EXPECTED_UNSUPPORTED} == {"istft", "fbank_cross"}
+    assert {n for n, k in EXPECTED_UNSUPPORTED if k == "fbank_cross"} == {r.name for r in es.ROUTES if r.channels == 1}
     for name in ROWS:
+        cs = case(torch, name)
+        if (name, "fbank_cross") in EXPECTED_UNSUPPORTED:   # a mono context: refused, the count zero, the buffer as it was
+            fb = bank_of(cs.eng)
+            assert fb.cross_fused == 0
+            out = torch.zeros(cs.F * row_bytes(cs.eng, "fbank_cross") // 4, dtype=torch.float32, device="cuda")
+            got = C.c_size_t(99)
+            rc = cs.eng._lib.sgx_fbank_cross_batch(fb._h, C.c_void_p(cs.dev.data_ptr()), cs.N, 0, cs.F, C.c_void_p(out.data_ptr()), C.byref(got))
+            assert rc == _lib.SGX_ERR_UNSUPPORTED and got.value == 0, (name, rc)
+            torch.cuda.synchronize()
+            assert not bool(out.any())
+        else:
+            assert "fbank_cross" in cs.base, name
         if (name, "istft") not in EXPECTED_UNSUPPORTED:
             continue
         cs = case(torch, name)
@@ -283,9 +350,21 @@ def test_unstaged_pixel_stage_against_the_oracle(torch_cuda, name):
 
 
 # ---- A: output guards ---------------------------------------------------------------------------------------------------------------
+def refused_for_alignment(torch, cs, arena, first, n, what):
+    """sgx_fbank_cross_batch wants 16 bytes (include/sgx.h): at 8 modulo 16 it answers SGX_ERR_INVALID_ARG and writes nothing"""
+    before = arena.words.clone()
+    got = C.c_size_t(99)
+    out = arena.payload(torch.float32)
+    assert out.data_ptr() % 16 == 8
+    rc = cs.eng._lib.sgx_fbank_cross_batch(bank_of(cs.eng)._h, C.c_void_p(cs.dev_ragged.data_ptr()), cs.dev_ragged.numel() // cs.r.channels, first, n,
+                                           C.c_void_p(out.data_ptr()), C.byref(got))
+    assert rc == _lib.SGX_ERR_INVALID_ARG and got.value == 0, (what, rc, got.value)
+    torch.cuda.synchronize()
+    assert arena.guards_intact() and torch.equal(arena.words, before), (what, "a refused call wrote")
+
+
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("name", ROWS)
+@pytest.mark.parametrize("name,kind", SERVED)
 def test_output_guards(torch_cuda, name, kind, variant):
     torch = torch_cuda
     cs = case(torch, name)
@@ -294,6 +373,9 @@ def test_output_guards(torch_cuda, name, kind, variant):
         for second in (False, True):
             prefill = ba.prefill_word(elem_of(kind), second)
             arena = Arena(torch, rows_of(kind, n) * rb, rb, variant == "odd", prefill)
+            if kind == "fbank_cross" and variant == "odd":
+                refused_for_alignment(torch, cs, arena, first, n, (name, kind, variant, first, n))
+                continue
             run(cs.eng, kind, cs.dev_ragged, first, n, out=arena.payload(dtype_of(torch, kind)))
             what = (name, kind, variant, first, n, "all ones" if second else "+inf")
             check_result(torch, cs, kind, first, n, arena.payload(), what)
@@ -334,8 +416,7 @@ def poisoned_stream(torch, cs, odd, tail, lo, hi):
     return arena, dev
 
 
-@pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("name", ROWS)
+@pytest.mark.parametrize("name,kind", SERVED)
 def test_input_isolation(torch_cuda, name, kind):
     torch = torch_cuda
     cs = case(torch, name)
@@ -381,13 +462,22 @@ def test_stale_state(torch_cuda, name):
     eng = engine(r, gradient="viridis")   # ONE context for the three runs
     hot = to_dev(torch, r, np.full((cs.N, r.channels), 3e38, np.float32))          # the spectra overflow to inf
     nan = to_dev(torch, r, np.full((cs.N, r.channels), np.nan, np.float32))
+    kinds = kinds_of(name)
     for stream in (hot, nan):
-        for kind in KINDS:
+        for kind in kinds:
             scratch = run(eng, kind, stream, 0, F)
         if cs.istft:
             eng.istft_batch(torch.view_as_real(eng.stft_batch_complex(stream)).contiguous())
     del scratch
-    for kind in KINDS:
+    if "fbank_cross" in kinds:
+        # the workspace between its two row layouts: a cross call (two workspace rows per frame) after a magnitude call of more frames
+        # and before one of fewer, on the overflowing stream and then on the real one
+        a, b, c = F, max(F - 2, 1), max(F - 4, 1)
+        for stream in (hot, cs.dev):
+            got = [run(eng, "fbank", stream, 0, a), run(eng, "fbank_cross", stream, 1, b), run(eng, "fbank", stream, 2, c)]
+        for kind, first, n, t in zip(("fbank", "fbank_cross", "fbank"), (0, 1, 2), (a, min(b, F - 1), min(c, F - 2)), got):
+            check_result(torch, cs, kind, first, n, words(torch, t), (name, kind, first, n, "between the workspace's two row layouts"))
+    for kind in kinds:
         out = None
         if kind.startswith("peak"):   # (a stale +inf would survive a max: what the buffer held before must not matter either)
             out = torch.full((rows_of(kind, F), eng.pairs, eng.R, 2), float("inf"), dtype=torch.float32, device="cuda")
@@ -414,13 +504,19 @@ def pixel_call(eng, entry, src, out=None):
         return eng.render_mags(src, out=out)
     if entry == "render_bands":
         return eng.render_bands(src, out=out)
+    if entry == "fbank_mags":
+        return bank_of(eng).apply(src, out=out)
+    if entry == "fbank_cross_spec":
+        return bank_of(eng).cross_apply(src, out=out)
     return eng.magnitude_in(src, PIXEL_RANGES, out=out)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("entry", ["render_mags", "render_bands", "magnitude_in"])
+@pytest.mark.parametrize("entry", ["render_mags", "render_bands", "magnitude_in", "fbank_mags", "fbank_cross_spec"])
 @pytest.mark.parametrize("ctx", sorted(PIXEL_CONTEXTS))
 def test_pixel_stage(torch_cuda, ctx, entry, variant):
+    """(the bank entries: edge_bank's filters on bin 0 and on bin M - 1 of every column would pull the neighbouring column's word, or the
+    NaN around the arena's payload, into a sum if a read were one bin off)"""
     torch = torch_cuda
     key = ("pixel", ctx)
     if key not in _cache:
@@ -428,19 +524,31 @@ def test_pixel_stage(torch_cuda, ctx, entry, variant):
     eng = _cache[key]
     odd = variant == "odd"
     rng = np.random.default_rng([len(ctx), len(entry)])
-    in_row = (eng.R if entry == "render_bands" else eng.M) * 2          # floats per input column
-    out_row = len(PIXEL_RANGES) * 8 if entry == "magnitude_in" else eng.R * 4   # bytes per output column
+    in_row = {"render_bands": eng.R * 2, "fbank_cross_spec": eng.M * 4}.get(entry, eng.M * 2)   # floats per input column
+    out_row = {"magnitude_in": len(PIXEL_RANGES) * 8, "fbank_mags": ba.N_BANK_FILTERS * 8, "fbank_cross_spec": ba.N_BANK_FILTERS * 16}.get(entry, eng.R * 4)   # bytes per output column
     for cols in (1, 7, 700):   # 700: the persistent workgroups walk several columns each
         # magnitudes from 1e-6 to 1: the whole of the colour ramp
         host = (10.0 ** rng.uniform(-6.0, 0.0, (cols, in_row // 2, 2))).astype(np.float32)
+        if entry == "fbank_cross_spec":
+            host *= rng.choice(np.float32([-1.0, 1.0]), host.shape)
         exact_in = torch.from_numpy(host).cuda()
         want = words(torch, pixel_call(eng, entry, exact_in))
+        if entry.startswith("fbank"):   # the clean run itself against the definition (tests/fbank_reference.py), on the first and the last column
+            bank, ends = fr.edge_bank(eng.M), [0, cols - 1]
+            ref = fr.bank_sums(host[ends], bank, 2) if entry == "fbank_mags" else fr.cross_sums(host[ends].reshape(2, eng.M, 2, 2), bank)
+            assert np.array_equal(want.view(cols, -1)[ends].cpu().numpy().view(np.uint32).reshape(-1), ref.view(np.uint32).reshape(-1)), (ctx, entry, cols)
         src = Arena(torch, cols * in_row * 4, in_row * 4, odd, ba.NAN_WORD, guard=ba.NAN_WORD)
         src.payload(torch.float32)[:] = exact_in.view(-1)
         for second in (False, True):
             prefill = ba.prefill_word(ELEM[entry], second)
             arena = Arena(torch, cols * out_row, out_row, odd, prefill)
             out = arena.payload(torch.uint8 if ELEM[entry] == "u8" else torch.float32)
+            if entry == "fbank_cross_spec" and odd:   # both buffers must be 16-byte aligned (include/sgx.h): refused, nothing written
+                before = arena.words.clone()
+                rc = eng._lib.sgx_fbank_cross_spec(bank_of(eng)._h, C.c_void_p(src.payload().data_ptr()), cols, C.c_void_p(out.data_ptr()))
+                torch.cuda.synchronize()
+                assert rc == _lib.SGX_ERR_INVALID_ARG and torch.equal(arena.words, before), (ctx, entry, variant, cols, rc)
+                continue
             pixel_call(eng, entry, src.payload(torch.float32).view(cols, in_row // 2, 2), out=out)
             what = (ctx, entry, variant, cols, "all ones" if second else "+inf")
             assert torch.equal(arena.payload(), want), what
@@ -485,6 +593,37 @@ def test_seams_render_and_bands(torch_cuda):
         assert torch.equal(px.view(-1), whole["render"][seam - 3:seam + 3].reshape(-1)), ("render_batch", seam)
         bands = eng.magnitude_in(rows, ranges)
         assert torch.equal(words(torch, bands), words(torch, whole["bands"][seam - 3:seam + 3])), ("bands_batch", seam)
+
+
+def test_seams_fbank(torch_cuda):
+    """sgx_fbank_batch and sgx_fbank_cross_batch across the workspace's chunks: the magnitude rows of 3072 frames fill it, the complex rows
+    of 1536 (in_workspace_chunks with two rows per frame), so 2 * 3072 + 37 frames cross two seams of the one loop and four of the other"""
+    torch = torch_cuda
+    eng = seam_engine()
+    chunk, cross_chunk = ba.fbank_chunk(eng.W, eng.pairs), ba.fbank_cross_chunk(eng.W, eng.pairs)
+    assert (chunk, cross_chunk) == (3072, 1536)
+    F = 2 * chunk + 37
+    seams = {"fbank": [s for s in range(chunk, F, chunk)], "fbank_cross": [s for s in range(cross_chunk, F, cross_chunk)]}
+    assert len(seams["fbank"]) == 2 and len(seams["fbank_cross"]) == 4
+    pcm = eng.white_noise(eng.W + (F - 1) * eng.H, seed=0x5EED090C)
+    fb = bank_of(eng)
+    assert fb.fused == 0 and fb.cross_fused == 0
+    rng = np.random.default_rng(910)
+    cuts = sorted(int(c) for c in rng.choice([f for f in range(1, F) if f % cross_chunk], 4, replace=False))   # five pieces
+    edges = [0] + cuts + [F]
+    for kind in ("fbank", "fbank_cross"):
+        whole = run(eng, kind, pcm, 0, F)
+        assert whole.shape[0] == F
+        parts = [run(eng, kind, pcm, a, b - a) for a, b in zip(edges, edges[1:])]
+        assert torch.equal(words(torch, torch.cat(parts, 0)), words(torch, whole)), (kind, cuts, "pieces differ from the whole")
+        del parts
+        for seam in seams[kind]:   # the six frames around each seam from the engine's own rows
+            if kind == "fbank":
+                staged = fb.apply(eng.stft_batch(pcm, seam - 3, 6).reshape(-1, eng.M, 2))
+            else:
+                staged = fb.cross_apply(torch.view_as_real(eng.stft_batch_complex(pcm, seam - 3, 6)).reshape(-1, eng.M, 2, 2))
+            assert torch.equal(words(torch, staged), words(torch, whole[seam - 3:seam + 3])), (kind, seam)
+    eng.close()
 
 
 def peak_against_bands(torch, eng, pcm, bands, first, groups):

@@ -21,7 +21,8 @@ import edge_signals as es
 import oracle
 from conftest import chirpz_bound, mags_error
 from spectrogram_rs_amd import SpectrogramEngine, _lib
-from test_gpu_bounds import Arena, dtype_of, elem_of, row_bytes, to_dev, words
+import fbank_reference as fr
+from test_gpu_bounds import Arena, bank_of, dtype_of, elem_of, row_bytes, to_dev, words
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +91,18 @@ def held_to_the_truth(case, r, pcm, got):
     print(f"CU-TRUTH {case.name} {F} frames worst {worst:.4f} (bound {bound})")
 
 
+def held_to_the_definition(torch, case, eng, kind, dev, F, ref_words):
+    """the limit-0 sums of a bank call on the first, the middle and the last frame against the header's definition over the engine's own
+    rows of those frames (tests/fbank_reference.py), bit for bit: the reference of the sweep is itself right"""
+    bank, probe = fr.edge_bank(eng.M), [0, F // 2, F - 1]
+    if kind == "fbank":
+        want = fr.bank_sums(eng.stft_batch(dev, 0, F)[probe].cpu().numpy(), bank, 2)
+    else:
+        want = fr.cross_sums(torch.view_as_real(eng.stft_batch_complex(dev, 0, F))[probe].cpu().numpy(), bank)
+    got = ref_words.view(torch.float32).view(F, eng.pairs, ba.N_BANK_FILTERS, want.shape[-1])[probe].cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (case.name, kind, "the limit-0 sums differ from the definition")
+
+
 def run_forward(eng, kind, group, dev, first, n, out=None):
     if kind == "stft":
         return eng.stft_batch(dev, first, n, out=out)
@@ -101,6 +114,10 @@ def run_forward(eng, kind, group, dev, first, n, out=None):
         return eng.render_batch(dev, first, n, out=out)
     if kind == "bands":
         return eng.bands_batch(dev, first, n, out=out)
+    if kind == "fbank":
+        return bank_of(eng).batch(dev, first, n, out=out)
+    if kind == "fbank_cross":
+        return bank_of(eng).cross_batch(dev, first, n, out=out)
     return eng.bands_peak_batch(dev, group, first, n, out=out)
 
 
@@ -131,6 +148,11 @@ def forward_case(torch, case, dcu):
         return streams[F]
 
     peak_fused = eng.bands_peak_fused
+    # the filterbank calls of the 4096-point kernels: fbank_reference.edge_bank at power 2, fused wherever bounds_arena.fbank_fused says so
+    bank_kinds = list(cc.bank_kinds(r))
+    if bank_kinds:
+        fb = bank_of(eng)
+        assert (fb.fused, fb.cross_fused) == (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)), (case.name, fb.fused, fb.cross_fused)
     for limit in cc.LIMITS:
         n_cu = cc.limit_value(limit, dcu)
         eng.set_cu_limit(0 if limit == 0 else n_cu)
@@ -142,7 +164,7 @@ def forward_case(torch, case, dcu):
         differs = False
         for first, n in cc.forward_calls(case, limit):
             groups = {"peak_3": 3, "peak_run": cc.peak_run_group(r, n, n_cu)}
-            for kind in FORWARD_KINDS:
+            for kind in FORWARD_KINDS + bank_kinds:
                 group = groups.get(kind, 0)
                 key = (F, kind, group, first)
                 if key not in ref:
@@ -150,6 +172,8 @@ def forward_case(torch, case, dcu):
                     ref[key] = words(torch, run_forward(eng, kind, group, dev, first, n)).clone()
                     if kind == "stft" and first == 0:
                         held_to_the_truth(case, r, pcm, ref[key].view(torch.float32).view(n, r.pairs, r.W - 1, 2).cpu().numpy())
+                    if kind in bank_kinds and first == 0:
+                        held_to_the_definition(torch, case, eng, kind, dev, F, ref[key])
                     eng.set_cu_limit(0 if limit == 0 else n_cu)
                 rb = row_bytes(eng, "bands" if kind.startswith("peak") else kind)
                 rows = -(-n // group) if group else n
@@ -258,6 +282,10 @@ def test_the_table_reaches_every_branch(torch_cuda):
     for b in cc.REQUIRED_BRANCHES:
         print(f"CU-BRANCH {b}: {len(reached.get(b, []))} (case, limit) pairs, e.g. {reached.get(b, [None])[0]}")
     assert not set(cc.REQUIRED_BRANCHES) - set(reached), sorted(set(cc.REQUIRED_BRANCHES) - set(reached))
+    # the fused bank call of the real-input kernel meets a last job of one frame behind other jobs of its run
+    banks = cc.bank_cases_with_a_last_job_of_one_frame(dcu)
+    print(f"CU-BRANCH the fused bank kinds at '{cc.LAST_JOB_ONE_FRAME}': {banks}")
+    assert {"k1r_h256", "k1r_h100", "k1r_h256_align4"} == {name for name, _ in banks}
     if VARIANT:   # the references of the sensitivity check are themselves untouched by the variant
         assert cc.references_have_one_job(dcu, VARIANT)
 

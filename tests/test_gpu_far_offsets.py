@@ -10,7 +10,9 @@ An offset truncated to 32 bits wraps to a lower, valid address of the same buffe
   4  every kernel family writes magnitudes, half rows, complex rows, pixel columns, bands and peak columns past 2^31 and 2^32 bytes; so
      do sgx_istft_batch (hops beyond the window: the gaps exact zeros) and, with their input past 2^32 bytes as well, sgx_render_mags,
      sgx_magnitude_in and sgx_render_bands, one context per kernel body, the body derived on the device from the launchers' own
-     quantities.  (Not here: sgx_image_* and sgx_view_* on rings of more than 2^32 bytes.)
+     quantities.  The filterbank calls write 1024 single-bin sums per frame past both marks on the fused family and on one workspace
+     family, and their stages alone (sgx_fbank_mags, sgx_fbank_cross_spec) on 64-point columns; their probe rows are held to the header's
+     definition (tests/fbank_reference.py) bit for bit.  (Not here: sgx_image_* and sgx_view_* on rings of more than 2^32 bytes.)
 The streams of 1 - 3 lie in NaN arenas where only the samples the call's frames own hold noise.  Results are compared bit for bit with
 a compact replay (the same samples at the same address modulo 16 and the same frame parity in a small fresh tensor); magnitudes and
 complex rows are also held to the float64 truth at the bound the project holds white noise to (conftest.KERNEL_BOUND / chirpz_bound,
@@ -24,6 +26,7 @@ import pytest
 import bounds_arena as ba
 import edge_signals as es
 import far_offsets as fo
+import fbank_reference as fr
 import oracle
 from conftest import KERNEL_BOUND, chirpz_bound, mags_error
 from test_gpu_bounds import words
@@ -102,7 +105,19 @@ def gpu():
         print(f"FAR-WORST {k} {_worst[k]:.4f}")
 
 
+def far_bank_of(eng):
+    """the context's bank of the far-offset cases (far_offsets.far_bank at power 2), made once"""
+    if getattr(eng, "_far_bank", None) is None:
+        eng._far_bank = eng.filterbank(*fo.far_bank(eng.M), power=2)
+        assert eng._far_bank.n_filters == fo.BANK_FILTERS
+    return eng._far_bank
+
+
 def run(eng, kind, pcm, first, n, out=None):
+    if kind == "fbank":
+        return far_bank_of(eng).batch(pcm, first, n, out=out)
+    if kind == "fbank_cross":
+        return far_bank_of(eng).cross_batch(pcm, first, n, out=out)
     if kind.startswith("peak_"):
         return eng.bands_peak_batch(pcm, int(kind[5:]), first, n, out=out)
     f = {"stft": eng.stft_batch, "f16": eng.stft_batch_f16, "complex": eng.stft_batch_complex, "render": eng.render_batch,
@@ -308,7 +323,7 @@ def run_hop_case(g, case, eng, eng_small, rows_eng, stream_i, stream, grad):
 
 
 # ---- part 4: outputs past 2^31 and 2^32 bytes --------------------------------------------------------------------------------------------
-ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "peak_2": "f32"}
+ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "peak_2": "f32", "fbank": "f32", "fbank_cross": "f32"}
 
 
 def count_equal(torch, t, word):
@@ -353,6 +368,9 @@ def test_output_marks(gpu, case):
     W, H, Cn = r.W, r.H, r.channels
     eng = g.engine(r) if case.R == fo.ROWS_DEFAULT else g.engine(r, rows=case.R)
     assert eng.R == case.R and eng.pairs == 1 and fo.out_row_bytes(r, kind, eng.R) == rb
+    if kind in fo.BANK_KINDS:   # the fused kernel on the 4096-point family, the workspace and the stage kernel on the other
+        fb = far_bank_of(eng)
+        assert (fb.fused, fb.cross_fused) == (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)) == ((1, 1) if case.family == "k1_lr" else (0, 0))
     F, rows, rw, group = case.frames, case.rows, rb // 4, case.group
     pcm = eng.white_noise(case.n_samples, seed=fo.NOISE_SEED)
     assert eng.num_frames(case.n_samples) == F
@@ -400,6 +418,13 @@ def test_output_marks(gpu, case):
             ratio = truth.hold(f"{case.id} row {k}", t0, got if kind == "stft" else None, got if kind == "complex" else None)
             worst = max(worst, ratio)
             assert ratio <= 1.0, (case.id, k, ratio, "misses the float64 truth")
+        elif kind == "fbank":   # the header's definition over the engine's own rows of that frame (tests/fbank_reference.py), bit for bit
+            want = fr.bank_sums(eng.stft_batch(pcm, first, n)[j].cpu().numpy(), fo.far_bank(eng.M), 2)
+            assert np.array_equal(one[j].cpu().numpy().view(np.uint32), want.view(np.uint32)), (case.id, k, "differs from the definition over the engine's rows")
+        elif kind == "fbank_cross":
+            spec = torch.view_as_real(eng.stft_batch_complex(pcm, first, n))[j].cpu().numpy()
+            want = fr.cross_sums(spec, fo.far_bank(eng.M))
+            assert np.array_equal(one[j].cpu().numpy().view(np.uint32), want.view(np.uint32)), (case.id, k, "differs from the definition over the engine's rows")
         elif kind == "render":
             mags = own_rows(g, case, eng, pcm, first, n)[j, 0].cpu().numpy()
             want = oracle.render_columns(mags[None], sr, grad, R=eng.R)[0]
@@ -624,3 +649,61 @@ def run_pixel_case(g, case, eng, grad):
             assert np.array_equal(one[0].cpu().numpy()[picked].view(np.uint32), want.view(np.uint32)), (case.id, k, "differs from the oracle's band means")
     del buf, payload, src, src_cols
     torch.cuda.synchronize()
+
+
+# ---- part 4, the filterbank stages alone: sgx_fbank_mags, sgx_fbank_cross_spec with an output past 2^32 bytes -----------------------------
+@pytest.mark.parametrize("case", fo.BANK_STAGE_CASES, ids=lambda c: c.id)
+def test_bank_stage_marks(gpu, case):
+    """the stage kernels place a column's sums at `col * n_filters`: with 1024 filters the element index passes 2^28 and 2^29 (bytes 2^31 and
+    2^32) at columns the case probes.  The guard, the prefill, the checksum in pieces, and the probe columns against the header's definition
+    (tests/fbank_reference.py) bit for bit"""
+    from spectrogram_rs_amd import SpectrogramEngine
+    g, torch = gpu, gpu.torch
+    eng = SpectrogramEngine(es.SR, device=0, window_samples=case.W, hop_samples=case.W // 2, channels=2)
+    try:
+        assert eng.M == case.M
+        bank = fo.far_bank(eng.M)
+        fb = eng.filterbank(*bank, power=2)
+        cross = case.entry == "fbank_cross_spec"
+        cols, iw, ow = case.cols, case.in_col_bytes // 4, case.out_col_bytes // 4
+        call = (lambda src, out=None: fb.cross_apply(src.view(-1, eng.M, 2, 2), out=out)) if cross else \
+            (lambda src, out=None: fb.apply(src.view(-1, eng.M, 2), out=out))
+        # the engine's noise as it is for the complex rows (either sign), its squares plus 1e-7 as magnitudes
+        src = eng.white_noise(cols * iw, seed=fo.NOISE_SEED, channels=1)
+        if not cross:
+            src.mul_(src).add_(1e-7)
+        before = eng.checksum(src)
+        prefill, guard = ba.as_i32(ba.prefill_word("f32", False)), ba.as_i32(ba.GUARD_WORD)
+        total = cols * ow
+        buf = torch.full((total + ba.guard_bytes(case.out_col_bytes) // 4,), prefill, dtype=torch.int32, device="cuda")
+        buf[total:] = guard
+        payload = buf[:total]
+        call(src, out=payload.view(torch.float32))
+        # (a)
+        assert bool((buf[total:] == guard).all()), (case.id, "the guard was written")
+        left = count_equal(torch, payload, prefill)
+        assert left == 0, (case.id, left, "words still hold the prefill")
+        assert eng.checksum(src) == before, (case.id, "the input was written")
+        # (c) pieces of columns below 2^31 bytes of output, each into a small buffer of its own
+        whole = eng.checksum(payload)
+        per = max(n for _, n in case.pieces())
+        piece_out = torch.empty(per * ow, dtype=torch.int32, device="cuda")
+        pieces = 0
+        for a, n in case.pieces():
+            piece_out[:n * ow] = prefill
+            call(src[a * iw:(a + n) * iw], out=piece_out.view(torch.float32))
+            pieces = (pieces + eng.checksum(piece_out[:n * ow], base_word=a * ow)) % (1 << 64)
+        assert whole == pieces, (case.id, "the checksum of the whole differs from the sum over the pieces")
+        del piece_out
+        # (b) the columns whose sums hold a mark, their neighbours, the first and the last
+        for k in case.probes():
+            col = src[k * iw:(k + 1) * iw].clone()
+            one = call(col)
+            assert torch.equal(words(torch, one), payload[k * ow:(k + 1) * ow]), (case.id, k, "differs from a call of that column alone")
+            host = col.cpu().numpy()
+            want = fr.cross_sums(host.reshape(1, eng.M, 2, 2), bank) if cross else fr.bank_sums(host.reshape(1, eng.M, 2), bank, 2)
+            assert np.array_equal(one.cpu().numpy().view(np.uint32), want.view(np.uint32)), (case.id, k, "differs from the definition")
+        del buf, payload, src
+    finally:
+        torch.cuda.synchronize()
+        eng.close()

@@ -4,7 +4,9 @@ The contract is that a bank's output is a pure function of the frame's row and t
 workspace route elsewhere -- equals sgx_fbank_mags over sgx_stft_batch's rows bit for bit, on every transform family, sub-range, frame
 count, compute-unit limit and stream.  The values are held to the float64 sum over the engine's own float32 rows within the standard
 bound of a float32 sum of `count` products in any order, (count + 2) 2^-24 sum |w| x^p, and end to end to the float64 truth of the
-float32-windowed frame within the rows' own allowance (tests/conftest.py) carried through the bank."""
+float32-windowed frame within the rows' own allowance (tests/conftest.py) carried through the bank.
+(Every route runs one device body, so "bit-identical across routes" here compares that body with itself; tests/test_gpu_fbank_order.py
+holds it to the header's sum order computed on the host, bit for bit.)"""
 import ctypes as C
 import functools
 

@@ -6,7 +6,9 @@ on every transform family, sub-range, compute-unit limit and stream.  The values
 float32 rows within a derived bound: any path has at most 2 roundings in a product term, ceil(count / 64) in a lane's chain and 6 in the
 tree, each relative 2^-24, plus one unit for the second-order terms: (ceil(count / 64) + 9) 2^-24 sum |w| m, m the sum of the absolute
 products of the term.  End to end the sums are held to the float64 truth of the float32-windowed frame within the complex rows' own
-allowance (tests/conftest.py) carried through the products."""
+allowance (tests/conftest.py) carried through the products.
+(Every route runs one device body, so "bit-identical across routes" here compares that body with itself; tests/test_gpu_fbank_order.py
+holds it to the header's products and sum order computed on the host, bit for bit.)"""
 import ctypes as C
 import functools
 

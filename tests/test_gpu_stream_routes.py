@@ -17,8 +17,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bounds_arena as ba
 import edge_signals as es
 import far_offsets as fo
+import fbank_reference as fr
 import stream_cases as sc
 from test_gpu_streams import SLEEP_CYCLES
 
@@ -87,8 +89,8 @@ def hold(g, eng, enqueue, what):
 class RouteCalls:
     """the calls of one run of a row, through the C ABI only, into buffers of their own"""
 
-    def __init__(self, torch, eng, r, entries, held):
-        self.torch, self.eng, self.lib, self.r, self.entries = torch, eng, eng._lib, r, entries
+    def __init__(self, torch, eng, r, entries, held, fb):
+        self.torch, self.eng, self.lib, self.r, self.entries, self.fb = torch, eng, eng._lib, r, entries, fb
         F = self.F = sc.frames_of(r)
         n = self.n = (F - 1) * r.H + r.W
         Cn, P, M, R = r.channels, eng.pairs, eng.M, eng.R
@@ -104,7 +106,11 @@ class RouteCalls:
             "bands": buffer(torch, (F, P, R, 2), f32, flt), "peak_3": buffer(torch, (cols, P, R, 2), f32, flt),
             "render_mags": buffer(torch, (F * P, R, 4), u8, pix), "magnitude_in": buffer(torch, (F * P, R, 2), f32, flt),
             "render_bands": buffer(torch, (F * P, R, 4), u8, pix), "checksum_add": torch.zeros(1, dtype=torch.int64, device="cuda"),
+            "fbank": buffer(torch, (F, P, fb.n_filters, 2), f32, flt), "fbank_mags": buffer(torch, (F * P, fb.n_filters, 2), f32, flt),
+            "fbank_cross_spec": buffer(torch, (F * P, fb.n_filters, 4), f32, flt),
         }
+        if "fbank_cross" in entries:
+            self.out["fbank_cross"] = buffer(torch, (F, P, fb.n_filters, 4), f32, flt)
         if "istft" in entries:
             self.out["istft"] = buffer(torch, (n, Cn), f32, flt)
         ends = eng.bin_edges()
@@ -130,6 +136,11 @@ class RouteCalls:
                 ck(lib.sgx_magnitude_in(ctx, ptr(o["stft"]), F * e.pairs, self.ranges.ctypes.data_as(C.c_void_p), e.R, ptr(o[entry])))
             elif entry == "render_bands":
                 ck(lib.sgx_render_bands(ctx, ptr(o["bands"]), F * e.pairs, ptr(o[entry])))
+            elif entry in ("fbank", "fbank_cross"):
+                ck(getattr(lib, sc.SYMBOL[entry])(self.fb._h, ptr(self.pcm), n, 0, F, ptr(o[entry]), C.byref(got)))
+                assert got.value == F, (r.name, entry)
+            elif entry in ("fbank_mags", "fbank_cross_spec"):
+                ck(getattr(lib, sc.SYMBOL[entry])(self.fb._h, ptr(o[sc.READS[entry]]), F * e.pairs, ptr(o[entry])))
             else:
                 assert entry == "checksum_add"
                 ck(lib.sgx_checksum_add(ctx, ptr(o["stft"]), o["stft"].numel() * 4, 0, ptr(o[entry])))
@@ -159,12 +170,15 @@ def test_route_on_a_held_stream(gpu, row):
     r, entries = es.ROUTE[row], sc.by_row()[row]
     eng = open_route(r)
     try:
+        # the bank of the sweep, made before any sleep kernel is queued (sgx_fbank_create may wait for its own uploads)
+        fb = eng.filterbank(*fr.edge_bank(eng.M), power=2)
+        assert (fb.fused, fb.cross_fused) == (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)), (row, fb.fused, fb.cross_fused)
         assert eng._lib.sgx_set_stream(eng._ctx, None) == 0                 # the NULL stream
-        warm, want = RouteCalls(torch, eng, r, entries, False), RouteCalls(torch, eng, r, entries, False)
+        warm, want = RouteCalls(torch, eng, r, entries, False, fb), RouteCalls(torch, eng, r, entries, False, fb)
         warm.enqueue(sc.SEED_A)          # a: the lazy allocations, the inverse's tables, the range tables
         want.enqueue(sc.SEED_B)          # b: the reference
         warm.enqueue(sc.SEED_A)          # c: the context's own buffers hold another stream's state
-        held = RouteCalls(torch, eng, r, entries, True)                     # d
+        held = RouteCalls(torch, eng, r, entries, True, fb)                 # d
         hold(gpu, eng, lambda S: held.enqueue(sc.SEED_B), row)              # e, f
         assert not same_bytes(torch, warm.out["stft"], want.out["stft"])    # (the stale state IS another state)
         render_fused, bands_fused = bool(eng.info.render_path & 1), bool(eng.bands_fused)
@@ -345,11 +359,18 @@ def rebind_engine(kw):
     return eng
 
 
-def rebind_setup(torch, eng, method):
+def rebind_setup(torch, eng, method, first_stream):
     """two streams of samples, their results from two calls made one after the other on the NULL stream, the context's buffers left in the
-    state of the first, and two prefilled outputs (out=: the caching allocator plays no part)"""
+    state of the first, and two prefilled outputs (out=: the caching allocator plays no part).  A method "fbank_<m>" is FilterBank.<m> of
+    a bank created while the context is bound to first_stream."""
     n = (REBIND_FRAMES - 1) * eng.H + eng.W
-    f = getattr(eng, method)
+    if method.startswith("fbank_"):
+        with torch.cuda.stream(first_stream):
+            fb = eng.filterbank(*fr.edge_bank(eng.M), power=2)     # (the wrapper binds the context to first_stream, then creates)
+        assert fb.fused == 0
+        f = getattr(fb, method[len("fbank_"):])
+    else:
+        f = getattr(eng, method)
     pcm = [eng.white_noise(n, seed=s) for s in (sc.SEED_A, sc.SEED_B)]
     want = [f(p).clone() for p in pcm]
     f(pcm[0])
@@ -366,7 +387,7 @@ def test_rebinding_a_busy_context_orders_the_new_stream_behind_the_old(gpu, name
     a, b = gpu.streams
     eng = rebind_engine(kw)
     try:
-        f, pcm, want, outs = rebind_setup(torch, eng, method)
+        f, pcm, want, outs = rebind_setup(torch, eng, method, a)
         with torch.cuda.stream(a):
             torch.cuda._sleep(SLEEP_CYCLES)
             f(pcm[0], out=outs[0])
@@ -393,7 +414,7 @@ def test_rebinding_to_the_same_stream_keeps_the_host_ahead(gpu):
     name, kw, method = sc.REBIND_CASES[0]
     eng = rebind_engine(kw)
     try:
-        f, pcm, want, outs = rebind_setup(torch, eng, method)
+        f, pcm, want, outs = rebind_setup(torch, eng, method, a)
         with torch.cuda.stream(a):
             torch.cuda._sleep(SLEEP_CYCLES)
             f(pcm[0], out=outs[0])            # the wrapper binds to a ...

@@ -17,10 +17,13 @@ def test_every_row_of_routes_is_in_the_table():
 
 def test_every_entry_point_the_route_serves_is_listed():
     rows = sc.by_row()
-    always = set(sc.BATCH) | set(sc.STAGE)
+    always = (set(sc.BATCH) | set(sc.STAGE)) - {"fbank_cross"}
+    assert {"fbank", "fbank_mags", "fbank_cross_spec"} <= always
     for r in es.ROUTES:
         listed = set(rows[r.name])
         assert always <= listed, (r.name, always - listed)
+        # the cross sums from PCM: every context with an (l, r) pair (the stage serves the mono rows as well)
+        assert ("fbank_cross" in listed) == (r.channels >= 2), r.name
         # the inverse: every length an in-LDS kernel serves, i.e. every row but kernel 11's
         assert ("istft" in listed) == (r.kernel != 11), r.name
         assert listed == set(sc.entries_served(r))
@@ -30,7 +33,10 @@ def test_every_entry_point_the_route_serves_is_listed():
     assert set(sc.SYMBOL.values()) <= exported and len(set(sc.SYMBOL.values())) == len(sc.ENTRIES) == len(sc.SYMBOL)
     enqueue_only = {n for n in exported if n.startswith(("sgx_stft_batch", "sgx_render_", "sgx_bands_", "sgx_istft_batch"))}
     enqueue_only -= {"sgx_bands_fused", "sgx_bands_peak_fused"}
-    assert enqueue_only | {"sgx_magnitude_in", "sgx_checksum_add"} == set(sc.SYMBOL.values())
+    banks = {n for n in exported if n.startswith("sgx_fbank_")} - {"sgx_fbank_create", "sgx_fbank_destroy", "sgx_fbank_filters", "sgx_fbank_fused",
+                                                                      "sgx_fbank_cross_fused"}
+    assert banks == {"sgx_fbank_batch", "sgx_fbank_mags", "sgx_fbank_cross_batch", "sgx_fbank_cross_spec"}
+    assert enqueue_only | banks | {"sgx_magnitude_in", "sgx_checksum_add"} == set(sc.SYMBOL.values())
     assert set(sc.READS) == {"istft"} | set(sc.STAGE) and set(sc.READS.values()) <= set(sc.BATCH)
     assert sc.HOST_WAITS == {}
 
@@ -38,7 +44,8 @@ def test_every_entry_point_the_route_serves_is_listed():
 def test_no_case_is_listed_twice():
     count = collections.Counter((c.row, c.entry) for c in sc.CASES)
     assert max(count.values()) == 1
-    assert len(sc.CASES) == len(es.ROUTES) * (len(sc.ENTRIES) - 1) + sum(1 for r in es.ROUTES if r.kernel != 11)
+    assert len(sc.CASES) == (len(es.ROUTES) * (len(sc.ENTRIES) - 2) + sum(1 for r in es.ROUTES if r.kernel != 11)
+                             + sum(1 for r in es.ROUTES if r.channels >= 2))
     for cases in (sc.VIEW_CASES, sc.IMAGE_CASES, sc.PIXEL_CASES):
         names = [c.name for c in cases]
         assert len(names) == len(set(names))
@@ -76,6 +83,18 @@ def test_every_helper_pass_is_taken_by_some_case():
     assert {es.ROUTE[row].kernel for row, _ in taken["large_passes"]} == {11} and {e for _, e in taken["large_passes"]} == set(sc.BATCH)
     assert {es.ROUTE[row].kernel for row, _ in taken["ladder"]} == {4}
     assert len(taken["inverse"]) == len(es.ROUTES) - 8
+    # the bank calls: one kernel on the 4096-point kernels (behind the de-interleave pass on 4 and 8 channels, above), the workspace and
+    # the stage everywhere else -- the frame pairs and the complex mono transform of that kernel included
+    assert {e for _, e in taken["workspace_fbank"]} == {"fbank"} and {e for _, e in taken["workspace_fbank_cross"]} == {"fbank_cross"}
+    unfused = {r.name for r in es.ROUTES if r.kernel != 2} | {"k1_complex_mono", "k1_paired_mono"}
+    assert {row for row, _ in taken["workspace_fbank"]} == unfused
+    assert {row for row, _ in taken["workspace_fbank_cross"]} == {n for n in unfused if es.ROUTE[n].channels >= 2}
+    for row in ("k1_ch4", "k1_ch8"):
+        assert sc.helpers(es.ROUTE[row], "fbank", True, True) == sc.helpers(es.ROUTE[row], "fbank_cross", True, True) == {"deinterleave"}
+    assert sc.helpers(es.ROUTE["k1_lr_h256"], "fbank_cross", True, True) == set()
+    assert sc.helpers(es.ROUTE["k16_mono_h512"], "fbank", False, False) == {"k16_plane", "workspace", "workspace_fbank"}
+    assert sc.helpers(es.ROUTE["bluestein_w23"], "fbank_cross", False, False) == {"ladder", "workspace", "workspace_fbank_cross"}
+    assert sc.helpers(es.ROUTE["k1r_h256"], "fbank_mags", True, True) == set()
     # one run of a persistent workgroup of the fused peak kernel is one frame here (23 frames on 4 n_cu workgroups): every column of three
     # frames crosses runs, so the combine pass writes every column
     assert sc.FRAMES < 4 * 64
@@ -105,4 +124,5 @@ def test_the_stand_alone_cases_cover_the_pixel_stage():
     assert sorted(-(-v.frames // v.viewport) for v in sc.VIEW_CASES) == [2, 3]
     # the ring laps itself and ends at an offset other than 0: the scrolled read composes two parts
     assert all(i.W != 2048 and i.width < sc.FRAMES and sc.FRAMES % i.width for i in sc.IMAGE_CASES)
-    assert [kw["window_samples"] for _, kw, _ in sc.REBIND_CASES] == [8192] * 3
+    assert [kw["window_samples"] for _, kw, _ in sc.REBIND_CASES] == [8192] * 4
+    assert [m for _, _, m in sc.REBIND_CASES if m.startswith("fbank_")] == ["fbank_batch"]
