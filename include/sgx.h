@@ -86,7 +86,10 @@ typedef struct sgx_config {
     uint32_t hop_samples;    /* if non-zero, H directly (stride ignored)                        */
     uint32_t channels;       /* interleaved channels in the PCM stream: 1 = mono, expanded to
                                 (s, s) as audio_input_list_model.rs:67-69 does; 2 = (l, r);
-                                2k = k independent (l, r) pairs (extension, BASELINE config 4)  */
+                                2k = k independent (l, r) pairs (extension, BASELINE config 4),
+                                at most 32768; odd counts above 1 are refused.  Every family
+                                and entry point is held to the truth at 6, 12, 64 and 32768
+                                channels by tests/test_gpu_channel_counts.py                  */
     uint32_t rows;           /* R, pixel rows per column (default 1024)                         */
     double f_min, f_max;     /* log axis range in Hz (default 32, 22030)                        */
     float min_db, max_db;    /* default -70, -10                                                */
