@@ -40,6 +40,17 @@ extern "C" {
     pub fn sgx_bands_peak_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
                                 group: usize, d_peak: *mut f32, n_out: *mut usize) -> c_int;   // peak-hold of the bands over groups of frames
     pub fn sgx_bands_peak_fused(ctx: *const SgxCtx) -> c_int;
+    // Welch-averaged spectra per bin: the mean over groups of frames of |X|^2 (psd) and of the four (L, R) products (csd)
+    pub fn sgx_psd_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                         group: usize, d_psd: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [columns][pairs][M][2]
+    pub fn sgx_csd_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                         group: usize, d_csd: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [columns][pairs][M][4]
+    pub fn sgx_psd_mags(ctx: *mut SgxCtx, d_mags: *const f32, n_frames: usize, group: usize, d_psd: *mut f32,
+                        n_out: *mut usize) -> c_int;   // the stage alone, from magnitude rows
+    pub fn sgx_csd_spec(ctx: *mut SgxCtx, d_spec: *const f32, n_frames: usize, group: usize, d_csd: *mut f32,
+                        n_out: *mut usize) -> c_int;   // the stage alone, from complex rows
+    pub fn sgx_psd_fused(ctx: *const SgxCtx) -> c_int;
+    pub fn sgx_csd_fused(ctx: *const SgxCtx) -> c_int;
     pub fn sgx_render_bands(ctx: *mut SgxCtx, d_bands: *const f32, n_columns: usize, d_rgba: *mut u8) -> c_int;   // color_for over band columns
     // filterbanks: weighted sums of bin magnitudes or powers over sparse filters (mel, bark, third octaves ...)
     pub fn sgx_fbank_create(ctx: *mut SgxCtx, n_filters: u32, h_first: *const u32, h_count: *const u32, h_weights: *const f32,

@@ -13,7 +13,7 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
  *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -303,6 +303,62 @@ SGX_API int sgx_bands_peak_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samp
                                  size_t group, float *d_peak, size_t *n_out);
 /* 1: one kernel from PCM to peak columns (plus at most one combine pass over partial columns); 0: the workspace route; < 0: error */
 SGX_API int sgx_bands_peak_fused(const sgx_ctx *ctx);
+
+/* ---- Welch-averaged spectra per bin: the mean over groups of frames ------------------------------------------------------------------
+ * The standard spectrum estimate (Welch's method: scipy.signal.welch, csd, coherence) at full bin resolution: a noise floor, a long-term
+ * average spectrum, and -- from the cross terms -- a transfer function or a coherence.  (The coherence quotient stated at
+ * sgx_fbank_cross_batch is identically 1 for one frame and a one-bin band; it means something only after the four terms have been
+ * averaged over frames, which is what sgx_csd_batch does.)
+ *
+ * Frames and columns as sgx_bands_peak_batch: frames [first_frame, first_frame + max_frames) that exist are the F frames of the call;
+ * column j = 0 .. ceil(F / group) - 1 covers frames first_frame + [j * group, min((j + 1) * group, F)), n_j of them; the last column may
+ * cover fewer.  group = 0: SGX_ERR_INVALID_ARG.  Any group up to SIZE_MAX (one column).  *n_out = number of COLUMNS.
+ * Per frame, pair and stored bin the summand x is
+ *   psd: x = rn(m * m) per side, m exactly the float32 that sgx_stft_batch stores (the x of a power-2 filterbank);
+ *   csd: x0 .. x3 exactly as sgx_fbank_cross_batch defines them from the words sgx_stft_batch_complex stores (every product rounded, one
+ *        add or subtract, no contraction).
+ * The mean of a column, per bin and component; the order is part of the definition:
+ *   1. the column's frames form blocks of 32 consecutive frames counted from the column's first frame (the last block may be shorter); a
+ *      block's partial is one chain of float32 adds from +0 in ascending frame order, s = rn(s + x), the add never contracted with the
+ *      product;
+ *   2. the column's sum S is one chain of float64 adds from +0 over its block partials in ascending order;
+ *   3. the output is (float)(S / (double)n_j): one float64 division, rounded once to float32.
+ * The block length 32 is fixed here: it does not depend on the device, the compute-unit limit, the route or the chunking.  The output is
+ * therefore a pure function of the rows: bit-identical across routes, compute-unit limits, streams, chunk seams and any split of a call
+ * at a column boundary (tests/test_gpu_psd.py), and numpy reproduces it bit for bit without a fused multiply-add (a float32 cumsum along
+ * the frames of a block, a float64 cumsum over the blocks: tests/psd_reference.py).  group = 1 gives exactly rn(m * m), or x0 .. x3.
+ * Against the float64 mean of the float64 products of the same float32 rows the error is at most 35 * 2^-24 times the mean of the
+ * absolute products of the term (1 rounding for the product, 31 for the chain, 1 for the cast, 2 for second-order terms).
+ *
+ * Scaling.  The rows are scaled 2 / W, so a stationary sinusoid of amplitude A at a bin centre gives psd = (A * S1 / W)^2 at that bin,
+ * with S1 = sum of w and S2 = sum of w^2 over w = sgx_window.  With p a psd value (or a csd component):
+ *   the one-sided power spectrum, mean square per bin (A^2 / 2 for that sinusoid):   p * W^2 / (2 * S1^2);
+ *   the one-sided power spectral density per Hz at sample rate fs:                   p * W^2 / (2 * fs * S2)
+ * (scipy's scaling = 'spectrum' and 'density' for a window of W samples zero-padded to nfft = 2W, whose bins k = 1 .. W - 1 the rows hold).
+ * No logarithm, no dB, and no division of one output by another: the coherence (out2^2 + out3^2) / (out0 * out1), the transfer function
+ * (out2 - i out3) / out0 and their guards against small denominators are the caller's, as for the filterbanks.
+ *
+ * sgx_psd_batch: d_psd [n_out][pairs][M][2] float, (l, r) per bin; a mono stream holds (v, v) (with SGX_FLAG_PAIRED_FRAMES what the rows hold).
+ * sgx_csd_batch: d_csd [n_out][pairs][M][4] float, 16-byte aligned (else SGX_ERR_INVALID_ARG, nothing written); on a mono context
+ *   SGX_ERR_UNSUPPORTED (there L = R and the answer is x0, x0, x0, 0).
+ * sgx_psd_mags / sgx_csd_spec: the stage alone over rows already on the device, d_mags [n_frames][pairs][M][2] as sgx_stft_batch writes
+ *   them, d_spec [n_frames][pairs][M][2][2] as sgx_stft_batch_complex does (16-byte aligned; any channel count: mono rows give
+ *   x0 = x1 = x2 and x3 = +0).  Every W the library accepts.  n_frames == 0: *n_out = 0, not an error.
+ * Too few samples is *n_out = 0, not an error; a null buffer is SGX_ERR_INVALID_ARG; n_out may be NULL.  Stream-ordered and asynchronous;
+ * nothing waits on the host (a grown workspace may, as elsewhere); every kernel of a call goes onto the context's stream.  Device
+ * memory beyond the caller's buffers is bounded whatever F and group are: the 192 MiB workspace (rows of a range of frames and one
+ * float32 partial row per block of the range) plus one float64 row [pairs][M][4] for a column that spans ranges.
+ * sgx_psd_fused / sgx_csd_fused: 1 one kernel from PCM to block partials, 0 the workspace route (the rows of a range of frames by their
+ * own route, then a block kernel and a combine kernel over them), < 0 error.  This build answers 0 on every context: no fused mode has been
+ * built and measured against the workspace route. */
+SGX_API int sgx_psd_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                          size_t group, float *d_psd, size_t *n_out);
+SGX_API int sgx_csd_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                          size_t group, float *d_csd, size_t *n_out);
+SGX_API int sgx_psd_mags(sgx_ctx *ctx, const float *d_mags, size_t n_frames, size_t group, float *d_psd, size_t *n_out);
+SGX_API int sgx_csd_spec(sgx_ctx *ctx, const float *d_spec, size_t n_frames, size_t group, float *d_csd, size_t *n_out);
+SGX_API int sgx_psd_fused(const sgx_ctx *ctx);
+SGX_API int sgx_csd_fused(const sgx_ctx *ctx);
 /* ---- filterbanks: weighted sums of bin magnitudes or powers over overlapping filters ---------------------------------------------
  * What a mel, bark or ERB front end, a third-octave analyser, a chroma vector or an A-weighted level is (the reference has none: every
  * reduction there is magnitude_in, an unweighted mean).

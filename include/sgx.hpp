@@ -162,6 +162,69 @@ public:
         return out;
     }
 
+    // Welch's estimate at full bin resolution: the mean of the squared magnitudes over groups of `group` consecutive frames,
+    // ceil(frames / group) columns x (W-1) bins of (l, r) (sgx_psd_batch; include/sgx.h states the order of the sum and the scaling)
+    std::vector<Output> psd_stream(const StereoMagnitude *lr, std::size_t n, std::size_t group)
+    {
+        if (group == 0) throw Error(SGX_ERR_INVALID_ARG, "psd_stream: group is 0");
+        const std::size_t frames = sgx_num_frames(ctx_, n), m = num_output_frequencies(), cols = frames ? (frames - 1) / group + 1 : 0;
+        std::vector<Output> out(cols, Output(m));
+        if (!cols) return out;
+        reserve(n * 2 * sizeof(float), cols * m * 2 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        int rc = sgx_psd_batch(ctx_, d_in_, n, 0, frames, group, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(cols * m * 2);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < cols; ++f)
+            for (std::size_t j = 0; j < m; ++j) out[f][j] = {flat[(f * m + j) * 2], flat[(f * m + j) * 2 + 1]};
+        return out;
+    }
+    // the same mean of the four (L, R) products of every bin: columns x (W-1) bins of {|L|^2, |R|^2, Re L conj R, Im L conj R}
+    // (sgx_csd_batch; a context of at least two channels)
+    std::vector<std::vector<std::array<float, 4>>> csd_stream(const StereoMagnitude *lr, std::size_t n, std::size_t group)
+    {
+        if (group == 0) throw Error(SGX_ERR_INVALID_ARG, "csd_stream: group is 0");
+        const std::size_t frames = sgx_num_frames(ctx_, n), m = num_output_frequencies(), cols = frames ? (frames - 1) / group + 1 : 0;
+        std::vector<std::vector<std::array<float, 4>>> out(cols, std::vector<std::array<float, 4>>(m));
+        if (!cols) return out;
+        reserve(n * 2 * sizeof(float), cols * m * 4 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        int rc = sgx_csd_batch(ctx_, d_in_, n, 0, frames, group, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(cols * m * 4);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < cols; ++f)
+            for (std::size_t j = 0; j < m; ++j) {
+                const float *b = &flat[(f * m + j) * 4];
+                out[f][j] = {b[0], b[1], b[2], b[3]};
+            }
+        return out;
+    }
+    // the stage alone over rows already on the device (DEVICE pointers; stream-ordered, not waited for): the number of columns written
+    // (sgx_psd_mags: [n_frames][pairs][M][2] -> [columns][pairs][M][2]; sgx_csd_spec: [n_frames][pairs][M][2][2] -> [columns][pairs][M][4])
+    std::size_t psd_mags(const float *d_mags, std::size_t n_frames, std::size_t group, float *d_psd)
+    {
+        std::size_t got = 0;
+        const int rc = sgx_psd_mags(ctx_, d_mags, n_frames, group, d_psd, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        return got;
+    }
+    std::size_t csd_spec(const float *d_spec, std::size_t n_frames, std::size_t group, float *d_csd)
+    {
+        std::size_t got = 0;
+        const int rc = sgx_csd_spec(ctx_, d_spec, n_frames, group, d_csd, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        return got;
+    }
+    // 1: one kernel from PCM to block partials, 0: the workspace route (sgx_psd_fused, sgx_csd_fused)
+    int psd_fused() const { return sgx_psd_fused(ctx_); }
+    int csd_fused() const { return sgx_csd_fused(ctx_); }
+
     // the complex (L, R) spectra behind process_stream's magnitudes for every complete frame of `lr`: frames x (W-1) bins of
     // {L, R} (sgx_stft_batch_complex)
     std::vector<std::vector<std::array<std::complex<float>, 2>>> process_stream_complex(const StereoMagnitude *lr, std::size_t n)

@@ -107,6 +107,12 @@ SIGNATURES = [
     ("sgx_bands_fused", C.c_int, [_ctx]),
     ("sgx_bands_peak_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_bands_peak_fused", C.c_int, [_ctx]),
+    ("sgx_psd_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_csd_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_psd_mags", C.c_int, [_ctx, _vp, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_csd_spec", C.c_int, [_ctx, _vp, _sz, _sz, _vp, C.POINTER(_sz)]),
+    ("sgx_psd_fused", C.c_int, [_ctx]),
+    ("sgx_csd_fused", C.c_int, [_ctx]),
     ("sgx_render_bands", C.c_int, [_ctx, _vp, _sz, _vp]),
     ("sgx_fbank_create", C.c_int, [_ctx, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     ("sgx_fbank_destroy", None, [_vp]),

@@ -7,6 +7,7 @@
 
 #include "sgx_fbank.hpp"
 #include "sgx_gradients.inc"
+#include "sgx_psd.hpp"
 #include "sgx_internal.hpp"
 
 namespace {
@@ -277,6 +278,10 @@ Route stft_route(const sgx_ctx *c, uint32_t channels, Out kind, const sgx_fbank 
     case Out::kFbankCross:   // likewise, on a stream of (l, r) pairs
         fused = may_fuse && rows.family == Family::kWg4096 && sgx::wg4096_can_fuse_fbank_cross(c, bank);
         break;
+    case Out::kPsd:       // the means over groups of frames: no family accumulates them itself (no fused mode has been measured
+    case Out::kCsd:       // against this route: DESIGN.md), so the rows go through the workspace on every context
+        fused = false;
+        break;
     }
     rows.fused = fused;
     return rows;
@@ -381,6 +386,108 @@ int stft_batch(sgx_ctx *c, const char *who, const float *d_pcm, size_t n_samples
     const hipError_t e = run_call(c, stft_route(c, c->C, kind), d_pcm, first_frame, n, total, d_out, kind);
     if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": kernel launch").c_str());
     if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+// ---- Welch-averaged spectra per bin (sgx_psd.hpp): the means over columns of `group` frames of n frames' rows, into d_out ---------------
+// rows(f, m) answers the device pointer to the rows of frames [f, f + m) of the call, or null with its error recorded.  own_rows: it
+// writes them to the front of the workspace, at most as many frames as this function asks for at once (the batch calls); else they lie in
+// the caller's buffer (the stage calls) and the workspace holds block partials only.  A row and a block's partial row are the same size
+// (psd: [pairs][M][2] floats, csd: [pairs][M][4]), so the workspace's budget is counted in rows of either.
+//
+// The call's blocks are taken in ranges.  A range holds whole blocks, and whole columns where a column's blocks fit one range; a longer
+// column is taken alone, range by range, its float64 sums carried in the context's one carry row.  A row so long that the workspace does
+// not hold a block of rows beside one partial row is taken a few frames at a time, each piece continuing the block's chain where the last
+// one stopped.  The bits do not depend on any of it: the order of both chains is the header's.
+template <typename Rows>
+int psd_reduce(sgx_ctx *c, const char *who, bool cross, size_t n, size_t group, bool own_rows, Rows rows, float *d_out)
+{
+    namespace psd = sgx::psd;
+    const psd::Geometry geo = psd::geometry(n, group);
+    const size_t rpf = cross ? 2 : 1, row_floats = mags_bytes_per_frame(c) / sizeof(float) * rpf;
+    const size_t elems = (size_t)c->pairs * c->M, nc = cross ? 4 : 2;
+    // (the whole workspace per range: ranges of 96, 48, 24 and 12 MiB ran at 0.82, 0.58, 0.30 and 0.19 of this rate: profiles/psd.txt)
+    const size_t cap = kWorkspaceBytes / (row_floats * sizeof(float));
+    const size_t fpb = geo.g < psd::kBlock ? (size_t)geo.g : (size_t)psd::kBlock;   // frames per block, at most
+    const size_t all = (size_t)geo.blocks();
+    size_t per = cap, piece = SIZE_MAX;   // blocks per range; frames per piece of a range
+    if (own_rows) {
+        if (cap >= fpb + 1) per = cap / (fpb + 1);
+        else { per = 1; piece = cap > 1 ? cap - 1 : 1; }
+    }
+    if (per < 1) per = 1;
+    if (per > all) per = all;
+    const bool carried = geo.bpc > per;
+    if (!carried) per -= per % (size_t)geo.bpc;
+    size_t row_slots = 0;
+    if (own_rows) {
+        row_slots = piece != SIZE_MAX ? piece : per * fpb;
+        if (row_slots > n) row_slots = n;
+    }
+    int rc = ensure_workspace(c, (row_slots + per) * rpf);
+    if (rc != SGX_OK) return rc;
+    if (carried) {
+        const hipError_t e = c->d_psd_carry.grow(c->stream, elems * nc);
+        if (e != hipSuccess) return fail_hip(c, e, "hipMalloc(psd carry row)");
+    }
+    float *partial = c->d_ws_mags.get() + row_slots * row_floats;
+    for (size_t b = 0; b < all;) {
+        const size_t j = b / (size_t)geo.bpc;
+        size_t m = all - b < per ? all - b : per;
+        if (carried && m > (size_t)geo.column_block_end(j) - b) m = (size_t)geo.column_block_end(j) - b;
+        const size_t f_lo = (size_t)geo.block_first(b), f_hi = (size_t)geo.block_end(b + m - 1);
+        for (size_t f = f_lo; f < f_hi;) {
+            const size_t k = f_hi - f < piece ? f_hi - f : piece;
+            const float *src = rows(f, k);
+            if (!src) return SGX_ERR_HIP;
+            const hipError_t e = psd::launch_psd_blocks(c, cross, psd::BlockPiece{src, partial, geo, elems, b, m, f, f + k, f != f_lo ? 1u : 0u});
+            if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": block launch").c_str());
+            f += k;
+        }
+        const hipError_t e = psd::launch_psd_combine(c, cross, psd::CombinePiece{partial, d_out, c->d_psd_carry.get(), geo, elems, b, m});
+        if (e != hipSuccess) return fail_hip(c, e, (std::string(who) + ": combine launch").c_str());
+        b += m;
+    }
+    return SGX_OK;
+}
+
+// sgx_psd_batch and sgx_csd_batch: the rows (or the complex rows) of a range of frames by their own route into the workspace, then the two
+// kernels of sgx_psd.hip
+int psd_batch(sgx_ctx *c, const char *who, bool cross, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, size_t group,
+              float *d_out, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (c && group == 0) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": group is 0");
+    if (c && cross && c->C < 2) return fail(c, SGX_ERR_UNSUPPORTED, std::string(who) + ": a mono context has no (l, r) pair (L = R: the means are x0, x0, x0, 0)");
+    size_t total, n;
+    int rc = begin_batch(c, who, n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    if (cross && ((uintptr_t)d_out & 15u)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": the output must be 16-byte aligned");
+    const Out rows_kind = cross ? Out::kComplex : Out::kMags;
+    rc = psd_reduce(c, who, cross, n, group, true, [&](size_t f, size_t m) -> const float * {
+        const hipError_t e = rows_to_workspace(c, d_pcm, first_frame + f, m, total, rows_kind);
+        if (e != hipSuccess) { fail_hip(c, e, (std::string(who) + ": stft launch").c_str()); return nullptr; }
+        return c->d_ws_mags.get();
+    }, d_out);
+    if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = (size_t)sgx::psd::geometry(n, group).columns();
+    return SGX_OK;
+}
+
+// sgx_psd_mags and sgx_csd_spec: the same two kernels over the caller's rows
+int psd_stage(sgx_ctx *c, const char *who, bool cross, const float *d_rows, size_t n_frames, size_t group, float *d_out, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (group == 0) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": group is 0");
+    if (n_frames == 0) return SGX_OK;
+    if (!d_rows || !d_out) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    if (cross && (((uintptr_t)d_rows | (uintptr_t)d_out) & 15u)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": buffers must be 16-byte aligned");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const size_t row_floats = mags_bytes_per_frame(c) / sizeof(float) * (cross ? 2 : 1);
+    const int rc = psd_reduce(c, who, cross, n_frames, group, false, [&](size_t f, size_t) { return d_rows + f * row_floats; }, d_out);
+    if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = (size_t)sgx::psd::geometry(n_frames, group).columns();
     return SGX_OK;
 }
 
@@ -1012,6 +1119,42 @@ int sgx_bands_peak_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_
     }
     if (n_out) *n_out = n_cols;
     return SGX_OK;
+}
+
+// ---- Welch-averaged spectra per bin: the mean over groups of frames of |X|^2, and of the four (L, R) products (sgx_psd.hpp) --------------
+
+int sgx_psd_fused(const sgx_ctx *c)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    return stft_route(c, c->C, Out::kPsd).fused ? 1 : 0;
+}
+
+int sgx_csd_fused(const sgx_ctx *c)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    return stft_route(c, c->C, Out::kCsd).fused ? 1 : 0;
+}
+
+int sgx_psd_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, size_t group, float *d_psd,
+                  size_t *n_out)
+{
+    return psd_batch(c, "sgx_psd_batch", false, d_pcm, n_samples, first_frame, max_frames, group, d_psd, n_out);
+}
+
+int sgx_csd_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, size_t group, float *d_csd,
+                  size_t *n_out)
+{
+    return psd_batch(c, "sgx_csd_batch", true, d_pcm, n_samples, first_frame, max_frames, group, d_csd, n_out);
+}
+
+int sgx_psd_mags(sgx_ctx *c, const float *d_mags, size_t n_frames, size_t group, float *d_psd, size_t *n_out)
+{
+    return psd_stage(c, "sgx_psd_mags", false, d_mags, n_frames, group, d_psd, n_out);
+}
+
+int sgx_csd_spec(sgx_ctx *c, const float *d_spec, size_t n_frames, size_t group, float *d_csd, size_t *n_out)
+{
+    return psd_stage(c, "sgx_csd_spec", true, d_spec, n_frames, group, d_csd, n_out);
 }
 
 int sgx_render_bands(sgx_ctx *c, const float *d_bands, size_t n_columns, uint8_t *d_rgba)

@@ -171,6 +171,7 @@ struct sgx_ctx {
     sgx::DeviceBuffer<sgx::RowEntry> d_band_rows;
     sgx::DeviceBuffer<sgx::SampleEntry> d_band_samples;
     sgx::DeviceBuffer<float> d_levels;  // sgx_spectrum_levels: the bands' (l, r) means, [n_bars][2], grown on demand
+    sgx::DeviceBuffer<double> d_psd_carry;   // sgx_psd_batch / sgx_csd_batch: the running float64 row [pairs][M][4] of a column that spans chunks, grown on demand
 
     unsigned long long palette_gen = 0;  // bumped by every palette upload (sgx_view rebuilds its palette texture on a change)
 
@@ -197,8 +198,10 @@ namespace sgx {
 // sgx_stft_batch_complex [F][pairs][M][2][2] floats, or the fused column: RGBA pixels [F][pairs][R][4] bytes, the rows' (l, r) means as
 // float2 [F][pairs][R] (sgx_bands_batch), or those held as a maximum over groups of frames, float2 [ceil(F / group)][pairs][R]; or the
 // weighted sums of a filterbank over the magnitudes, float2 [F][pairs][n_filters] (sgx_fbank_batch), or over the four products of the
-// (L, R) pair, float4 [F][pairs][n_filters] (sgx_fbank_cross_batch).
-enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak, kFbank, kFbankCross };
+// (L, R) pair, float4 [F][pairs][n_filters] (sgx_fbank_cross_batch); or the means over groups of frames of the squared magnitudes, float2
+// [ceil(F / group)][pairs][M] (sgx_psd_batch), and of the four products, float4 [ceil(F / group)][pairs][M] (sgx_csd_batch).  No family
+// writes the last two itself: their route is the rows into the workspace and the kernels of sgx_psd.hip over them.
+enum class Out { kMags, kMagsF16, kComplex, kRgba, kBands, kPeak, kFbank, kFbankCross, kPsd, kCsd };
 // `total`: frames the stream holds (mono transforms carry frame pairs and pair by global index).  channels and pairs are the CALL's, not the
 // context's: sgx_process_one runs a two-channel frame (2, 1) on a context of any channel count.  peak_group (kPeak): 1 .. n.  bank (kFbank,
 // kFbankCross): the filterbank whose sums the call writes.

@@ -310,6 +310,73 @@ class SpectrogramEngine:
         """1 when bands_peak_batch runs one kernel from PCM to peak columns (plus a combine pass), 0 on the workspace route"""
         return self._check(self._lib.sgx_bands_peak_fused(self._ctx))
 
+    # ---- Welch-averaged spectra per bin -----------------------------------------------------
+    def _welch_batch(self, fn, comps, pcm, group, first_frame, max_frames, out):
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        group = int(group)
+        cols = -(-n // group) if group > 0 else 0
+        out = self._out(out, (cols, self.pairs, self.M, comps), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(fn(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n, min(group, 2 ** 64 - 1),
+                           C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == cols
+        return out
+
+    def _welch_rows(self, fn, comps, rows, row_floats, group, out):
+        import torch
+
+        assert rows.dtype == torch.float32 and rows.numel() % row_floats == 0, "expected whole float32 rows of this context"
+        n = rows.numel() // row_floats
+        group = int(group)
+        cols = -(-n // group) if group > 0 else 0
+        out = self._out(out, (cols, self.pairs, self.M, comps), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(fn(self._ctx, self._dev_f32(rows), n, min(group, 2 ** 64 - 1), C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == cols
+        return out
+
+    def psd_batch(self, pcm, group: int, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [ceil(frames / group)][pairs][M][2] float32: Welch's estimate per bin, the mean of stft_batch's squared magnitudes
+        over groups of `group` consecutive frames (the last group may be shorter).  include/sgx.h states the order of the sum, which
+        makes the result a pure function of the rows, and the factors to a power spectrum or a density per Hz.  Mono holds (v, v)."""
+        return self._welch_batch(self._lib.sgx_psd_batch, 2, pcm, group, first_frame, max_frames, out)
+
+    def csd_batch(self, pcm, group: int, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [ceil(frames / group)][pairs][M][4] float32: the means over groups of frames of |L|^2, |R|^2, Re L conj R and
+        Im L conj R per bin (the products as FilterBank.cross_batch defines them).  A context of at least two channels."""
+        return self._welch_batch(self._lib.sgx_csd_batch, 4, pcm, group, first_frame, max_frames, out)
+
+    def psd_mags(self, mags, group: int, out=None):
+        """The stage of psd_batch alone: float32 [frames][pairs][M][2] rows, as stft_batch writes them -> [columns][pairs][M][2]"""
+        return self._welch_rows(self._lib.sgx_psd_mags, 2, mags, self.pairs * self.M * 2, group, out)
+
+    def csd_spec(self, spec, group: int, out=None):
+        """The stage of csd_batch alone: the complex64 [frames][pairs][M][2] that stft_batch_complex returns, or its float32
+        [frames][pairs][M][2][2] view -> [columns][pairs][M][4].  Any channel count: mono rows give x0 = x1 = x2 and x3 = +0."""
+        import torch
+
+        if spec.dtype == torch.complex64:
+            spec = torch.view_as_real(spec)
+        return self._welch_rows(self._lib.sgx_csd_spec, 4, spec.contiguous(), self.pairs * self.M * 4, group, out)
+
+    @property
+    def psd_fused(self) -> int:
+        """1 when psd_batch runs one kernel from PCM to block partials, 0 on the workspace route"""
+        return self._check(self._lib.sgx_psd_fused(self._ctx))
+
+    @property
+    def csd_fused(self) -> int:
+        """1 when csd_batch runs one kernel from PCM to block partials, 0 on the workspace route"""
+        return self._check(self._lib.sgx_csd_fused(self._ctx))
+
     # ---- filterbanks ------------------------------------------------------------------------
     def filterbank(self, first, count, weights, power: int = 2) -> "FilterBank":
         """A bank of sparse filters over the M stored bins (include/sgx.h states the definition): filter f weighs the bins
