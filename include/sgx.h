@@ -196,6 +196,16 @@ SGX_API int sgx_sync(sgx_ctx *ctx);
 SGX_API int sgx_set_cu_limit(sgx_ctx *ctx, uint32_t n);
 SGX_API uint32_t sgx_cu_limit(const sgx_ctx *ctx);   /* the count in force; 0 for a null context */
 
+/* Diagnostic: how the rows calls (sgx_stft_batch, _f16, _complex) of a mono W 2048 context deal their frame pairs ("jobs") to the
+ * persistent workgroups. By default a long float or half rows call deals 12/16 of them as one static run per workgroup and lets the
+ * workgroups claim the rest in chunks of 8, so that all finish together; a call that would leave static runs of fewer than 64 jobs,
+ * and every complex rows call, is dealt statically.
+ * (16, 0): always static. (0, 0): the default rule. Any other share 0 .. 16 with a chunk of 1 .. 2^20 jobs: that split at any size.
+ * Anything else: SGX_ERR_INVALID_ARG. Results do not depend on it, bit for bit (tests/test_gpu_claimed_runs.py). */
+SGX_API int sgx_set_run_claim(sgx_ctx *ctx, uint32_t static_sixteenths, uint32_t chunk_jobs);
+/* the split a float or half rows call of n_frames frames would run under now: (16, 0) where that is the static one */
+SGX_API int sgx_run_claim(const sgx_ctx *ctx, size_t n_frames, uint32_t *static_sixteenths, uint32_t *chunk_jobs);
+
 /* ---- the transform: replaces AudioTransform::process / AudioStreamTransform::process ----- */
 
 /* Batched FastFourierTransform::process (fft.rs:43-99) driven by the hop loop

@@ -178,6 +178,8 @@ struct sgx_ctx {
     // device limits, read once at sgx_create (not on the per-tick latency path)
     int n_cu = 256;          // the count in force: every persistent grid and job split follows it (sgx_set_cu_limit; default n_cu_device)
     int n_cu_device = 256;   // hipDeviceAttributeMultiprocessorCount
+    // sgx_set_run_claim: how the rows launches of the real-input 4096-point kernel deal their jobs (run_claim.hpp).  (0, 0): the automatic rule
+    uint32_t claim_sixteenths = 0, claim_chunk = 0;
     size_t lds_optin = 64 * 1024;   // hipDeviceAttributeSharedMemPerBlockOptin: the largest LDS image a workgroup may ask for
     // resident workgroups per CU of a kernel instantiation at a block size and LDS image (hipOccupancyMaxActiveBlocksPerMultiprocessor, cached)
     mutable std::vector<std::pair<std::array<size_t, 3>, int>> occupancy_cache;

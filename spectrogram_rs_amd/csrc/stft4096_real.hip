@@ -38,6 +38,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "run_claim.hpp"
 #include "stft4096_wg.hpp"
 
 namespace sgx {
@@ -153,6 +154,15 @@ __device__ __forceinline__ float lane_xor8(float v) { return __int_as_float(__bu
 #if SGX_STAMPS
 // diagnostic build only (tools/k1r_phases.py): per-phase wave cycles (s_memtime), summed over all waves and iterations; SGX_STAMP: sgx_internal.hpp
 __device__ unsigned long long g_phase_cycles_r[24];
+// tools/k1r_finish.py: per workgroup {wall clock at entry, at exit, block index, jobs done}, plain stores of thread 0.  The wall clock is the
+// constant-rate counter all CUs share (the cycle counter of the phase stamps is per CU and not comparable between them).
+// -DSGX_STAMPS=2 keeps these and compiles the phase stamps away, so that the iteration is the product's.
+constexpr int kFinishBlocks = 4096;
+__device__ unsigned long long g_finish_r[4 * kFinishBlocks];
+#if SGX_STAMPS == 2
+#undef SGX_STAMP
+#define SGX_STAMP(i)
+#endif
 #endif
 
 template <int MODE, int PIX, bool SLIDE>
@@ -168,6 +178,9 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     constexpr bool FUSED = MODE == kPixels || MODE == kBands || MODE == kPeak || MODE == kFbank;  // the column goes through LDS to the pixel passes (kFbank: to the filter pass)
 
     const int tid = threadIdx.x;
+#if SGX_STAMPS
+    if (tid == 0 && blockIdx.x < kFinishBlocks) g_finish_r[4 * blockIdx.x] = wall_clock64();
+#endif
     const int t_p1 = TR ? (tid >> 4) + 16 * (tid & 15) : tid;     // pass-1 column of this thread
     float *plane = reinterpret_cast<float *>(smem_raw);
     const uint32_t m0_wave = __builtin_amdgcn_readfirstlane((uint32_t)(tid >> 6) * 272u);   // TR: byte offset of this wave inside a plane row (64 + 4 words per wave)
@@ -204,13 +217,24 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     const int cbase2 = (g2 >> 3) * 128 + (g2 & 7); // its image-2 column is cbase2 + 8 q2
     __syncthreads();
 
-    const unsigned long long job_begin = (unsigned long long)blockIdx.x * p.jobs_per_block;
+    // The rows launches run their jobs in RUNS: the static one, [blockIdx.x * jobs_per_block, + jobs_per_block), and then -- where the launch
+    // carries a claim counter (run_claim.hpp) -- chunks of the pool until a claim index falls past it.  The workgroups of this launch do not
+    // run at one speed (profiles/k1r_claimed_tail.txt), and with static runs alone the launch waits for the slowest.  The fused modes and
+    // the sensitivity build keep the static split (kPeak's run alignment is built on it).
+#ifdef SGX_VARIANT_SKIP_LAST_JOB
+    constexpr bool CLAIM = false;
+#else
+    constexpr bool CLAIM = !FUSED;
+#endif
+    const bool claiming = CLAIM && p.claim_counter != nullptr;
+    unsigned long long *claim_word = reinterpret_cast<unsigned long long *>(tw2 + 256);   // LDS, behind the tables: the claim of the run after this one
+    unsigned long long job_begin = (unsigned long long)blockIdx.x * p.jobs_per_block;
     unsigned long long job_end = job_begin + p.jobs_per_block;
     if (job_end > p.n_jobs) job_end = p.n_jobs;
 #ifdef SGX_VARIANT_SKIP_LAST_JOB   // the sensitivity build of tests/test_gpu_cu_counts.py: a run of more than one job omits its last (omits work only)
     if (job_end > job_begin + 1) --job_end;
 #endif
-    if (job_begin >= job_end) return;
+    if (job_begin >= job_end && !claiming) return;
 
     // Columns from `col0` of the stream on, as a raw buffer (uniform base + one 32-bit lane offset); its record count is what the
     // stream still holds from there, so a column past the end reads as zero: a pair's second frame that the stream does not hold, or
@@ -236,330 +260,364 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
 #pragma unroll
         for (int a = 0; a < 4; ++a) { R[2 * a] = column(r0, 2048 * a); R[2 * a + 1] = column(r1, 2048 * a); }
     };
-    {
-        const __amdgpu_buffer_rsrc_t r0 = columns_from(128 * (p.first_frame + 2 * job_begin));
-        if (SLIDE) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) R[j] = column(r0, 1024 * j);
-            L = column(r0, 9216);         // c[128 fa + 1152 + tid]
-        } else {
-            load_pair(p.first_frame + 2 * job_begin);
-            L = R[7];
-        }
-        // the window is waited for HERE (an empty asm that reads it), so that the loop header carries no pending load of the entry path:
-        // merged with the back edge -- where the same registers are long complete -- it made the compiler wait at the top of EVERY
-        // iteration with vmcnt(2), i.e. for the sixteen row stores just issued to be acknowledged by memory
-#pragma unroll
-        for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(R[j].x), "v"(R[j].y));
-        asm volatile("" ::"v"(L.x), "v"(L.y));
-        // (the resident constants too: the compiler schedules their loads BEHIND the window's, and a constant still pending at the
-        // loop entry became a vmcnt(10) .. vmcnt(5) at its first use inside the loop -- in every iteration)
-#pragma unroll
-        for (int q = 1; q < 8; ++q) asm volatile("" ::"v"(tw1[q].x), "v"(tw1[q].y));
-#pragma unroll
-        for (int q = 0; q < 8; ++q) asm volatile("" ::"v"(twu[q].x), "v"(twu[q].y), "v"(win[q]));
-        // (L as well: in flight at the loop entry it made the wait at its first use -- the exchange write, two thirds into the
-        // iteration -- a vmcnt(1): all sixteen row stores of the PREVIOUS iteration acknowledged.  Every later L is complete before the
-        // back edge: the copy from Ln behind the stores waits for it with vmcnt(16), the stores still in flight.)
-    }
     float2 *xch = buf + 2304;         // [256] the iteration's loads, beside the partner rows (image 2 is dead by then)
-
     char *out = reinterpret_cast<char *>(p.mags);
     constexpr int kBin = C64 ? 16 : (F16 ? 4 : 8);   // bytes per output bin
 #if SGX_STAMPS
     unsigned long long st_acc[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long st_last = __builtin_readcyclecounter();
+    unsigned long long jobs_done = 0;
 #endif
-    for (unsigned long long job = job_begin; job < job_end; ++job) {
-        SGX_STAMP(19)
-        const unsigned long long fa = p.first_frame + 2 * job;             // frame A; B = fa + 1
-        const unsigned long long la = 2 * job, lb = la + 1;                // their rows in the output
-        const bool have_b = lb < p.n_frames;                                // (a B outside the range is computed and dropped)
+    for (;;) {   // the runs of this workgroup
+        {
+            const __amdgpu_buffer_rsrc_t r0 = columns_from(128 * (p.first_frame + 2 * job_begin));
+            if (SLIDE) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) R[j] = column(r0, 1024 * j);
+                L = column(r0, 9216);         // c[128 fa + 1152 + tid]
+            } else {
+                load_pair(p.first_frame + 2 * job_begin);
+                L = R[7];
+            }
+            // The claim of the NEXT run is requested here, behind the requests for this run's window and in front of the wait for them: the two
+            // round trips overlap, and thread 0 parks the index in LDS, where the end of the run finds it behind a barrier.  Requested at
+            // the end of the run instead, the whole workgroup would wait for a round trip to L2 behind its own row stores.
+            // One returning add, relaxed, agent scope (a workgroup reads nothing another one writes); request and wait in ONE statement:
+            // the compiler's own atomic waits for the result where it is issued -- it reduces over the wave first -- with the window
+            // still unrequested, and a request of our own whose wait came later would leave it a register it believes complete.
+            if (claiming && tid == 0) {
+                unsigned long long claimed;
+                asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0\n\t"
+                             "s_waitcnt vmcnt(0)"
+                             : "=&v"(claimed)
+                             : "v"(p.claim_counter), "v"(1ull)
+                             : "memory");
+                *claim_word = claimed;
+            }
+            // the window is waited for HERE (an empty asm that reads it), so that the loop header carries no pending load of the entry path:
+            // merged with the back edge -- where the same registers are long complete -- it made the compiler wait at the top of EVERY
+            // iteration with vmcnt(2), i.e. for the sixteen row stores just issued to be acknowledged by memory
+#pragma unroll
+            for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(R[j].x), "v"(R[j].y));
+            asm volatile("" ::"v"(L.x), "v"(L.y));
+            // (the resident constants too: the compiler schedules their loads BEHIND the window's, and a constant still pending at the
+            // loop entry became a vmcnt(10) .. vmcnt(5) at its first use inside the loop -- in every iteration)
+#pragma unroll
+            for (int q = 1; q < 8; ++q) asm volatile("" ::"v"(tw1[q].x), "v"(tw1[q].y));
+#pragma unroll
+            for (int q = 0; q < 8; ++q) asm volatile("" ::"v"(twu[q].x), "v"(twu[q].y), "v"(win[q]));
+            // (L as well: in flight at the loop entry it made the wait at its first use -- the exchange write, two thirds into the
+            // iteration -- a vmcnt(1): all sixteen row stores of the PREVIOUS iteration acknowledged.  Every later L is complete before the
+            // back edge: the copy from Ln behind the stores waits for it with vmcnt(16), the stores still in flight.)
+        }
+        for (unsigned long long job = job_begin; job < job_end; ++job) {
+            SGX_STAMP(19)
+            const unsigned long long fa = p.first_frame + 2 * job;             // frame A; B = fa + 1
+            const unsigned long long la = 2 * job, lb = la + 1;                // their rows in the output
+            const bool have_b = lb < p.n_frames;                                // (a B outside the range is computed and dropped)
 
-        // ---- Hann (fft.rs:53-63) and pass 1 for both frames
-        float yr[8], yi[8];
-        {
-            float zr[4], zi[4];
+            // ---- Hann (fft.rs:53-63) and pass 1 for both frames
+            float yr[8], yi[8];
+            {
+                float zr[4], zi[4];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) { zr[a] = R[2 * a].x * win[2 * a]; zi[a] = R[2 * a].y * win[2 * a + 1]; }
-            fft8_half_zero(zr, zi, yr, yi);
-        }
-        float vr[8], vi[8];
-        {
-            float zr[4], zi[4];
+                for (int a = 0; a < 4; ++a) { zr[a] = R[2 * a].x * win[2 * a]; zi[a] = R[2 * a].y * win[2 * a + 1]; }
+                fft8_half_zero(zr, zi, yr, yi);
+            }
+            float vr[8], vi[8];
+            {
+                float zr[4], zi[4];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) { zr[a] = R[2 * a + 1].x * win[2 * a]; zi[a] = R[2 * a + 1].y * win[2 * a + 1]; }
-            fft8_half_zero(zr, zi, vr, vi);
-        }
-        SGX_STAMP(0)    // Hann + pass 1 (two frames)
-        lds_barrier();  // the previous iteration's partner reads are complete
-        SGX_STAMP(1)    // barrier 0
+                for (int a = 0; a < 4; ++a) { zr[a] = R[2 * a + 1].x * win[2 * a]; zi[a] = R[2 * a + 1].y * win[2 * a + 1]; }
+                fft8_half_zero(zr, zi, vr, vi);
+            }
+            SGX_STAMP(0)    // Hann + pass 1 (two frames)
+            lds_barrier();  // the previous iteration's partner reads are complete
+            SGX_STAMP(1)    // barrier 0
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const float2 ya = make_float2(yr[q], yi[q]), yb = make_float2(vr[q], vi[q]);
+            for (int q = 0; q < 8; ++q) {
+                const float2 ya = make_float2(yr[q], yi[q]), yb = make_float2(vr[q], vi[q]);
+                if (TR) {
+                    addtid_rows<272>(q == 0 ? ya : cmulf(ya, tw1[q]), q == 0 ? yb : cmulf(yb, tw1[q]), m0_wave, q, 8 + q);
+                } else {
+                    buf[q * kS1 + tid] = q == 0 ? ya : cmulf(ya, tw1[q]);
+                    buf[(8 + q) * kS1 + tid] = q == 0 ? yb : cmulf(yb, tw1[q]);
+                }
+            }
+            __builtin_amdgcn_s_setprio(0);  // (wave priorities: stft4096_wg.hip)
+            SGX_STAMP(2)    // twiddles + image-1 writes
+            lds_barrier();
+            SGX_STAMP(3)    // barrier 1
+
+            // ---- pass 2: thread (g2 = 8 F + q1, t0): 16-point FFT over t1, then twiddle w_256^{t0 q2}
+            float xr[16], xi[16];
             if (TR) {
-                addtid_rows<272>(q == 0 ? ya : cmulf(ya, tw1[q]), q == 0 ? yb : cmulf(yb, tw1[q]), m0_wave, q, 8 + q);
+                read_planes(rd4_1, xr, xi);
             } else {
-                buf[q * kS1 + tid] = q == 0 ? ya : cmulf(ya, tw1[q]);
-                buf[(8 + q) * kS1 + tid] = q == 0 ? yb : cmulf(yb, tw1[q]);
+#pragma unroll
+                for (int t1 = 0; t1 < 16; ++t1) {
+                    const float2 v = buf[g2 * kS1 + t0_2 + 16 * t1];
+                    xr[t1] = v.x; xi[t1] = v.y;
+                }
             }
-        }
-        __builtin_amdgcn_s_setprio(0);  // (wave priorities: stft4096_wg.hip)
-        SGX_STAMP(2)    // twiddles + image-1 writes
-        lds_barrier();
-        SGX_STAMP(3)    // barrier 1
-
-        // ---- pass 2: thread (g2 = 8 F + q1, t0): 16-point FFT over t1, then twiddle w_256^{t0 q2}
-        float xr[16], xi[16];
-        if (TR) {
-            read_planes(rd4_1, xr, xi);
-        } else {
+            fft16(xr, xi);
+            SGX_STAMP(4)    // image-1 reads + FFT16
+            lds_barrier();  // everyone has read image 1
+            SGX_STAMP(5)    // barrier 2
+            if (TR) {
+                lds_cfloat2 *tw2p = lds_ptr(tw2 + t0_2);
 #pragma unroll
-            for (int t1 = 0; t1 < 16; ++t1) {
-                const float2 v = buf[g2 * kS1 + t0_2 + 16 * t1];
-                xr[t1] = v.x; xi[t1] = v.y;
-            }
-        }
-        fft16(xr, xi);
-        SGX_STAMP(4)    // image-1 reads + FFT16
-        lds_barrier();  // everyone has read image 1
-        SGX_STAMP(5)    // barrier 2
-        if (TR) {
-            lds_cfloat2 *tw2p = lds_ptr(tw2 + t0_2);
-#pragma unroll
-            for (int q2 = 0; q2 < 16; q2 += 2) {
-                const int pa = FFT16_OUT[q2], pb = FFT16_OUT[q2 + 1];
-                const float2 va = make_float2(xr[pa], xi[pa]), vb = make_float2(xr[pb], xi[pb]);
-                addtid_rows<280>(q2 == 0 ? va : cmulf(va, lds_read_alone(tw2p, q2 * 16)), cmulf(vb, lds_read_alone(tw2p, (q2 + 1) * 16)), m0_wave, q2, q2 + 1);
-            }
-        } else {
-#pragma unroll
-            for (int q2 = 0; q2 < 16; ++q2) {
-                const int pos = FFT16_OUT[q2];
-                const float2 v = make_float2(xr[pos], xi[pos]);
-                buf[t0_2 * kS2 + cbase2 + 8 * q2] = q2 == 0 ? v : cmulf(v, tw2[q2 * 16 + t0_2]);
-            }
-        }
-        SGX_STAMP(6)    // pass-2 twiddles + image-2 writes
-        lds_barrier();
-        SGX_STAMP(7)    // barrier 3
-
-        // ---- pass 3: thread (F, u): 16-point FFT over t0 -> Z[u + 128 q3]
-        if (TR) {
-            read_planes(rd4_2, xr, xi);
-        } else {
-#pragma unroll
-            for (int t0 = 0; t0 < 16; ++t0) {
-                const float2 v = buf[t0 * kS2 + tid];
-                xr[t0] = v.x; xi[t0] = v.y;
-            }
-        }
-        fft16(xr, xi);
-
-        // ---- rows: the load of the NEXT iteration (its R[9]), ahead of this iteration's stores (vmcnt retires in issue order), into a
-        // second register pair -- L is still needed for the exchange.  Unconditional (a conditional request keeps the old value alive
-        // around the loop); past the end of the stream it reads zeros.  (Requested at the TOP of the iteration instead -- a whole
-        // iteration to return in -- it sits right behind the previous iteration's sixteen stores: 5-7 % slower, same device.)
-        float2 Ln = make_float2(0.0f, 0.0f);
-        if (SLIDE && !FUSED) Ln = column(columns_from(128 * (fa + 2) + 1152), 0);
-        if (!SLIDE) load_pair(fa + 2);     // (R is dead since pass 1; past the end of the stream: zeros, never stored)
-
-        if (FUSED) __builtin_amdgcn_s_setprio(1);   // the pixel passes are long: 3 only from the row pass (the pixel stores) on
-        else __builtin_amdgcn_s_setprio(3);
-        SGX_STAMP(8)    // image-2 reads + FFT16 + next column requested
-        lds_barrier();  // everyone has read image 2
-        SGX_STAMP(9)    // barrier 4
-        // partner exchange: publish q3 = 8..15
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int pos = FFT16_OUT[8 + j];
-            buf[j * 256 + tid] = make_float2(xr[pos], xi[pos]);
-        }
-        // the next R[6] = c[128 fa + 1024 + tid] of the thread half a row away: its L (lower half publishes) or its R[7] (upper half)
-        if (SLIDE && !TR) {
-            xch[tid].x = tid < 128 ? L.x : R[7].x;
-            xch[tid].y = tid < 128 ? L.y : R[7].y;
-        }
-        SGX_STAMP(10)   // partner + window-exchange writes
-        lds_barrier();
-        SGX_STAMP(11)   // barrier 5
-        if (SLIDE) {
-            // (TR: column t + 128 is lane ^ 8 of the same wave -- no trip through LDS)
-            const float2 Y = TR ? make_float2(lane_xor8((tid & 8) ? R[7].x : L.x), lane_xor8((tid & 8) ? R[7].y : L.y)) : xch[(tid + 128) & 255];
-            // ---- slide the window by two half rows, here: L is dead from now on (the Hann products of this iteration were taken at its top)
-#pragma unroll
-            for (int j = 0; j < 6; ++j) R[j] = R[j + 2];
-            R[6] = Y;
-            R[7] = L;
-        }
-
-        // ---- untangle + magnitude: bins k = u + 128 q3 and 2048 - k.  Z[2048 - k] is register 15 - q3 of thread 128 - u (row 7 - q3);
-        // thread 0 holds its own partners one row up (register 16 - q3), and spends its q3 = 0 slot -- DC and Nyquist are not outputs
-        // (fft.rs:81) -- on the self-paired bin 1024: Z = P = its register 8, twiddle -i (twu[0][0])
-        const int pcol = F * 128 + (u == 0 ? 256 : 128 - u);
-        float m1[8], m2[8];
-        // rows: every bin pair is stored as soon as it is computed (stft4096_wg.hip does the same for (l, r) rows):
-        // sixteen stores spread over the untangle instead of one burst behind it
-        constexpr bool kInterleave = (!FUSED && SLIDE) || C64;   // (C64: at any hop -- four arrays of eight would stay live otherwise)   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
-        const long long row = (long long)(F == 0 ? la : lb) * (long long)kM * kBin - kBin;      // byte of the (absent) bin 0
-        const __amdgpu_buffer_rsrc_t r = out_rsrc(out, !FUSED ? row : 0, !FUSED && (F == 0 || have_b));
-        const int l1 = kBin * u, l2 = kBin * (1152 - u);                                        // bins u + 128 q3 ; 2048 - u - 128 q3 = (1152 - u) + 128 (7 - q3)
-        auto store_pair = [&](const int q3) {
-            // bin k at byte kBin (k - 1).  Thread 0's q3 = 0 slot: bin 1024 from m1, and a second copy of it where its m2 would go.
-            const float a = m1[q3], b = (q3 == 0 && u == 0) ? m1[0] : m2[q3];
-            const int o1 = (q3 == 0 && u == 0) ? kBin * 1024 : l1;
-            const int o2 = (q3 == 0 && u == 0) ? kBin * 128 : l2;                               // 128 + 128 * 7 = 1024
-            const int s1 = kBin * 128 * q3, s2 = kBin * 128 * (7 - q3);
-            if (F16) {
-                const __half2 ha = __floats2half2_rn(a, a), hb = __floats2half2_rn(b, b);
-                __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t *>(&ha), r, o1 + (s1 & 2047), s1 & ~2047, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t *>(&hb), r, o2 + (s2 & 2047), s2 & ~2047, 0);
+                for (int q2 = 0; q2 < 16; q2 += 2) {
+                    const int pa = FFT16_OUT[q2], pb = FFT16_OUT[q2 + 1];
+                    const float2 va = make_float2(xr[pa], xi[pa]), vb = make_float2(xr[pb], xi[pb]);
+                    addtid_rows<280>(q2 == 0 ? va : cmulf(va, lds_read_alone(tw2p, q2 * 16)), cmulf(vb, lds_read_alone(tw2p, (q2 + 1) * 16)), m0_wave, q2, q2 + 1);
+                }
             } else {
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(a), __float_as_uint(a)}, r, o1 + (s1 & 2047), s1 & ~2047, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(b), __float_as_uint(b)}, r, o2 + (s2 & 2047), s2 & ~2047, 0);
-            }
-        };
-        float2 pvs[8];
-        if (kInterleave) {
 #pragma unroll
-            for (int q3 = 0; q3 < 8; ++q3) pvs[q3] = buf[(7 - q3) * 256 + pcol];
-        }
-#pragma unroll
-        for (int q3 = 0; q3 < 8; ++q3) {
-            const int pos = FFT16_OUT[q3];
-            float zr_ = xr[pos], zi_ = xi[pos];
-            float2 pv = kInterleave ? pvs[q3] : buf[(7 - q3) * 256 + pcol];
-            if (q3 == 0) {
-                const float2 own = buf[F * 128];              // thread 0 of the frame: its register 8 as published
-                const int p8 = FFT16_OUT[8];
-                zr_ = u == 0 ? xr[p8] : zr_; zi_ = u == 0 ? xi[p8] : zi_;
-                pv.x = u == 0 ? own.x : pv.x; pv.y = u == 0 ? own.y : pv.y;
+                for (int q2 = 0; q2 < 16; ++q2) {
+                    const int pos = FFT16_OUT[q2];
+                    const float2 v = make_float2(xr[pos], xi[pos]);
+                    buf[t0_2 * kS2 + cbase2 + 8 * q2] = q2 == 0 ? v : cmulf(v, tw2[q2 * 16 + t0_2]);
+                }
             }
-            const float er = zr_ + pv.x, ei = zi_ - pv.y;    // Z + conj P   = 2 E
-            const float orr = zi_ + pv.y, oi = pv.x - zr_;    // -i (Z - conj P) = 2 O
-            const float wr = fmaf(twu[q3].x, orr, -(twu[q3].y * oi)), wi = fmaf(twu[q3].x, oi, twu[q3].y * orr);
-            const float ar = er + wr, ai = ei + wi, br = er - wr, bi = ei - wi;
-            if constexpr (C64) {
-                // S[k] = (ar, ai) and S[2048 - k] = conj(br + i bi), both already times 2 / W; thread 0's q3 = 0 slot: bin 1024 twice
-                const bool self = q3 == 0 && u == 0;
-                const float cr2 = self ? ar : br, ci2 = self ? ai : -bi;
-                const int o1 = self ? kBin * 1024 : l1, o2 = self ? kBin * 128 : l2;
+            SGX_STAMP(6)    // pass-2 twiddles + image-2 writes
+            lds_barrier();
+            SGX_STAMP(7)    // barrier 3
+
+            // ---- pass 3: thread (F, u): 16-point FFT over t0 -> Z[u + 128 q3]
+            if (TR) {
+                read_planes(rd4_2, xr, xi);
+            } else {
+#pragma unroll
+                for (int t0 = 0; t0 < 16; ++t0) {
+                    const float2 v = buf[t0 * kS2 + tid];
+                    xr[t0] = v.x; xi[t0] = v.y;
+                }
+            }
+            fft16(xr, xi);
+
+            // ---- rows: the load of the NEXT iteration (its R[9]), ahead of this iteration's stores (vmcnt retires in issue order), into a
+            // second register pair -- L is still needed for the exchange.  Unconditional (a conditional request keeps the old value alive
+            // around the loop); past the end of the stream it reads zeros.  (Requested at the TOP of the iteration instead -- a whole
+            // iteration to return in -- it sits right behind the previous iteration's sixteen stores: 5-7 % slower, same device.)
+            float2 Ln = make_float2(0.0f, 0.0f);
+            if (SLIDE && !FUSED) Ln = column(columns_from(128 * (fa + 2) + 1152), 0);
+            if (!SLIDE) load_pair(fa + 2);     // (R is dead since pass 1; past the end of the stream: zeros, never stored)
+
+            if (FUSED) __builtin_amdgcn_s_setprio(1);   // the pixel passes are long: 3 only from the row pass (the pixel stores) on
+            else __builtin_amdgcn_s_setprio(3);
+            SGX_STAMP(8)    // image-2 reads + FFT16 + next column requested
+            lds_barrier();  // everyone has read image 2
+            SGX_STAMP(9)    // barrier 4
+            // partner exchange: publish q3 = 8..15
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int pos = FFT16_OUT[8 + j];
+                buf[j * 256 + tid] = make_float2(xr[pos], xi[pos]);
+            }
+            // the next R[6] = c[128 fa + 1024 + tid] of the thread half a row away: its L (lower half publishes) or its R[7] (upper half)
+            if (SLIDE && !TR) {
+                xch[tid].x = tid < 128 ? L.x : R[7].x;
+                xch[tid].y = tid < 128 ? L.y : R[7].y;
+            }
+            SGX_STAMP(10)   // partner + window-exchange writes
+            lds_barrier();
+            SGX_STAMP(11)   // barrier 5
+            if (SLIDE) {
+                // (TR: column t + 128 is lane ^ 8 of the same wave -- no trip through LDS)
+                const float2 Y = TR ? make_float2(lane_xor8((tid & 8) ? R[7].x : L.x), lane_xor8((tid & 8) ? R[7].y : L.y)) : xch[(tid + 128) & 255];
+                // ---- slide the window by two half rows, here: L is dead from now on (the Hann products of this iteration were taken at its top)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) R[j] = R[j + 2];
+                R[6] = Y;
+                R[7] = L;
+            }
+
+            // ---- untangle + magnitude: bins k = u + 128 q3 and 2048 - k.  Z[2048 - k] is register 15 - q3 of thread 128 - u (row 7 - q3);
+            // thread 0 holds its own partners one row up (register 16 - q3), and spends its q3 = 0 slot -- DC and Nyquist are not outputs
+            // (fft.rs:81) -- on the self-paired bin 1024: Z = P = its register 8, twiddle -i (twu[0][0])
+            const int pcol = F * 128 + (u == 0 ? 256 : 128 - u);
+            float m1[8], m2[8];
+            // rows: every bin pair is stored as soon as it is computed (stft4096_wg.hip does the same for (l, r) rows):
+            // sixteen stores spread over the untangle instead of one burst behind it
+            constexpr bool kInterleave = (!FUSED && SLIDE) || C64;   // (C64: at any hop -- four arrays of eight would stay live otherwise)   // (same device, 1e6 frames: H 256 3.64 / 3.87 / 3.84 -> 3.56 / 3.82 / 3.81 ms; any other hop -- eight column loads in flight around the stores -- 4.02 -> 4.29: the burst stays there)
+            const long long row = (long long)(F == 0 ? la : lb) * (long long)kM * kBin - kBin;      // byte of the (absent) bin 0
+            const __amdgpu_buffer_rsrc_t r = out_rsrc(out, !FUSED ? row : 0, !FUSED && (F == 0 || have_b));
+            const int l1 = kBin * u, l2 = kBin * (1152 - u);                                        // bins u + 128 q3 ; 2048 - u - 128 q3 = (1152 - u) + 128 (7 - q3)
+            auto store_pair = [&](const int q3) {
+                // bin k at byte kBin (k - 1).  Thread 0's q3 = 0 slot: bin 1024 from m1, and a second copy of it where its m2 would go.
+                const float a = m1[q3], b = (q3 == 0 && u == 0) ? m1[0] : m2[q3];
+                const int o1 = (q3 == 0 && u == 0) ? kBin * 1024 : l1;
+                const int o2 = (q3 == 0 && u == 0) ? kBin * 128 : l2;                               // 128 + 128 * 7 = 1024
                 const int s1 = kBin * 128 * q3, s2 = kBin * 128 * (7 - q3);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(ar), __float_as_uint(ai), __float_as_uint(ar), __float_as_uint(ai)}, r, o1 + s1, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cr2), __float_as_uint(ci2), __float_as_uint(cr2), __float_as_uint(ci2)}, r, o2 + s2, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                continue;
-            }
-            m1[q3] = __builtin_amdgcn_sqrtf(fmaf(ar, ar, ai * ai));   // |S[k]| 2 / W      (the scale rides on the window)
-            m2[q3] = __builtin_amdgcn_sqrtf(fmaf(br, br, bi * bi));   // |S[2048 - k]| 2 / W
+                if (F16) {
+                    const __half2 ha = __floats2half2_rn(a, a), hb = __floats2half2_rn(b, b);
+                    __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t *>(&ha), r, o1 + (s1 & 2047), s1 & ~2047, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t *>(&hb), r, o2 + (s2 & 2047), s2 & ~2047, 0);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(a), __float_as_uint(a)}, r, o1 + (s1 & 2047), s1 & ~2047, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(b), __float_as_uint(b)}, r, o2 + (s2 & 2047), s2 & ~2047, 0);
+                }
+            };
+            float2 pvs[8];
             if (kInterleave) {
-                store_pair(q3);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-
-        // ---- store row [M][2] (or half pairs): straight-line code: the wait for the prefetched rows below is then vmcnt(stores issued since)
-        if (!FUSED) {
-            if (!kInterleave) {
 #pragma unroll
-                for (int q3 = 0; q3 < 8; ++q3) store_pair(q3);
+                for (int q3 = 0; q3 < 8; ++q3) pvs[q3] = buf[(7 - q3) * 256 + pcol];
             }
-        } else {
-            // ---- fused pixel columns (simple_spectrogram.rs:141-161): the pair's magnitudes go to LDS as float2 per bin -- (frame A,
-            // frame B), each half written by its own frame's threads -- and K1's two pixel passes render both columns
-            float2 *mpair = buf;                           // the padded column [bin] (wg::kColSlots)
-            float2 *vbuf = mpair + wg::kColSlots;          // [sample slot]
-            float *mcol = reinterpret_cast<float *>(buf) + F;
-            lds_barrier();  // partner and exchange reads done: the image can be overwritten
-            SGX_STAMP(13)   // (pixels) barrier 6
-            // the sample pass's table words (nine per thread, the same in every iteration but eighteen registers nobody has to spare across
-            // the transform) are requested as the column writes free m1 / m2, one word behind each pair of writes: their L1 / L2 latency
-            // falls on the rest of the writes and on the barrier instead of on the head of the pass
-            constexpr bool kEarlyWords = PIX != wg::kPixGeneric && MODE != kFbank;   // (the generic instantiation -- interpolator and LUT walk at run time -- has no register left: one spill)
-            wg::SampleWords sw;
-            const __amdgpu_buffer_rsrc_t rt_words = wg::pcm_rsrc(reinterpret_cast<const float *>(p.samples));
-            int tid_w = tid;
-            asm volatile("" : "+v"(tid_w));   // (opaque: the nine table offsets are not to be hoisted out of the loop over the transforms)
 #pragma unroll
             for (int q3 = 0; q3 < 8; ++q3) {
-                const bool self = q3 == 0 && u == 0;       // thread 0's bin-1024 slot: m1 twice
-                const int k1 = self ? 1024 : u + 128 * q3, k2 = self ? 1024 : 2048 - u - 128 * q3;
-                mcol[2 * k1] = m1[q3];
-                mcol[2 * k2] = self ? m1[0] : m2[q3];
-                if (q3 == 0 && u == 1) {                   // this thread holds bin 1 (m1[0]) and bin 2047 (m2[0]): the repeats around the column
-                    mcol[0] = m1[0];
-                    mcol[2 * (kM + 1)] = mcol[2 * (kM + 2)] = m2[0];
+                const int pos = FFT16_OUT[q3];
+                float zr_ = xr[pos], zi_ = xi[pos];
+                float2 pv = kInterleave ? pvs[q3] : buf[(7 - q3) * 256 + pcol];
+                if (q3 == 0) {
+                    const float2 own = buf[F * 128];              // thread 0 of the frame: its register 8 as published
+                    const int p8 = FFT16_OUT[8];
+                    zr_ = u == 0 ? xr[p8] : zr_; zi_ = u == 0 ? xi[p8] : zi_;
+                    pv.x = u == 0 ? own.x : pv.x; pv.y = u == 0 ? own.y : pv.y;
                 }
-                if (kEarlyWords) {
-                    sw.se[q3] = wg::sample_word(rt_words, p, (uint32_t)tid_w + 256u * q3);
+                const float er = zr_ + pv.x, ei = zi_ - pv.y;    // Z + conj P   = 2 E
+                const float orr = zi_ + pv.y, oi = pv.x - zr_;    // -i (Z - conj P) = 2 O
+                const float wr = fmaf(twu[q3].x, orr, -(twu[q3].y * oi)), wi = fmaf(twu[q3].x, oi, twu[q3].y * orr);
+                const float ar = er + wr, ai = ei + wi, br = er - wr, bi = ei - wi;
+                if constexpr (C64) {
+                    // S[k] = (ar, ai) and S[2048 - k] = conj(br + i bi), both already times 2 / W; thread 0's q3 = 0 slot: bin 1024 twice
+                    const bool self = q3 == 0 && u == 0;
+                    const float cr2 = self ? ar : br, ci2 = self ? ai : -bi;
+                    const int o1 = self ? kBin * 1024 : l1, o2 = self ? kBin * 128 : l2;
+                    const int s1 = kBin * 128 * q3, s2 = kBin * 128 * (7 - q3);
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(ar), __float_as_uint(ai), __float_as_uint(ar), __float_as_uint(ai)}, r, o1 + s1, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cr2), __float_as_uint(ci2), __float_as_uint(cr2), __float_as_uint(ci2)}, r, o2 + s2, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    continue;
+                }
+                m1[q3] = __builtin_amdgcn_sqrtf(fmaf(ar, ar, ai * ai));   // |S[k]| 2 / W      (the scale rides on the window)
+                m2[q3] = __builtin_amdgcn_sqrtf(fmaf(br, br, bi * bi));   // |S[2048 - k]| 2 / W
+                if (kInterleave) {
+                    store_pair(q3);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if (kEarlyWords) sw.se[8] = wg::sample_word(rt_words, p, (uint32_t)tid_w + 2048u);
-            static_assert(wg::kSampleSteps == 9 && wg::kSampleEarly == 9, "one word per column-write step and one behind them");
-            SGX_STAMP(14)   // (pixels) column writes
-            lds_barrier();
-            SGX_STAMP(15)   // (pixels) barrier 7
-            if constexpr (MODE == kFbank) {
-                // one filter pass over the pair's column (frame A in .x, frame B in .y), a wave per filter: element j of a row is bin j + 1
-                float2 *sums = reinterpret_cast<float2 *>(p.rgba);
-                __builtin_amdgcn_s_setprio(3);
-                fbank::filter_pass<true>(mpair + 1, reinterpret_cast<const fbank::Filter *>(p.rows), reinterpret_cast<const float *>(p.samples), p.R,
-                                         p.interp == 2u, sums + la * (size_t)p.R, sums + lb * (size_t)p.R, true, have_b, (uint32_t)tid, 4u);
-                // the next iteration's load behind the pass, straight into L (dead since the slide): requested in front of it, it is two
-                // more registers alive through the pass and two spills
+
+            // ---- store row [M][2] (or half pairs): straight-line code: the wait for the prefetched rows below is then vmcnt(stores issued since)
+            if (!FUSED) {
+                if (!kInterleave) {
+#pragma unroll
+                    for (int q3 = 0; q3 < 8; ++q3) store_pair(q3);
+                }
+            } else {
+                // ---- fused pixel columns (simple_spectrogram.rs:141-161): the pair's magnitudes go to LDS as float2 per bin -- (frame A,
+                // frame B), each half written by its own frame's threads -- and K1's two pixel passes render both columns
+                float2 *mpair = buf;                           // the padded column [bin] (wg::kColSlots)
+                float2 *vbuf = mpair + wg::kColSlots;          // [sample slot]
+                float *mcol = reinterpret_cast<float *>(buf) + F;
+                lds_barrier();  // partner and exchange reads done: the image can be overwritten
+                SGX_STAMP(13)   // (pixels) barrier 6
+                // the sample pass's table words (nine per thread, the same in every iteration but eighteen registers nobody has to spare across
+                // the transform) are requested as the column writes free m1 / m2, one word behind each pair of writes: their L1 / L2 latency
+                // falls on the rest of the writes and on the barrier instead of on the head of the pass
+                constexpr bool kEarlyWords = PIX != wg::kPixGeneric && MODE != kFbank;   // (the generic instantiation -- interpolator and LUT walk at run time -- has no register left: one spill)
+                wg::SampleWords sw;
+                const __amdgpu_buffer_rsrc_t rt_words = wg::pcm_rsrc(reinterpret_cast<const float *>(p.samples));
+                int tid_w = tid;
+                asm volatile("" : "+v"(tid_w));   // (opaque: the nine table offsets are not to be hoisted out of the loop over the transforms)
+#pragma unroll
+                for (int q3 = 0; q3 < 8; ++q3) {
+                    const bool self = q3 == 0 && u == 0;       // thread 0's bin-1024 slot: m1 twice
+                    const int k1 = self ? 1024 : u + 128 * q3, k2 = self ? 1024 : 2048 - u - 128 * q3;
+                    mcol[2 * k1] = m1[q3];
+                    mcol[2 * k2] = self ? m1[0] : m2[q3];
+                    if (q3 == 0 && u == 1) {                   // this thread holds bin 1 (m1[0]) and bin 2047 (m2[0]): the repeats around the column
+                        mcol[0] = m1[0];
+                        mcol[2 * (kM + 1)] = mcol[2 * (kM + 2)] = m2[0];
+                    }
+                    if (kEarlyWords) {
+                        sw.se[q3] = wg::sample_word(rt_words, p, (uint32_t)tid_w + 256u * q3);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if (kEarlyWords) sw.se[8] = wg::sample_word(rt_words, p, (uint32_t)tid_w + 2048u);
+                static_assert(wg::kSampleSteps == 9 && wg::kSampleEarly == 9, "one word per column-write step and one behind them");
+                SGX_STAMP(14)   // (pixels) column writes
+                lds_barrier();
+                SGX_STAMP(15)   // (pixels) barrier 7
+                if constexpr (MODE == kFbank) {
+                    // one filter pass over the pair's column (frame A in .x, frame B in .y), a wave per filter: element j of a row is bin j + 1
+                    float2 *sums = reinterpret_cast<float2 *>(p.rgba);
+                    __builtin_amdgcn_s_setprio(3);
+                    fbank::filter_pass<true>(mpair + 1, reinterpret_cast<const fbank::Filter *>(p.rows), reinterpret_cast<const float *>(p.samples), p.R,
+                                             p.interp == 2u, sums + la * (size_t)p.R, sums + lb * (size_t)p.R, true, have_b, (uint32_t)tid, 4u);
+                    // the next iteration's load behind the pass, straight into L (dead since the slide): requested in front of it, it is two
+                    // more registers alive through the pass and two spills
+                    if (SLIDE) L = column(columns_from(128 * (fa + 2) + 1152), 0);
+                } else {
+                if (kEarlyWords) wg::sample_pass_with<PIX>(p, mpair, vbuf, tid, sw);
+                else wg::sample_pass<PIX>(p, mpair, vbuf, tid);
+                // the fused pixel path requests the next iteration's load HERE, straight into L (dead since the slide): requested in front
+                // of the exchange like the rows' it is two more live registers through the sample pass -- two spills, and a spill reload
+                // is a vector-memory load the compiler waits for with vmcnt(0), this load included (same device: 3.79 -> 3.68 ms)
+                [[maybe_unused]] wg::PeakDst peak_a{}, peak_b{};
+                [[maybe_unused]] wg::PeakOld<true> peak_old{};
+                if constexpr (MODE == kPeak) {
+                    // the column's rows as they are, requested in front of the barrier -- and in front of the next transform's load, which comes
+                    // from HBM: the counter retires in order, and behind that load the row pass would wait for it too
+                    peak_a = wg::peak_dst(p, la);
+                    peak_b = have_b ? wg::peak_dst_next(p, peak_a, lb) : peak_a;
+                    peak_old = wg::peak_prefetch<true>(p, peak_a, tid);
+                }
                 if (SLIDE) L = column(columns_from(128 * (fa + 2) + 1152), 0);
-            } else {
-            if (kEarlyWords) wg::sample_pass_with<PIX>(p, mpair, vbuf, tid, sw);
-            else wg::sample_pass<PIX>(p, mpair, vbuf, tid);
-            // the fused pixel path requests the next iteration's load HERE, straight into L (dead since the slide): requested in front
-            // of the exchange like the rows' it is two more live registers through the sample pass -- two spills, and a spill reload
-            // is a vector-memory load the compiler waits for with vmcnt(0), this load included (same device: 3.79 -> 3.68 ms)
-            [[maybe_unused]] wg::PeakDst peak_a{}, peak_b{};
-            [[maybe_unused]] wg::PeakOld<true> peak_old{};
-            if constexpr (MODE == kPeak) {
-                // the column's rows as they are, requested in front of the barrier -- and in front of the next transform's load, which comes
-                // from HBM: the counter retires in order, and behind that load the row pass would wait for it too
-                peak_a = wg::peak_dst(p, la);
-                peak_b = have_b ? wg::peak_dst_next(p, peak_a, lb) : peak_a;
-                peak_old = wg::peak_prefetch<true>(p, peak_a, tid);
+                SGX_STAMP(16)   // (pixels) sample pass
+                lds_barrier();
+                SGX_STAMP(17)   // (pixels) barrier 8
+                __builtin_amdgcn_s_setprio(3);
+                if constexpr (MODE == kPeak) {
+                    wg::row_pass_peak<true>(p, row_words, vbuf, peak_a, peak_b, peak_old, have_b, tid);
+                } else if constexpr (MODE == kBands) {
+                    float2 *bands = reinterpret_cast<float2 *>(p.rgba);
+                    wg::row_pass_bands<true>(p, row_words, vbuf, bands + la * (size_t)p.R, bands + lb * (size_t)p.R, true, have_b, tid);
+                } else {
+                    uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
+                    wg::row_pass<true, PIX>(p, row_words, vbuf, rgba + la * (size_t)p.R, rgba + lb * (size_t)p.R, true, have_b, pal, tid);
+                }
+                }
             }
-            if (SLIDE) L = column(columns_from(128 * (fa + 2) + 1152), 0);
-            SGX_STAMP(16)   // (pixels) sample pass
-            lds_barrier();
-            SGX_STAMP(17)   // (pixels) barrier 8
-            __builtin_amdgcn_s_setprio(3);
-            if constexpr (MODE == kPeak) {
-                wg::row_pass_peak<true>(p, row_words, vbuf, peak_a, peak_b, peak_old, have_b, tid);
-            } else if constexpr (MODE == kBands) {
-                float2 *bands = reinterpret_cast<float2 *>(p.rgba);
-                wg::row_pass_bands<true>(p, row_words, vbuf, bands + la * (size_t)p.R, bands + lb * (size_t)p.R, true, have_b, tid);
-            } else {
-                uchar4 *rgba = reinterpret_cast<uchar4 *>(p.rgba);
-                wg::row_pass<true, PIX>(p, row_words, vbuf, rgba + la * (size_t)p.R, rgba + lb * (size_t)p.R, true, have_b, pal, tid);
+            if (SLIDE && !FUSED) {
+                // `Ln` is pinned behind the row stores: its copy into L needs the load complete, and scheduled in front of the stores (where
+                // the compiler had put it) that is a vmcnt(0) in the middle of the iteration; here it is vmcnt(stores since).  (The load
+                // straight into L behind the slide, no second pair: 4 % slower on the same device.)
+                asm volatile("" : "+v"(Ln.x), "+v"(Ln.y));
+                L = Ln;
             }
-            }
+            SGX_STAMP(18)   // rows: 16 stores issued + wait for the next column; pixels: the row pass (sums, dB, LUT, pixel stores)
         }
-        if (SLIDE && !FUSED) {
-            // `Ln` is pinned behind the row stores: its copy into L needs the load complete, and scheduled in front of the stores (where
-            // the compiler had put it) that is a vmcnt(0) in the middle of the iteration; here it is vmcnt(stores since).  (The load
-            // straight into L behind the slide, no second pair: 4 % slower on the same device.)
-            asm volatile("" : "+v"(Ln.x), "+v"(Ln.y));
-            L = Ln;
-        }
-        SGX_STAMP(18)   // rows: 16 stores issued + wait for the next column; pixels: the row pass (sums, dB, LUT, pixel stores)
+#if SGX_STAMPS
+        jobs_done += job_end - job_begin;
+#endif
+        if (!claiming) break;
+        lds_barrier();   // (a run may be empty: no barrier of the loop stands between the write above and this read)
+        const unsigned long long word = *claim_word;
+        const unsigned long long chunk_i = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(word >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)word);
+        lds_barrier();   // everyone has read it: thread 0 may park the next one
+        if (chunk_i >= p.claim_chunks) break;
+        job_begin = p.claim_pool_begin + chunk_i * p.claim_chunk;
+        job_end = job_begin + p.claim_chunk < p.n_jobs ? job_begin + p.claim_chunk : p.n_jobs;
     }
 #if SGX_STAMPS
+    if (tid == 0 && blockIdx.x < kFinishBlocks) {
+        g_finish_r[4 * blockIdx.x + 1] = wall_clock64();
+        g_finish_r[4 * blockIdx.x + 2] = blockIdx.x;
+        g_finish_r[4 * blockIdx.x + 3] = jobs_done;
+    }
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int i = 0; i < 20; ++i) atomicAdd(&g_phase_cycles_r[i], st_acc[i]);
-        atomicAdd(&g_phase_cycles_r[20], (unsigned long long)(job_end - job_begin));
+        atomicAdd(&g_phase_cycles_r[20], jobs_done);
     }
 #endif
 }
 
 struct RealTables {
     DeviceBuffer<float2> d_tw1, d_tw2, d_twu;
+    DeviceBuffer<unsigned long long> d_claim;   // [1] the claim counter of a rows launch with a claimed tail: zeroed on the stream in front of every such launch
 };
 
 }  // namespace wgr
@@ -573,6 +631,12 @@ extern "C" __attribute__((visibility("default"))) int sgx_debug_phase_cycles_r(u
         e = hipMemcpyToSymbol(HIP_SYMBOL(wgr::g_phase_cycles_r), zero, sizeof(zero));
     }
     return e == hipSuccess ? 0 : -1;
+}
+// the first n_blocks records of g_finish_r (four words each), as the last launch of the kernel left them
+extern "C" __attribute__((visibility("default"))) int sgx_debug_finish_r(unsigned long long *h_out, int n_blocks)
+{
+    if (n_blocks < 0 || n_blocks > wgr::kFinishBlocks) return -1;
+    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(wgr::g_finish_r), sizeof(unsigned long long) * 4 * (size_t)n_blocks) == hipSuccess ? 0 : -1;
 }
 #endif
 
@@ -593,6 +657,7 @@ hipError_t real4096_init(sgx_ctx *c)
     hipError_t e = t->d_tw1.upload(tw1);
     if (e == hipSuccess) e = t->d_tw2.upload(tw2);
     if (e == hipSuccess) e = t->d_twu.upload(twu);
+    if (e == hipSuccess) e = t->d_claim.alloc(1);
     if (e == hipSuccess) c->real = std::move(t);
     return e;
 }
@@ -605,6 +670,23 @@ bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels)
 }
 
 namespace wg {
+
+// the split of a rows launch of n_jobs jobs in `blocks` workgroups: (16, 0) static, else (static share in sixteenths, jobs per chunk)
+struct RowsClaim { uint32_t sixteenths, chunk; };
+static RowsClaim rows_claim(const sgx_ctx *c, Out kind, unsigned long long n_jobs, unsigned long long blocks)
+{
+    const bool rows = kind == Out::kMags || kind == Out::kMagsF16 || kind == Out::kComplex;
+#ifdef SGX_VARIANT_SKIP_LAST_JOB   // (the sensitivity build compiles the static split only)
+    const bool compiled = false;
+#else
+    const bool compiled = true;
+#endif
+    if (!rows || !compiled || n_jobs == 0 || (c->claim_sixteenths == 16u && c->claim_chunk == 0u)) return {16u, 0u};
+    if (c->claim_chunk != 0u) return {c->claim_sixteenths, c->claim_chunk};
+    // (the complex rows -- twice the bytes per job -- gain nothing from it: 1e6 frames +0.2 ... +3.5 % on three buffers, profiles/k1r_claimed_tail.txt)
+    if (kind == Out::kComplex) return {16u, 0u};
+    return run_claim_engages(n_jobs, blocks) ? RowsClaim{kClaimAutoSixteenths, kClaimAutoChunk} : RowsClaim{16u, 0u};
+}
 
 // p: as launch_wg4096 (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
 // transform's own tables and the job split are set here
@@ -625,10 +707,27 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
         p.peak_run = 2 * runs.per;
     }
     p.jobs_per_block = runs.per;
+    // The rows launches deal only a share of the jobs statically and let the workgroups claim the rest in chunks (run_claim.hpp): where the
+    // context forces it (sgx_set_run_claim), else where the static run that is left is still long.  Otherwise nothing here differs from
+    // the static launch: no counter, no memset.
+    const RowsClaim rc = rows_claim(c, kind, p.n_jobs, runs.blocks);
+    if (rc.sixteenths != 16u || rc.chunk != 0u) {
+        const RunClaim split = run_claim(p.n_jobs, runs.blocks, rc.sixteenths, rc.chunk);
+        // zero on the stream in front of every launch: a replayed or an aborted launch leaves nothing behind that the next one reads
+        const hipError_t e = hipMemsetAsync(t->d_claim.get(), 0, sizeof(unsigned long long), c->stream);
+        if (e != hipSuccess) return e;
+        p.jobs_per_block = split.per;
+        p.claim_counter = t->d_claim.get();
+        p.claim_pool_begin = split.pool_begin;
+        p.claim_chunks = split.n_chunks;
+        p.claim_chunk = (uint32_t)split.chunk;
+    }
+    const size_t lds_claim = p.claim_counter ? sizeof(unsigned long long) : 0;   // the parked claim index, behind the tables
     const dim3 grid((unsigned)runs.blocks), block(256);
     auto launch = [&](auto slide_c) {
         constexpr bool S_ = decltype(slide_c)::value;
-        constexpr size_t lds_rows = S_ ? kLdsBytesR : kLdsBytes, lds_render = S_ ? kLdsBytesRenderR : kLdsBytesRender;
+        const size_t lds_rows = (S_ ? kLdsBytesR : kLdsBytes) + lds_claim;
+        constexpr size_t lds_render = S_ ? kLdsBytesRenderR : kLdsBytesRender;
         if (hold_peak) {
             if (p.interp == SGX_INTERP_COSINE) hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCosine, S_>), grid, block, lds_rows, c->stream, p);
             else hipLaunchKernelGGL((stft4096_real_kernel<kPeak, kPixPeakCubic, S_>), grid, block, lds_rows, c->stream, p);
@@ -658,3 +757,32 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
 }  // namespace wg
 
 }  // namespace sgx
+
+// Diagnostic: how the rows launches of the real-input 4096-point kernel deal their jobs (run_claim.hpp).  (16, 0): the static split; (0, 0): the
+// automatic rule; else the claimed tail at any size, `static_sixteenths` of the jobs dealt statically and the rest in chunks of `chunk_jobs`.
+// The results do not depend on it, bit for bit.
+int sgx_set_run_claim(sgx_ctx *c, uint32_t static_sixteenths, uint32_t chunk_jobs)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    if (!sgx::run_claim_valid(static_sixteenths, chunk_jobs)) {
+        c->err = "sgx_set_run_claim: a share of 0 .. 16 sixteenths with a chunk of 1 .. 2^20 jobs, (16, 0) for the static split or (0, 0) for the automatic rule";
+        return SGX_ERR_INVALID_ARG;
+    }
+    c->claim_sixteenths = static_sixteenths;
+    c->claim_chunk = chunk_jobs;
+    return SGX_OK;
+}
+
+// the split a float or half rows call of n_frames frames runs under, now: (16, 0) where it is the static one (complex rows: only a forced split)
+int sgx_run_claim(const sgx_ctx *c, size_t n_frames, uint32_t *static_sixteenths, uint32_t *chunk_jobs)
+{
+    if (!c || !static_sixteenths || !chunk_jobs) return SGX_ERR_INVALID_ARG;
+    sgx::wg::RowsClaim rc{16u, 0u};
+    if (sgx::real4096_serves(c, nullptr, c->C) && !(c->cfg.flags & (SGX_FLAG_PAIRED_FRAMES | SGX_FLAG_COMPLEX_MONO))) {
+        const unsigned long long n_jobs = ((unsigned long long)n_frames + 1) / 2;
+        rc = sgx::wg::rows_claim(c, sgx::Out::kMags, n_jobs, sgx::run_split(c, n_jobs, 4).blocks);
+    }
+    *static_sixteenths = rc.sixteenths;
+    *chunk_jobs = rc.chunk;
+    return SGX_OK;
+}

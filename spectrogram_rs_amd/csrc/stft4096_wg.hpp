@@ -47,9 +47,20 @@ struct Params {
     uint32_t H, C, pair_l, pair_r, pairs, pair;
     uint32_t out_f16;          // magnitudes are stored as (l, r) half pairs, 4 B per bin (the F16F16 ring of gpu_spectrogram.rs:218-226)
     // fused pixel path (RENDER): magnitudes never leave LDS
-    const uint32_t *rows;      // [R]  first slot | count << 16
-    const PackedSample *samples;   // one entry per LDS slot: the rows' samples in lin_space order, plus pad slots (see wg4096_init)
-    uint32_t n_samples;        // slots per column (sum of the rows' counts + pads)
+    // The rows launches of the real-input kernel read none of the pixel fields: a launch with a claimed tail (run_claim.hpp) carries its
+    // four values in those words, for the same reason as the peak-hold columns above.  claim_counter null: the static split.
+    union {
+        const uint32_t *rows;      // [R]  first slot | count << 16
+        unsigned long long *claim_counter;   // one device word, zero at the launch: the next chunk of the pool
+    };
+    union {
+        const PackedSample *samples;   // one entry per LDS slot: the rows' samples in lin_space order, plus pad slots (see wg4096_init)
+        unsigned long long claim_pool_begin;   // first job of the pool; jobs_per_block is then the static run
+    };
+    union {
+        uint32_t n_samples;        // slots per column (sum of the rows' counts + pads)
+        uint32_t claim_chunk;      // jobs per chunk
+    };
     union {
         const float *lut_thr;            // [255]
         unsigned long long peak_group;   // frames per column, at most n_frames
@@ -58,7 +69,10 @@ struct Params {
         const uchar4 *lut_rgba;          // [256]
         unsigned long long peak_run;     // frames per workgroup: its run is [blockIdx.x * peak_run, + peak_run) of the call's frames
     };
-    uint8_t *rgba;             // [F][pairs][R][4]
+    union {
+        uint8_t *rgba;             // [F][pairs][R][4]
+        unsigned long long claim_chunks;   // chunks of the pool: a claim index from here on ends the workgroup
+    };
     uint32_t R, interp;
     float guess_a, guess_b;    // LUT index ~ floor(log2(power + 1e-7) * a + b), then exact fix-up
     uint32_t seed_pm1;         // the host has shown that this seed is never off by more than one (seed_within_one): one compare pair fixes it

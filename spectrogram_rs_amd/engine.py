@@ -117,6 +117,18 @@ class SpectrogramEngine:
         """the compute-unit count in force"""
         return int(self._lib.sgx_cu_limit(self._ctx))
 
+    def set_run_claim(self, static_sixteenths: int, chunk_jobs: int):
+        """Diagnostic: how the rows calls of a mono W 2048 engine deal their frame pairs to the persistent workgroups: (16, 0) one static run
+        each, (0, 0) the default rule, else `static_sixteenths` / 16 of them statically and the rest claimed in chunks of `chunk_jobs`.
+        Results do not depend on it."""
+        self._check(self._lib.sgx_set_run_claim(self._ctx, C.c_uint32(static_sixteenths), C.c_uint32(chunk_jobs)))
+
+    def run_claim(self, n_frames: int):
+        """(static_sixteenths, chunk_jobs) a rows call of n_frames frames would run under now; (16, 0): the static split"""
+        s, k = C.c_uint32(), C.c_uint32()
+        self._check(self._lib.sgx_run_claim(self._ctx, C.c_size_t(n_frames), C.byref(s), C.byref(k)))
+        return int(s.value), int(k.value)
+
     def _dev_f32(self, t):
         import torch
 
