@@ -78,6 +78,8 @@ extern "C" {
     pub fn sgx_cu_limit(ctx: *const SgxCtx) -> u32;
     pub fn sgx_set_run_claim(ctx: *mut SgxCtx, static_sixteenths: u32, chunk_jobs: u32) -> c_int;
     pub fn sgx_run_claim(ctx: *const SgxCtx, n_frames: usize, static_sixteenths: *mut u32, chunk_jobs: *mut u32) -> c_int;
+    pub fn sgx_set_run_weights(ctx: *mut SgxCtx, w: *const u32) -> c_int;
+    pub fn sgx_run_weights(ctx: *const SgxCtx, n_frames: usize, w: *mut u32) -> c_int;
 }
 extern "C" {   // from libamdhip64, for staging buffers
     pub fn hipMalloc(p: *mut *mut c_void, bytes: usize) -> c_int;

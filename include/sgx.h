@@ -197,14 +197,23 @@ SGX_API int sgx_set_cu_limit(sgx_ctx *ctx, uint32_t n);
 SGX_API uint32_t sgx_cu_limit(const sgx_ctx *ctx);   /* the count in force; 0 for a null context */
 
 /* Diagnostic: how the rows calls (sgx_stft_batch, _f16, _complex) of a mono W 2048 context deal their frame pairs ("jobs") to the
- * persistent workgroups. By default a long float or half rows call deals 12/16 of them as one static run per workgroup and lets the
- * workgroups claim the rest in chunks of 8, so that all finish together; a call that would leave static runs of fewer than 64 jobs,
- * and every complex rows call, is dealt statically.
+ * persistent workgroups. By default a long float or half rows call deals most of them as one static run per workgroup and lets the
+ * workgroups claim the rest in chunks, so that all finish together: 15/16 in weighted runs (sgx_set_run_weights) and chunks of 4 at a
+ * hop of 256 on the whole device, 12/16 in equal runs and chunks of 8 elsewhere. A call that would leave static runs of fewer than
+ * 64 jobs at 12/16, and every complex rows call, is dealt statically.
  * (16, 0): always static. (0, 0): the default rule. Any other share 0 .. 16 with a chunk of 1 .. 2^20 jobs: that split at any size.
  * Anything else: SGX_ERR_INVALID_ARG. Results do not depend on it, bit for bit (tests/test_gpu_claimed_runs.py). */
 SGX_API int sgx_set_run_claim(sgx_ctx *ctx, uint32_t static_sixteenths, uint32_t chunk_jobs);
 /* the split a float or half rows call of n_frames frames would run under now: (16, 0) where that is the static one */
 SGX_API int sgx_run_claim(const sgx_ctx *ctx, size_t n_frames, uint32_t *static_sixteenths, uint32_t *chunk_jobs);
+/* Diagnostic: the weights of those calls' static runs. Four workgroups share a compute unit, the n-th one placed there runs at its own
+ * rate, and its static run is w[n] / 64 of the equal one. Four weights of at least 1 each that sum to 256; (64, 64, 64, 64): equal runs.
+ * NULL or all zero: the default, the measured weights where a call fills every compute unit of the device four times and equal runs
+ * elsewhere. Weights that are set apply at any size and any sgx_set_cu_limit. Anything else: SGX_ERR_INVALID_ARG.
+ * Results do not depend on the weights, bit for bit (tests/test_gpu_weighted_runs.py). */
+SGX_API int sgx_set_run_weights(sgx_ctx *ctx, const uint32_t w[4]);
+/* the four weights a float rows call of n_frames frames would run under now */
+SGX_API int sgx_run_weights(const sgx_ctx *ctx, size_t n_frames, uint32_t w[4]);
 
 /* ---- the transform: replaces AudioTransform::process / AudioStreamTransform::process ----- */
 

@@ -96,6 +96,8 @@ SIGNATURES = [
     ("sgx_cu_limit", C.c_uint32, [_ctx]),
     ("sgx_set_run_claim", C.c_int, [_ctx, C.c_uint32, C.c_uint32]),
     ("sgx_run_claim", C.c_int, [_ctx, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("sgx_set_run_weights", C.c_int, [_ctx, C.POINTER(C.c_uint32)]),
+    ("sgx_run_weights", C.c_int, [_ctx, _sz, C.POINTER(C.c_uint32)]),
     ("sgx_stft_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_stft_batch_f16", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_stft_batch_complex", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),

@@ -180,6 +180,8 @@ struct sgx_ctx {
     int n_cu_device = 256;   // hipDeviceAttributeMultiprocessorCount
     // sgx_set_run_claim: how the rows launches of the real-input 4096-point kernel deal their jobs (run_claim.hpp).  (0, 0): the automatic rule
     uint32_t claim_sixteenths = 0, claim_chunk = 0;
+    // sgx_set_run_weights: the slot weights of those launches' static runs (run_claim.hpp).  All zero: the automatic ones
+    uint32_t run_weights[4] = {0, 0, 0, 0};
     size_t lds_optin = 64 * 1024;   // hipDeviceAttributeSharedMemPerBlockOptin: the largest LDS image a workgroup may ask for
     // resident workgroups per CU of a kernel instantiation at a block size and LDS image (hipOccupancyMaxActiveBlocksPerMultiprocessor, cached)
     mutable std::vector<std::pair<std::array<size_t, 3>, int>> occupancy_cache;

@@ -230,6 +230,23 @@ __global__ void __launch_bounds__(256, 4) stft4096_real_kernel(Params p)
     unsigned long long *claim_word = reinterpret_cast<unsigned long long *>(tw2 + 256);   // LDS, behind the tables: the claim of the run after this one
     unsigned long long job_begin = (unsigned long long)blockIdx.x * p.jobs_per_block;
     unsigned long long job_end = job_begin + p.jobs_per_block;
+    // The static run of a rows launch dealt by slot (run_claim.hpp: the n-th workgroup placed on a CU runs at the n-th slot's rate, and its
+    // run is sized for it): the deal rides in the LUT and seed words, and slot_run is compares, selects and three scalar multiplications.
+    if (CLAIM && p.slot_n_cu != 0u) {
+        SlotDeal deal{};
+        deal.per[0] = p.slot_per0;
+        deal.per[1] = p.slot_per1;
+        deal.per[2] = ((unsigned long long)p.slot_per2_hi << 32) | p.slot_per2_lo;
+        deal.per[3] = ((unsigned long long)p.slot_per3_hi << 32) | p.slot_per3_lo;
+        deal.n_cu = p.slot_n_cu;
+        deal.leftover = p.slot_leftover;
+        const JobRun run = slot_run(deal, blockIdx.x);
+        // (scalar by statement: the compiler forms the 64-bit products in vector registers, and a run held there stays in two of them for
+        // the whole loop -- every register of the iteration renumbered)
+        auto uniform = [](unsigned long long v) { return ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)v); };
+        job_begin = uniform(run.begin);
+        job_end = uniform(run.end);
+    }
     if (job_end > p.n_jobs) job_end = p.n_jobs;
 #ifdef SGX_VARIANT_SKIP_LAST_JOB   // the sensitivity build of tests/test_gpu_cu_counts.py: a run of more than one job omits its last (omits work only)
     if (job_end > job_begin + 1) --job_end;
@@ -671,21 +688,36 @@ bool real4096_serves(const sgx_ctx *c, const float *d_pcm, uint32_t channels)
 
 namespace wg {
 
-// the split of a rows launch of n_jobs jobs in `blocks` workgroups: (16, 0) static, else (static share in sixteenths, jobs per chunk)
-struct RowsClaim { uint32_t sixteenths, chunk; };
+// the deal of a rows launch of n_jobs jobs in `blocks` workgroups: (16, 0) static, else (static share in sixteenths, jobs per chunk); w: the slot
+// weights of the static runs (run_claim.hpp), all 64 for the equal deal
+struct RowsClaim { uint32_t sixteenths, chunk; uint32_t w[4]; };
 static RowsClaim rows_claim(const sgx_ctx *c, Out kind, unsigned long long n_jobs, unsigned long long blocks)
 {
     const bool rows = kind == Out::kMags || kind == Out::kMagsF16 || kind == Out::kComplex;
-#ifdef SGX_VARIANT_SKIP_LAST_JOB   // (the sensitivity build compiles the static split only)
+#ifdef SGX_VARIANT_SKIP_LAST_JOB   // (the sensitivity build compiles the equal static split only)
     const bool compiled = false;
 #else
     const bool compiled = true;
 #endif
-    if (!rows || !compiled || n_jobs == 0 || (c->claim_sixteenths == 16u && c->claim_chunk == 0u)) return {16u, 0u};
-    if (c->claim_chunk != 0u) return {c->claim_sixteenths, c->claim_chunk};
-    // (the complex rows -- twice the bytes per job -- gain nothing from it: 1e6 frames +0.2 ... +3.5 % on three buffers, profiles/k1r_claimed_tail.txt)
-    if (kind == Out::kComplex) return {16u, 0u};
-    return run_claim_engages(n_jobs, blocks) ? RowsClaim{kClaimAutoSixteenths, kClaimAutoChunk} : RowsClaim{16u, 0u};
+    RowsClaim rc{16u, 0u, {64u, 64u, 64u, 64u}};
+    if (!rows || !compiled || n_jobs == 0) return rc;
+    // the weights: the context's (sgx_set_run_weights) anywhere, else the measured ones where the slots are the measured ones
+    const bool forced_w = c->run_weights[0] != 0u;
+    const unsigned *w = forced_w ? c->run_weights : slot_weights_measured(blocks, (unsigned long long)c->n_cu, c->n_cu != c->n_cu_device, c->H) ? slot_weights_auto(kind == Out::kComplex) : kSlotWeightsEqual;
+    for (int s = 0; s < 4; ++s) rc.w[s] = w[s];
+    if (c->claim_sixteenths == 16u && c->claim_chunk == 0u) return rc;
+    if (c->claim_chunk != 0u) {
+        rc.sixteenths = c->claim_sixteenths;
+        rc.chunk = c->claim_chunk;
+        return rc;
+    }
+    // (the complex rows -- twice the bytes per job -- lose with a pool of equal runs, +0.2 ... +3.5 %, profiles/k1r_claimed_tail.txt, and gain nothing
+    // from one behind weighted runs, profiles/k1r_slot_weights.txt: their weights stand alone)
+    if (kind == Out::kComplex || !run_claim_engages(n_jobs, blocks)) return rc;
+    const bool weighted = !slot_weights_equal(rc.w);
+    rc.sixteenths = weighted ? kSlotAutoSixteenths : kClaimAutoSixteenths;
+    rc.chunk = weighted ? kSlotAutoChunk : kClaimAutoChunk;
+    return rc;
 }
 
 // p: as launch_wg4096 (stft4096_wg.hip) fills it for a one-channel stream -- stream, window, tw2, output, the pixel tables; the
@@ -711,12 +743,28 @@ hipError_t launch_real4096(const sgx_ctx *c, Params p, Out kind)
     // context forces it (sgx_set_run_claim), else where the static run that is left is still long.  Otherwise nothing here differs from
     // the static launch: no counter, no memset.
     const RowsClaim rc = rows_claim(c, kind, p.n_jobs, runs.blocks);
-    if (rc.sixteenths != 16u || rc.chunk != 0u) {
-        const RunClaim split = run_claim(p.n_jobs, runs.blocks, rc.sixteenths, rc.chunk);
+    const bool pooled = rc.sixteenths != 16u || rc.chunk != 0u;
+    RunClaim split{};
+    if (!slot_weights_equal(rc.w)) {
+        // static runs sized by slot: the deal rides in the LUT and seed words (Params), the kernel forms its run from them (slot_run)
+        const SlotDeal deal = slot_deal(p.n_jobs, runs.blocks, (unsigned long long)c->n_cu, rc.sixteenths, rc.chunk, rc.w);
+        p.slot_per0 = deal.per[0];
+        p.slot_per1 = deal.per[1];
+        p.slot_per2_lo = (uint32_t)deal.per[2];
+        p.slot_per2_hi = (uint32_t)(deal.per[2] >> 32);
+        p.slot_per3_lo = (uint32_t)deal.per[3];
+        p.slot_per3_hi = (uint32_t)(deal.per[3] >> 32);
+        p.slot_n_cu = (uint32_t)c->n_cu;
+        p.slot_leftover = (uint32_t)deal.leftover;
+        split = deal.claim;
+    } else if (pooled) {
+        split = run_claim(p.n_jobs, runs.blocks, rc.sixteenths, rc.chunk);
+        p.jobs_per_block = split.per;
+    }
+    if (pooled) {
         // zero on the stream in front of every launch: a replayed or an aborted launch leaves nothing behind that the next one reads
         const hipError_t e = hipMemsetAsync(t->d_claim.get(), 0, sizeof(unsigned long long), c->stream);
         if (e != hipSuccess) return e;
-        p.jobs_per_block = split.per;
         p.claim_counter = t->d_claim.get();
         p.claim_pool_begin = split.pool_begin;
         p.claim_chunks = split.n_chunks;
@@ -777,12 +825,39 @@ int sgx_set_run_claim(sgx_ctx *c, uint32_t static_sixteenths, uint32_t chunk_job
 int sgx_run_claim(const sgx_ctx *c, size_t n_frames, uint32_t *static_sixteenths, uint32_t *chunk_jobs)
 {
     if (!c || !static_sixteenths || !chunk_jobs) return SGX_ERR_INVALID_ARG;
-    sgx::wg::RowsClaim rc{16u, 0u};
+    sgx::wg::RowsClaim rc{16u, 0u, {64u, 64u, 64u, 64u}};
     if (sgx::real4096_serves(c, nullptr, c->C) && !(c->cfg.flags & (SGX_FLAG_PAIRED_FRAMES | SGX_FLAG_COMPLEX_MONO))) {
         const unsigned long long n_jobs = ((unsigned long long)n_frames + 1) / 2;
         rc = sgx::wg::rows_claim(c, sgx::Out::kMags, n_jobs, sgx::run_split(c, n_jobs, 4).blocks);
     }
     *static_sixteenths = rc.sixteenths;
     *chunk_jobs = rc.chunk;
+    return SGX_OK;
+}
+
+// Diagnostic: the slot weights of those launches' static runs (run_claim.hpp: the n-th workgroup placed on a CU runs w[n] / 64 of the equal
+// run).  Null or all zero: the automatic weights.  Forced weights apply at any CU limit.  The results do not depend on them, bit for bit.
+int sgx_set_run_weights(sgx_ctx *c, const uint32_t *w)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    const bool automatic = !w || (w[0] == 0u && w[1] == 0u && w[2] == 0u && w[3] == 0u);
+    if (!automatic && !sgx::run_weights_valid(w)) {
+        c->err = "sgx_set_run_weights: four weights of at least 1 each that sum to 256, or all zero (a null pointer) for the automatic ones";
+        return SGX_ERR_INVALID_ARG;
+    }
+    for (int s = 0; s < 4; ++s) c->run_weights[s] = automatic ? 0u : w[s];
+    return SGX_OK;
+}
+
+// the weights a float rows call of n_frames frames runs under, now: (64, 64, 64, 64) where its static runs are equal
+int sgx_run_weights(const sgx_ctx *c, size_t n_frames, uint32_t *w)
+{
+    if (!c || !w) return SGX_ERR_INVALID_ARG;
+    sgx::wg::RowsClaim rc{16u, 0u, {64u, 64u, 64u, 64u}};
+    if (sgx::real4096_serves(c, nullptr, c->C) && !(c->cfg.flags & (SGX_FLAG_PAIRED_FRAMES | SGX_FLAG_COMPLEX_MONO))) {
+        const unsigned long long n_jobs = ((unsigned long long)n_frames + 1) / 2;
+        rc = sgx::wg::rows_claim(c, sgx::Out::kMags, n_jobs, sgx::run_split(c, n_jobs, 4).blocks);
+    }
+    for (int s = 0; s < 4; ++s) w[s] = rc.w[s];
     return SGX_OK;
 }

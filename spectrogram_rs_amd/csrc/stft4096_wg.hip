@@ -44,6 +44,14 @@ constexpr int kPrioA = 1, kPrioB = 2;   // (l, r) / (s, s) transforms: wave prio
 #if SGX_STAMPS
 // diagnostic build only (tools/k1_phases.py): per-phase wave cycles (s_memtime), summed over all waves and iterations; SGX_STAMP: sgx_internal.hpp
 __device__ unsigned long long g_phase_cycles[20];
+// tools/k1_finish.py: per workgroup {wall clock at entry, at exit, block index, jobs done}, plain stores of thread 0, as K1R keeps them
+// (stft4096_real.hip).  -DSGX_STAMPS=2 keeps these and compiles the phase stamps away, so that the iteration is the product's.
+constexpr int kFinishBlocks = 4096;
+__device__ unsigned long long g_finish[4 * kFinishBlocks];
+#if SGX_STAMPS == 2
+#undef SGX_STAMP
+#define SGX_STAMP(i)
+#endif
 #endif
 
 // PIX: kPixNone = rows (float or half pairs); else the fused pixel path with that pixel code (stft4096_wg.hpp)
@@ -105,6 +113,9 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
     float *plane = reinterpret_cast<float *>(smem_raw);           // TR: re [16][272], im [16][272] behind it (34 816 B, the images' bytes)
     const uint32_t m0_wave = __builtin_amdgcn_readfirstlane((uint32_t)(tid >> 6) * 272u);   // TR: byte offset of this wave inside a plane row
     const float4 *rd4 = reinterpret_cast<const float4 *>(plane + 272 * (tid >> 4) + 68 * ((tid & 15) >> 2) + 16 * (tid & 3));   // TR: both read sides
+#if SGX_STAMPS
+    if (tid == 0 && blockIdx.x < kFinishBlocks) g_finish[4 * blockIdx.x] = wall_clock64();
+#endif
     tw2[tid] = p.tw2[tid];
     uint32_t row_words[4] = {0u, 0u, 0u, 0u};  // RENDER: the table words of this thread's rows tid + 256 i
     if (RENDER && !FBANK && !CROSS) {
@@ -580,6 +591,11 @@ __global__ void __launch_bounds__(256, 4) stft4096_wg_kernel(Params p)
         }
     }
 #if SGX_STAMPS
+    if (tid == 0 && blockIdx.x < kFinishBlocks) {
+        g_finish[4 * blockIdx.x + 1] = wall_clock64();
+        g_finish[4 * blockIdx.x + 2] = blockIdx.x;
+        g_finish[4 * blockIdx.x + 3] = job_end > job_begin ? job_end - job_begin : 0;
+    }
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) atomicAdd(&g_phase_cycles[i], st_acc[i]);
@@ -656,6 +672,12 @@ extern "C" __attribute__((visibility("default"))) int sgx_debug_phase_cycles(uns
         e = hipMemcpyToSymbol(HIP_SYMBOL(wg::g_phase_cycles), zero, sizeof(zero));
     }
     return e == hipSuccess ? 0 : -1;
+}
+// the first n_blocks records of g_finish (four words each), as the last launch of the kernel left them
+extern "C" __attribute__((visibility("default"))) int sgx_debug_finish(unsigned long long *h_out, int n_blocks)
+{
+    if (n_blocks < 0 || n_blocks > wg::kFinishBlocks) return -1;
+    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(wg::g_finish), sizeof(unsigned long long) * 4 * (size_t)n_blocks) == hipSuccess ? 0 : -1;
 }
 #endif
 

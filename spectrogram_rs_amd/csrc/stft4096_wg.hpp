@@ -61,22 +61,30 @@ struct Params {
         uint32_t n_samples;        // slots per column (sum of the rows' counts + pads)
         uint32_t claim_chunk;      // jobs per chunk
     };
+    // A rows launch of the real-input kernel whose static runs are dealt by slot (run_claim.hpp, SlotDeal) carries the deal in the LUT and
+    // seed words: the four run lengths (slots 2 and 3 as two 32-bit halves each), the blocks per slot and the leftover count.  The slot
+    // bases are not carried -- there are 44 such bytes, not 72 -- but formed from the lengths in front of the run loop (slot_run).
+    // slot_n_cu 0: the equal deal, blockIdx.x * jobs_per_block.
     union {
         const float *lut_thr;            // [255]
         unsigned long long peak_group;   // frames per column, at most n_frames
+        unsigned long long slot_per0;
     };
     union {
         const uchar4 *lut_rgba;          // [256]
         unsigned long long peak_run;     // frames per workgroup: its run is [blockIdx.x * peak_run, + peak_run) of the call's frames
+        unsigned long long slot_per1;
     };
     union {
         uint8_t *rgba;             // [F][pairs][R][4]
         unsigned long long claim_chunks;   // chunks of the pool: a claim index from here on ends the workgroup
     };
-    uint32_t R, interp;
-    float guess_a, guess_b;    // LUT index ~ floor(log2(power + 1e-7) * a + b), then exact fix-up
-    uint32_t seed_pm1;         // the host has shown that this seed is never off by more than one (seed_within_one): one compare pair fixes it
-    uint32_t single_rows;      // bit i: every row of block i (rows 256 i .. 256 i + 255) averages exactly one sample
+    union { uint32_t R; uint32_t slot_per2_lo; };
+    union { uint32_t interp; uint32_t slot_per2_hi; };
+    union { float guess_a; uint32_t slot_per3_lo; };    // LUT index ~ floor(log2(power + 1e-7) * a + b), then exact fix-up
+    union { float guess_b; uint32_t slot_per3_hi; };
+    union { uint32_t seed_pm1; uint32_t slot_n_cu; };         // the host has shown that this seed is never off by more than one (seed_within_one): one compare pair fixes it
+    union { uint32_t single_rows; uint32_t slot_leftover; };  // bit i: every row of block i (rows 256 i .. 256 i + 255) averages exactly one sample
     uint32_t block_max_cnt;    // byte i: the largest sample count of a row of block i.  No kernel reads it (docs/history/retired_switches.md): it keeps the argument layout
     // the real-input kernel (stft4096_real.hip: every mono frame its own transform; tw1 is then [8][256] w_2048^{t q1})
     const float2 *twu;         // [8][128] w_4096^{u + 128 q3} at [q3][u]; [0][0] holds w_4096^{1024} = -i

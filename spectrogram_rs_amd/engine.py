@@ -129,6 +129,18 @@ class SpectrogramEngine:
         self._check(self._lib.sgx_run_claim(self._ctx, C.c_size_t(n_frames), C.byref(s), C.byref(k)))
         return int(s.value), int(k.value)
 
+    def set_run_weights(self, w=None):
+        """Diagnostic: the weights of those calls' static runs, by the workgroup's place on its compute unit: four integers of at least 1
+        that sum to 256, (64, 64, 64, 64) for equal runs; None or all zero: the default.  Results do not depend on them."""
+        arr = (C.c_uint32 * 4)(*(int(x) for x in w)) if w is not None else None
+        self._check(self._lib.sgx_set_run_weights(self._ctx, arr))
+
+    def run_weights(self, n_frames: int):
+        """the four weights a float rows call of n_frames frames would run under now"""
+        w = (C.c_uint32 * 4)()
+        self._check(self._lib.sgx_run_weights(self._ctx, C.c_size_t(n_frames), w))
+        return tuple(int(x) for x in w)
+
     def _dev_f32(self, t):
         import torch
 

@@ -4,7 +4,9 @@ into each of three buffers kept alive (the first allocation among them), hot; in
 A, B, A' -- A' is a second context of build A, and |A - A'| is the A/A spread the difference is read against.  Both libraries are loaded
 with local symbol scope.  Per buffer: the median over the rounds of the mean launch time, the ratio B / A, and whether A - B exceeds twice
 the spread.
-usage: tools/k1r_ab_libs.py <libA.so: the base> <libB.so: the change> [--frames N] [--rounds R] [--launches L] [--kind stft|f16|complex] [--hop H]"""
+--claim-b / --weights-b force a split / slot weights on build B's context (sgx_set_run_claim, sgx_set_run_weights), --claim-a a split on A's.
+usage: tools/k1r_ab_libs.py <libA.so: the base> <libB.so: the change> [--frames N] [--rounds R] [--launches L] [--kind stft|f16|complex] [--hop H]
+       [--claim-a S,K] [--claim-b S,K] [--weights-b w0,w1,w2,w3]"""
 import argparse
 import ctypes as C
 import os
@@ -24,6 +26,9 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--launches", type=int, default=12)
 ap.add_argument("--kind", default="stft", choices=["stft", "f16", "complex"], help="float rows (the headline), half rows, complex rows")
 ap.add_argument("--hop", type=int, default=256)
+ap.add_argument("--claim-a", default="")
+ap.add_argument("--claim-b", default="")
+ap.add_argument("--weights-b", default="")
 args = ap.parse_args()
 F = args.frames
 
@@ -47,6 +52,14 @@ DTYPE = {"stft": torch.float32, "f16": torch.float16, "complex": torch.complex64
 bufs = [torch.empty((F, 1, 2047, 2), dtype=DTYPE, device="cuda") for _ in range(3)]
 engs = {"A": engine_of(args.lib_a), "B": engine_of(args.lib_b), "A'": engine_of(args.lib_a)}
 pcm = engs["A"].white_noise((F - 1) * args.hop + 2048)
+if args.claim_a:
+    for n in ("A", "A'"):
+        engs[n].set_run_claim(*(int(x) for x in args.claim_a.split(",")))
+if args.claim_b:
+    engs["B"].set_run_claim(*(int(x) for x in args.claim_b.split(",")))
+if args.weights_b:
+    engs["B"].set_run_weights([int(x) for x in args.weights_b.split(",")])
+print("A runs under", engs["A"].run_claim(F), " B under", engs["B"].run_claim(F), engs["B"].run_weights(F) if hasattr(engs["B"]._lib, "sgx_run_weights") else "")
 
 
 def launch(eng, out):
