@@ -202,7 +202,9 @@ SGX_API uint32_t sgx_cu_limit(const sgx_ctx *ctx);   /* the count in force; 0 fo
  * hop of 256 on the whole device, 12/16 in equal runs and chunks of 8 elsewhere. A call that would leave static runs of fewer than
  * 64 jobs at 12/16, and every complex rows call, is dealt statically.
  * (16, 0): always static. (0, 0): the default rule. Any other share 0 .. 16 with a chunk of 1 .. 2^20 jobs: that split at any size.
- * Anything else: SGX_ERR_INVALID_ARG. Results do not depend on it, bit for bit (tests/test_gpu_claimed_runs.py). */
+ * Anything else: SGX_ERR_INVALID_ARG. Results do not depend on it, bit for bit (tests/test_gpu_claimed_runs.py).
+ * The rows launches of the workspace routes take the same deal -- sgx_psd_batch always, and sgx_render_batch, sgx_bands_batch,
+ * sgx_bands_peak_batch and sgx_fbank_batch under SGX_FLAG_NO_FUSED_RENDER -- and the same file holds those consumers to it. */
 SGX_API int sgx_set_run_claim(sgx_ctx *ctx, uint32_t static_sixteenths, uint32_t chunk_jobs);
 /* the split a float or half rows call of n_frames frames would run under now: (16, 0) where that is the static one */
 SGX_API int sgx_run_claim(const sgx_ctx *ctx, size_t n_frames, uint32_t *static_sixteenths, uint32_t *chunk_jobs);
@@ -210,7 +212,8 @@ SGX_API int sgx_run_claim(const sgx_ctx *ctx, size_t n_frames, uint32_t *static_
  * rate, and its static run is w[n] / 64 of the equal one. Four weights of at least 1 each that sum to 256; (64, 64, 64, 64): equal runs.
  * NULL or all zero: the default, the measured weights where a call fills every compute unit of the device four times and equal runs
  * elsewhere. Weights that are set apply at any size and any sgx_set_cu_limit. Anything else: SGX_ERR_INVALID_ARG.
- * Results do not depend on the weights, bit for bit (tests/test_gpu_weighted_runs.py). */
+ * Results do not depend on the weights, bit for bit (tests/test_gpu_weighted_runs.py); the rows launches of the workspace routes take
+ * the same deal, the automatic one included, and that file holds their consumers to it as well. */
 SGX_API int sgx_set_run_weights(sgx_ctx *ctx, const uint32_t w[4]);
 /* the four weights a float rows call of n_frames frames would run under now */
 SGX_API int sgx_run_weights(const sgx_ctx *ctx, size_t n_frames, uint32_t w[4]);
@@ -344,7 +347,8 @@ SGX_API int sgx_bands_peak_fused(const sgx_ctx *ctx);
  *   3. the output is (float)(S / (double)n_j): one float64 division, rounded once to float32.
  * The block length 32 is fixed here: it does not depend on the device, the compute-unit limit, the route or the chunking.  The output is
  * therefore a pure function of the rows: bit-identical across routes, compute-unit limits, streams, chunk seams and any split of a call
- * at a column boundary (tests/test_gpu_psd.py), and numpy reproduces it bit for bit without a fused multiply-add (a float32 cumsum along
+ * at a column boundary (tests/test_gpu_psd.py; the harnesses of every entry point hold these calls too: tests/test_gpu_bounds.py,
+ * test_gpu_stream_routes.py, test_gpu_far_offsets.py, test_gpu_channel_counts.py, test_gpu_cu_counts.py), and numpy reproduces it bit for bit without a fused multiply-add (a float32 cumsum along
  * the frames of a block, a float64 cumsum over the blocks: tests/psd_reference.py).  group = 1 gives exactly rn(m * m), or x0 .. x3.
  * Against the float64 mean of the float64 products of the same float32 rows the error is at most 35 * 2^-24 times the mean of the
  * absolute products of the term (1 rounding for the product, 31 for the chain, 1 for the cast, 2 for second-order terms).

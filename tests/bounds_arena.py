@@ -107,6 +107,135 @@ def fbank_cross_chunk(W: int, pairs: int) -> int:
     return max(WORKSPACE_BYTES // (2 * mags_bytes_per_frame(W, pairs)), 1)
 
 
+# ---- the ranges of the Welch calls (a restatement of psd_reduce, sgx_api.hip, and of Geometry, sgx_psd.hpp) -------------------------
+WELCH_BLOCK = 32                # include/sgx.h: frames per block of the float32 chain
+
+
+def welch_row_bytes(W: int, pairs: int, cross: bool) -> int:
+    """a row of the Welch calls and a block's partial row alike: the magnitudes of a frame (psd), twice that (csd)"""
+    return mags_bytes_per_frame(W, pairs) * (2 if cross else 1)
+
+
+def welch_cap(W: int, pairs: int, cross: bool) -> int:
+    """rows (or partial rows) the workspace holds; 0 where one row is larger than all of it"""
+    return WORKSPACE_BYTES // welch_row_bytes(W, pairs, cross)
+
+
+@dataclass(frozen=True)
+class WelchRange:
+    blocks: tuple           # [b_lo, b_hi) of the call's blocks
+    frames: tuple           # [f_lo, f_hi) of the call's frames
+    pieces: tuple           # ((f, f + k, resume), ...): the rows launches of the range; resume: the block launch loads its partials
+    reads_carry: bool       # the combine continues the column's float64 sums from the carry row
+    writes_carry: bool      # ... and leaves them there: the column ends in a later range
+
+
+@dataclass(frozen=True)
+class WelchPlan:
+    cap: int
+    fpb: int                # frames per block, at most
+    per: int                # blocks per range, at most
+    piece: int              # frames per rows launch where a block's rows do not fit beside one partial row, else 0
+    carried: bool           # a column has more blocks than a range: taken alone, its sums in the carry row between ranges
+    row_slots: int          # rows in front of the partial rows (0: the stage calls, whose rows are the caller's)
+    ranges: tuple
+
+    @property
+    def workspace_rows(self):
+        """rows the workspace is grown to: the row slots and `per` partial rows behind them"""
+        return self.row_slots + self.per
+
+    @property
+    def resumed(self):
+        return any(p[2] for r in self.ranges for p in r.pieces)
+
+
+def welch_ranges(W: int, pairs: int, cross: bool, n: int, group: int, own_rows: bool, cap: int = None) -> WelchPlan:
+    """The ranges psd_reduce takes a call of n frames in columns of `group` in.  own_rows: the batch calls, whose rows go to the front
+    of the workspace; else the stage calls.  cap: the rows the workspace holds, by default that of (W, pairs, cross)."""
+    assert n >= 1 and group >= 1
+    if cap is None:
+        cap = welch_cap(W, pairs, cross)
+    g = min(group, n)
+    bpc = (g + WELCH_BLOCK - 1) // WELCH_BLOCK
+    full, rem = divmod(n, g)
+    every = full * bpc + (rem + WELCH_BLOCK - 1) // WELCH_BLOCK
+
+    def column_end(j):
+        return n if n - j * g < g else (j + 1) * g
+
+    def block_first(b):
+        return (b // bpc) * g + (b % bpc) * WELCH_BLOCK
+
+    def block_end(b):
+        f, ce = block_first(b), column_end(b // bpc)
+        return ce if ce - f < WELCH_BLOCK else f + WELCH_BLOCK
+
+    def column_block_end(j):
+        return every if every - j * bpc < bpc else (j + 1) * bpc
+
+    fpb = min(g, WELCH_BLOCK)
+    per, piece = cap, 0
+    if own_rows:
+        if cap >= fpb + 1:
+            per = cap // (fpb + 1)
+        else:
+            per, piece = 1, (cap - 1 if cap > 1 else 1)
+    per = min(max(per, 1), every)
+    carried = bpc > per
+    if not carried:
+        per -= per % bpc
+    row_slots = min(piece if piece else per * fpb, n) if own_rows else 0
+    ranges, b = [], 0
+    while b < every:
+        j = b // bpc
+        m = min(every - b, per)
+        if carried:
+            m = min(m, column_block_end(j) - b)
+        f_lo, f_hi = block_first(b), block_end(b + m - 1)
+        pieces, f = [], f_lo
+        while f < f_hi:
+            k = min(f_hi - f, piece) if piece else f_hi - f
+            pieces.append((f, f + k, f != f_lo))
+            f += k
+        reads = carried and b != j * bpc
+        writes = carried and b + m != column_block_end(j)
+        ranges.append(WelchRange((b, b + m), (f_lo, f_hi), tuple(pieces), reads, writes))
+        b += m
+    return WelchPlan(cap, fpb, per, piece, carried, row_slots, tuple(ranges))
+
+
+WELCH_MAX = 2 ** 64 - 1         # group = SIZE_MAX: one column of all frames
+
+
+def welch_first_carried(W: int, pairs: int, cross: bool) -> int:
+    """the fewest frames whose one column (group = SIZE_MAX) a batch call carries: more blocks than a range holds"""
+    cap = welch_cap(W, pairs, cross)
+    per = cap // (WELCH_BLOCK + 1) if cap >= WELCH_BLOCK + 1 else 1
+    return WELCH_BLOCK * per + 1
+
+
+def welch_carried_route(routes, cross: bool = False):
+    """(frames, route) of the route with the fewest frames whose group = SIZE_MAX column is carried, kernel 11 left out (its rows go
+    through a scratch of their own: tests/test_gpu_psd.py carries a column there)"""
+    served = [r for r in routes if r.kernel != 11 and not (cross and r.channels == 1)]
+    return min(((welch_first_carried(r.W, r.pairs, cross), r) for r in served), key=lambda t: (t[0], t[1].W, t[1].channels, t[1].H))
+
+
+def welch_odd_seam(W: int, pairs: int, groups=range(1, 65)):
+    """(group, frames) of the first group whose batch call ends its first range on an odd frame, with the fewest frames that reach a
+    second range of at least two frames; None where no group of `groups` has one"""
+    cap = welch_cap(W, pairs, False)
+    for g in groups:
+        long = welch_ranges(W, pairs, False, cap + g + 3, g, True)  # (more frames than the workspace holds rows: at least two ranges)
+        seam = long.ranges[0].frames[1]
+        if len(long.ranges) >= 2 and seam % 2:
+            frames = seam + 3
+            assert welch_ranges(W, pairs, False, frames, g, True).ranges[0].frames[1] == seam
+            return g, frames
+    return None
+
+
 N_BANK_FILTERS = 263            # fbank_reference.edge_bank: the bank of the bounds sweep
 FUSED_BANK_KERNEL = 2           # info.stft_kernel of the 4096-point kernels, the only ones with a fused bank mode
 

@@ -423,6 +423,14 @@ def bank_kinds(r: es.Route) -> tuple:
     return ("fbank", "fbank_cross") if r.channels >= 2 else ("fbank",)
 
 
+def welch_kinds(r: es.Route) -> tuple:
+    """the Welch calls a forward case runs besides its other entry points: sgx_psd_batch at group 3 on every case and, with an (l, r)
+    pair, sgx_csd_batch.  No context runs them fused: they are always on the workspace route, so the split under test is that of the
+    rows (magnitudes, complex) the call reads -- forward_split of the same frames -- and the two kernels of sgx_psd.hip behind it take
+    nothing from the compute-unit count."""
+    return ("psd_3", "csd_3") if r.channels >= 2 else ("psd_3",)
+
+
 LAST_JOB_ONE_FRAME = "run_split: a last job without its second frame"
 
 

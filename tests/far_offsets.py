@@ -228,7 +228,7 @@ def hop_cases():
 
 
 # ---- part 4: outputs past 2^31 and 2^32 bytes --------------------------------------------------------------------------------------------
-OUTPUT_KINDS = ["stft", "f16", "complex", "render", "bands", "peak_2", "fbank", "fbank_cross"]
+OUTPUT_KINDS = ["stft", "f16", "complex", "render", "bands", "peak_2", "fbank", "fbank_cross", "psd_1", "csd_1"]
 OUTPUT_FAMILIES = [f for f in FAMILIES if f != "mixed_runtime_real"]   # (its run-time geometry and real-input mode: mixed_runtime, mixed_real)
 ROWS_DEFAULT, ROWS_MAX = 1024, 65536
 # the filterbank calls: the fused route (the 4096-point kernel on (l, r)) and one workspace family with a short hop.  The bank is the
@@ -250,6 +250,8 @@ def far_bank(M: int):
 
 
 def out_row_bytes(r: es.Route, kind: str, R: int) -> int:
+    if kind in WELCH_KINDS:
+        return welch_out_row_bytes(r, kind)
     if kind in BANK_KINDS:
         return r.pairs * BANK_FILTERS * (8 if kind == "fbank" else 16)
     if kind in ("stft", "f16", "complex"):
@@ -322,7 +324,8 @@ def output_case(family: str, kind: str) -> OutputCase:
 
 
 def output_cases():
-    return [output_case(f, k) for f in OUTPUT_FAMILIES for k in OUTPUT_KINDS if k not in BANK_KINDS or f in BANK_OUTPUT_FAMILIES]
+    return [output_case(f, k) for f in OUTPUT_FAMILIES for k in OUTPUT_KINDS
+            if (k not in BANK_KINDS or f in BANK_OUTPUT_FAMILIES) and (k not in WELCH_KINDS or f == WELCH_OUTPUT_FAMILIES[k])]
 
 
 # ---- what the method is for: one address computation, truncated --------------------------------------------------------------------------
@@ -500,3 +503,67 @@ class BankStageCase:
 
 
 BANK_STAGE_CASES = [BankStageCase("fbank_mags_w64", "fbank_mags", 64), BankStageCase("fbank_cross_spec_w64", "fbank_cross_spec", 64)]
+
+
+# ---- part 4, the Welch calls: sgx_psd_batch / sgx_csd_batch outputs and the stages' inputs and outputs past 2^32 bytes ------------------
+# The batch calls at group 1 (a column per frame: the most a frame of input can be made to write) on the two 4096-point families: the
+# real-input kernel of a mono stream, whose rows launches into the workspace take the automatic weighted deal (run_claim.hpp), and the
+# (l, r) kernel for the cross means.  Every range of psd_reduce passes `first_frame + f` on, up to the call's last frame.
+WELCH_KINDS = ("psd_1", "csd_1")
+WELCH_OUTPUT_FAMILIES = {"psd_1": "k1r", "csd_1": "k1_lr"}
+
+
+def welch_out_row_bytes(r: es.Route, kind: str) -> int:
+    return r.pairs * (r.W - 1) * (8 if kind == "psd_1" else 16)
+
+
+@dataclass(frozen=True)
+class WelchStageCase:
+    name: str
+    entry: str           # psd_mags, csd_spec
+    W: int               # the shortest rows a context of the generic kernel takes: the case is its offsets
+    groups: tuple = (1, 2)
+
+    @property
+    def id(self):
+        return self.name
+
+    @property
+    def M(self):
+        return self.W - 1
+
+    @property
+    def row_bytes(self):
+        """a frame's rows of the input and a column of the output alike (one pair)"""
+        return self.M * (8 if self.entry == "psd_mags" else 16)
+
+    @property
+    def frames(self):
+        """the input crosses 2^31 and 2^32 bytes with two rows to spare"""
+        return rows_for(self.row_bytes)
+
+    def cols(self, group: int) -> int:
+        return -(-self.frames // group)
+
+    def crossed(self, group: int):
+        """(input marks, output marks) a call at `group` crosses: group 1 all four; group 2 the input's two and byte 2^31 of the output"""
+        out_bytes = self.cols(group) * self.row_bytes
+        return [m for m in OUTPUT_MARKS if m < self.frames * self.row_bytes], [m for m in OUTPUT_MARKS if m < out_bytes]
+
+    def probes(self, group: int):
+        """the columns that hold a mark of the output, the columns whose frames hold a mark of the input, their neighbours, the first
+        and the last"""
+        n = self.cols(group)
+        out = {0, n - 1}
+        marks_in, marks_out = self.crossed(group)
+        for k in [m // self.row_bytes for m in marks_out] + [m // self.row_bytes // group for m in marks_in]:
+            out.update(c for c in (k - 1, k, k + 1) if 0 <= c < n)
+        return sorted(out)
+
+    def pieces(self, group: int):
+        """[(first column, columns)]: the input frames and the output columns of every piece below PIECE_LIMIT bytes"""
+        per = (PIECE_LIMIT - 1) // (self.row_bytes * group)
+        return [(a, min(per, self.cols(group) - a)) for a in range(0, self.cols(group), per)]
+
+
+WELCH_STAGE_CASES = [WelchStageCase("psd_mags_w64", "psd_mags", 64), WelchStageCase("csd_spec_w64", "csd_spec", 64)]

@@ -15,16 +15,17 @@ import edge_signals as es
 
 PEAK_GROUP = 3
 # the order of the calls: the batch entry points, then the calls that consume what those just made
-BATCH = ("stft", "f16", "complex", "render", "bands", "peak_3", "fbank", "fbank_cross")
-STAGE = ("render_mags", "magnitude_in", "render_bands", "checksum_add", "fbank_mags", "fbank_cross_spec")
+BATCH = ("stft", "f16", "complex", "render", "bands", "peak_3", "fbank", "fbank_cross", "psd_3", "csd_3")
+STAGE = ("render_mags", "magnitude_in", "render_bands", "checksum_add", "fbank_mags", "fbank_cross_spec", "psd_mags", "csd_spec")
 ENTRIES = BATCH + ("istft",) + STAGE
 SYMBOL = {"stft": "sgx_stft_batch", "f16": "sgx_stft_batch_f16", "complex": "sgx_stft_batch_complex", "render": "sgx_render_batch",
           "bands": "sgx_bands_batch", "peak_3": "sgx_bands_peak_batch", "istft": "sgx_istft_batch", "render_mags": "sgx_render_mags",
           "magnitude_in": "sgx_magnitude_in", "render_bands": "sgx_render_bands", "checksum_add": "sgx_checksum_add",
-          "fbank": "sgx_fbank_batch", "fbank_cross": "sgx_fbank_cross_batch", "fbank_mags": "sgx_fbank_mags", "fbank_cross_spec": "sgx_fbank_cross_spec"}
+          "fbank": "sgx_fbank_batch", "fbank_cross": "sgx_fbank_cross_batch", "fbank_mags": "sgx_fbank_mags", "fbank_cross_spec": "sgx_fbank_cross_spec",
+          "psd_3": "sgx_psd_batch", "csd_3": "sgx_csd_batch", "psd_mags": "sgx_psd_mags", "csd_spec": "sgx_csd_spec"}
 # what a call reads that another call of the same run wrote: a wrong input makes a wrong output whatever the call itself does
 READS = {"istft": "complex", "render_mags": "stft", "magnitude_in": "stft", "render_bands": "bands", "checksum_add": "stft",
-         "fbank_mags": "stft", "fbank_cross_spec": "complex"}
+         "fbank_mags": "stft", "fbank_cross_spec": "complex", "psd_mags": "stft", "csd_spec": "complex"}
 # entry points that wait on the host in their steady state, with the reason (include/sgx.h's conventions name them): none
 HOST_WAITS: dict = {}
 
@@ -53,8 +54,19 @@ def fbank_cross_served(r: es.Route) -> bool:
     return r.channels >= 2
 
 
+def csd_served(r: es.Route) -> bool:
+    """sgx_csd_batch: a context with an (l, r) pair, as sgx_fbank_cross_batch; sgx_csd_spec serves every context"""
+    return r.channels >= 2
+
+
+def psd_fused(r: es.Route) -> int:
+    """sgx_psd_fused and sgx_csd_fused: no context runs a fused Welch mode in this build"""
+    return 0
+
+
 def entries_served(r: es.Route) -> tuple:
-    return tuple(e for e in ENTRIES if (e != "istft" or istft_served(r)) and (e != "fbank_cross" or fbank_cross_served(r)))
+    return tuple(e for e in ENTRIES if (e != "istft" or istft_served(r)) and (e != "fbank_cross" or fbank_cross_served(r))
+                 and (e != "csd_3" or csd_served(r)))
 
 
 @dataclass(frozen=True)
@@ -79,7 +91,8 @@ def by_row() -> dict:
 
 # ---- the helper passes -------------------------------------------------------------------------------------------------------------------
 HELPERS = ("deinterleave", "k16_plane", "to_half", "workspace", "workspace_render", "workspace_magnitude_in", "workspace_peak",
-           "peak_combine", "ladder", "large_passes", "inverse", "workspace_fbank", "workspace_fbank_cross")
+           "peak_combine", "ladder", "large_passes", "inverse", "workspace_fbank", "workspace_fbank_cross", "workspace_psd_blocks",
+           "workspace_psd_combine")
 
 
 def family(r: es.Route) -> str:
@@ -131,6 +144,13 @@ def helpers(r: es.Route, entry: str, render_fused: bool, bands_fused: bool) -> s
         if ba.fbank_fused(r, cross=entry == "fbank_cross"):
             return rows
         return rows | {"workspace", "workspace_" + entry}
+    if entry in ("psd_3", "csd_3"):
+        # the rows (magnitudes, complex) into the front of the workspace behind the rows' own helpers, then the two kernels of sgx_psd.hip:
+        # block partials behind the rows, the float64 chain over them
+        assert not psd_fused(r)
+        return rows | {"workspace", "workspace_psd_blocks", "workspace_psd_combine"}
+    if entry in ("psd_mags", "csd_spec"):
+        return {"workspace_psd_blocks", "workspace_psd_combine"}     # the same two kernels over the caller's rows
     return set()
 
 
@@ -184,6 +204,24 @@ PIXEL_CASES = [
     PixelCase("magnitude_in_w64", "magnitude_in_kernel<true>", "magnitude_in", 64, 126),
     PixelCase("magnitude_in_w20481", "magnitude_in_kernel<false>", "magnitude_in", 20481, 1024, large=True, n_ranges=20480),
 ]
+
+@dataclass(frozen=True)
+class WelchCase:
+    name: str
+    W: int
+    H: int
+    channels: int
+    frames: int
+    group: int
+    cross: bool
+
+
+# a context where bounds_arena.welch_ranges says the call is both carried (the float64 sums of its one column wait in the context's carry
+# row, grown on the stream by the call under test) and pieced (a block's rows a few frames at a time, the later pieces resumed):
+# tests/test_gpu_psd.py's W 32768 context of 64 channels
+WELCH_CASES = [WelchCase("psd_w32768_ch64", 32768, 8192, 64, 36, ba.WELCH_MAX, False),
+               WelchCase("csd_w32768_ch64", 32768, 8192, 64, 36, ba.WELCH_MAX, True)]
+
 
 # rebinding a busy context: (name, engine keywords, the wrapper's method)
 REBIND_CASES = [

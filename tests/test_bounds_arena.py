@@ -127,3 +127,131 @@ def test_peak_chunk_loop():
 ])
 def test_fused_peak_run(n, group, n_cu, fpj, want):
     assert ba.fused_peak_run(n, group, n_cu, fpj) == want
+
+
+# ---- the ranges of the Welch calls (bounds_arena.welch_ranges: a restatement of psd_reduce) ---------------------------------------------
+def test_welch_row_counts_of_test_gpu_psd():
+    # the rows tests/test_gpu_psd.py counts on: 8 channels at W 2048: 4 * 2047 * 8 = 65504 bytes, 201326592 / 65504 = 3073.5
+    assert ba.welch_cap(2048, 4, False) == 3073
+    # 8 channels at W 19200: 4 * 19199 * 8 = 614368 bytes: 327.7 rows, 163.8 complex rows
+    assert (ba.welch_cap(19200, 4, False), ba.welch_cap(19200, 4, True)) == (327, 163)
+    # 64 channels at W 32768: 32 * 32767 * 8 = 8388352 bytes, 64 bytes short of 8 MiB: 24 rows and 12 complex rows (not 22 and 11: what
+    # the test needs of them, fewer than a block of 32 rows and its partial, holds of both)
+    assert (ba.welch_cap(32768, 32, False), ba.welch_cap(32768, 32, True)) == (24, 12)
+    # a row larger than the workspace: no row fits
+    assert ba.welch_cap(2048, 16384, False) == 0 and ba.welch_row_bytes(2048, 16384, False) > ba.WORKSPACE_BYTES
+
+
+def test_welch_plan_by_hand():
+    # W 2048 with 8 channels at group 3: blocks of 3 frames, 3073 // 4 = 768 blocks a range, 2304 rows in front of 768 partial rows
+    p = ba.welch_ranges(2048, 4, False, 2400, 3, True)
+    assert (p.cap, p.fpb, p.per, p.piece, p.carried, p.row_slots, p.workspace_rows) == (3073, 3, 768, 0, False, 2304, 3072)
+    assert [(r.blocks, r.frames) for r in p.ranges] == [((0, 768), (0, 2304)), ((768, 800), (2304, 2400))]
+    assert all(r.pieces == ((r.frames[0], r.frames[1], False),) and not r.reads_carry and not r.writes_carry for r in p.ranges)
+    # group 1: 3073 // 2 = 1536 frames a range
+    assert [r.frames for r in ba.welch_ranges(2048, 4, False, 2400, 1, True).ranges] == [(0, 1536), (1536, 2400)]
+    # the stage over the caller's rows: no row slots, the whole workspace partial rows
+    q = ba.welch_ranges(2048, 4, False, 2400, 3, False)
+    assert (q.row_slots, q.per, len(q.ranges)) == (0, 800, 1)
+    # W 19200 with 8 channels, 400 frames: 327 // 33 = 9 blocks a range.  group 33 (2 blocks a column): 8 blocks = 4 columns a range;
+    # one column of 400 frames has 13 blocks: carried over two ranges
+    p = ba.welch_ranges(19200, 4, False, 400, 33, True)
+    assert (p.per, p.carried, p.row_slots) == (8, False, 256) and [r.frames for r in p.ranges] == [(0, 132), (132, 264), (264, 396), (396, 400)]
+    p = ba.welch_ranges(19200, 4, False, 400, ba.WELCH_MAX, True)
+    assert (p.per, p.carried) == (9, True)
+    assert [(r.frames, r.reads_carry, r.writes_carry) for r in p.ranges] == [((0, 288), False, True), ((288, 400), True, False)]
+    # W 32768 with 64 channels, 36 frames: 24 rows: 23 frames a piece beside one partial row
+    p = ba.welch_ranges(32768, 32, False, 36, 33, True)
+    assert (p.cap, p.per, p.piece, p.carried, p.row_slots, p.workspace_rows) == (24, 1, 23, True, 23, 24)
+    assert [(r.frames, r.pieces, r.reads_carry, r.writes_carry) for r in p.ranges] == [
+        ((0, 32), ((0, 23, False), (23, 32, True)), False, True), ((32, 33), ((32, 33, False),), True, False),
+        ((33, 36), ((33, 36, False),), False, False)]
+    # no row fits: a frame a piece, two rows of workspace all the same
+    p = ba.welch_ranges(2048, 16384, False, 3, 2, True)
+    assert (p.cap, p.per, p.piece, p.row_slots, p.workspace_rows) == (0, 1, 1, 1, 2)
+    assert [r.pieces for r in p.ranges] == [((0, 1, False), (1, 2, True)), ((2, 3, False),)]
+
+
+@pytest.mark.parametrize("cap", [0, 1, 2, 3, 5, 32, 33, 34, 66, 67, 100, 1000])
+@pytest.mark.parametrize("own_rows", [True, False])
+def test_welch_ranges_partition_the_call(cap, own_rows):
+    """the blocks of all ranges partition Geometry.blocks() and their frames [0, n); the pieces partition a range's frames and fit the row
+    slots; the partial rows lie behind the row slots; the carry row is written before it is read, by the same column; and the whole is
+    psd_reference.plan's (written from the same source at another time)"""
+    import psd_reference as ref
+    for n in (1, 2, 31, 32, 33, 64, 65, 100, 333):
+        for group in (1, 2, 5, 31, 32, 33, 64, 65, 70, n, n + 10, ba.WELCH_MAX):
+            p = ba.welch_ranges(64, 1, False, n, group, own_rows, cap=cap)
+            geo = ref.Geometry(n, group)
+            what = (cap, own_rows, n, group)
+            assert p.ranges[0].blocks[0] == 0 and p.ranges[-1].blocks[1] == geo.blocks(), what
+            assert p.ranges[0].frames[0] == 0 and p.ranges[-1].frames[1] == n, what
+            holds_carry = False
+            for a, b in zip(p.ranges, p.ranges[1:] + (None,)):
+                assert a.blocks[0] < a.blocks[1] <= a.blocks[0] + p.per and a.frames[0] < a.frames[1], what
+                if b is not None:
+                    assert a.blocks[1] == b.blocks[0] and a.frames[1] == b.frames[0], what
+                assert a.frames == (geo.block_first(a.blocks[0]), geo.block_end(a.blocks[1] - 1)), what
+                assert a.pieces[0][0] == a.frames[0] and a.pieces[-1][1] == a.frames[1], what
+                assert all(x[1] == y[0] for x, y in zip(a.pieces, a.pieces[1:])), what
+                assert [x[2] for x in a.pieces] == [False] + [True] * (len(a.pieces) - 1), what
+                if own_rows:
+                    assert all(x[1] - x[0] <= p.row_slots for x in a.pieces), (what, "a rows launch writes into the partial rows")
+                else:
+                    assert len(a.pieces) == 1, what
+                j0, j1 = a.blocks[0] // geo.bpc, (a.blocks[1] - 1) // geo.bpc
+                if p.carried:
+                    assert j0 == j1, (what, "a carried range holds blocks of two columns")
+                    assert a.reads_carry == (a.blocks[0] != j0 * geo.bpc) and a.writes_carry == (a.blocks[1] != geo.column_block_end(j0)), what
+                else:
+                    assert a.blocks[0] == j0 * geo.bpc and a.blocks[1] == geo.column_block_end(j1), (what, "a range ends inside a column")
+                    assert not a.reads_carry and not a.writes_carry, what
+                assert a.reads_carry == holds_carry, (what, "the carry row is read before it was written, or left unread")
+                holds_carry = a.writes_carry
+            assert not holds_carry, what
+            if own_rows:
+                assert p.workspace_rows <= max(cap, 2), (what, "more workspace than the bound")
+            other, (slots, per, carried) = ref.plan(n, group, cap, own_rows)
+            assert (slots, per, carried) == (p.row_slots, p.per, p.carried), what
+            assert other == [(r.blocks[0], r.blocks[1] - r.blocks[0], [(f, e - f, res) for f, e, res in r.pieces]) for r in p.ranges], what
+
+
+def test_welch_cases_of_the_gpu_tests():
+    """every case the GPU tests name shows the property it is there for"""
+    import channel_counts as cc
+    # tests/test_gpu_bounds.py, part E: a carried column on a family that is not kernel 11 -- the fewest frames of the route table
+    for cross, frames in ((False, 737), (True, 353)):
+        n, r = ba.welch_carried_route(es.ROUTES, cross)
+        assert (n, r.name) == (frames, "k16_ch8_h300")
+        p = ba.welch_ranges(r.W, r.pairs, cross, n, ba.WELCH_MAX, True)
+        assert p.carried and len(p.ranges) == 2 and p.ranges[0].writes_carry and p.ranges[1].reads_carry and not p.piece
+        assert not ba.welch_ranges(r.W, r.pairs, cross, n - 1, ba.WELCH_MAX, True).carried
+    # ... and a seam of two ranges at an odd frame of a paired mono W 2048 context: group 1, 12294 // 2 = 6147 frames a range
+    assert ba.welch_odd_seam(2048, 1) == (1, 6150)
+    p = ba.welch_ranges(2048, 1, False, 6150, 1, True)
+    assert [r.frames for r in p.ranges] == [(0, 6147), (6147, 6150)] and not p.carried
+    # tests/test_gpu_bounds.py, part C: no group is carried on the two chunk rows at their 300 and 70 frames (a carried column needs
+    # more blocks than a range holds: 32 * (cap // 33) + 1 frames and more)
+    for name, frames in (("large_w6001_chunks", 300), ("large_w16384_ch4_chunks", 70)):
+        r = es.ROUTE[name]
+        assert max(9, r.min_frames) == frames
+        for cross in (False, True):
+            assert ba.welch_first_carried(r.W, r.pairs, cross) > frames
+            for g in list(range(1, frames + 6)) + [ba.WELCH_MAX]:
+                assert not ba.welch_ranges(r.W, r.pairs, cross, frames, g, True).carried, (name, cross, g)
+    # tests/test_gpu_stream_routes.py: W 32768 with 64 channels, 36 frames, one column: carried and pieced, the second piece resumed
+    for cross in (False, True):
+        p = ba.welch_ranges(32768, 32, cross, 36, ba.WELCH_MAX, True)
+        assert p.carried and p.piece and p.resumed and len(p.ranges) == 2
+        assert p.ranges[0].writes_carry and p.ranges[1].reads_carry and len(p.ranges[0].pieces) >= 2
+    # tests/test_gpu_psd.py: at least two ranges of whole columns at W 2048 with 8 channels
+    p = ba.welch_ranges(2048, 4, False, 2400, 3, True)
+    assert len(p.ranges) >= 2 and not p.carried and all(r.frames[0] % 3 == 0 for r in p.ranges)
+    # tests/test_gpu_channel_counts.py: the rows of 32 768 channels: none, or fewer than a block and its partial
+    caps = {c.name: (ba.welch_cap(c.W, c.pairs, False), ba.welch_cap(c.W, c.pairs, True)) for c in cc.CAP_ROWS}
+    assert caps == {"generic_w64_cap": (24, 12), "bluestein_w23_cap": (69, 34), "mixed_w735_runtime_cap": (2, 1), "k1_h256_cap": (0, 0),
+                    "k16_h512_cap": (0, 0)}
+    for c in cc.CAP_ROWS:
+        for cross in (False, True):
+            p = ba.welch_ranges(c.W, c.pairs, cross, c.frames, ba.WELCH_MAX, True)
+            assert (p.piece == 1) == (p.cap <= 2) and p.workspace_rows <= max(p.cap, 2)

@@ -3,6 +3,7 @@ rests on (no GPU).  tests/test_gpu_channel_counts.py then holds every family to 
 import numpy as np
 import pytest
 
+import bounds_arena as ba
 import channel_counts as cn
 import edge_signals as es
 import oracle
@@ -174,3 +175,29 @@ def test_inverse_ratio_is_check_definition(W, H, channels):
     want = ti.check_definition(got, ref, env, W, H, win)
     assert want > 0.1
     assert cn.inverse_ratio(torch, got, ref, env, W, H, win, ti.DEFINITION_TOL) == pytest.approx(want, rel=1e-12)
+
+
+def test_the_welch_ranges_of_the_table():
+    """what tests/test_gpu_channel_counts.py's Welch checks meet, by bounds_arena.welch_ranges (a restatement of psd_reduce): the 6-, 12-
+    and 64-channel rows take every call in one range of whole columns; at 32 768 channels the workspace holds no row (W 2048, W 8192: a
+    frame per piece, two rows of workspace all the same), fewer than a block of 32 and its partial (W 735, W 64) or two blocks (W 23)"""
+    for c in cn.TABLE:
+        for cross in (False, True):
+            for group in sorted({1, 2, 4, c.frames}):
+                plan = ba.welch_ranges(c.W, c.pairs, cross, c.frames, group, True)
+                assert len(plan.ranges) == 1 and not plan.carried and not plan.piece and plan.cap >= 33, (c.name, cross, group)
+    caps = {c.name: (ba.welch_cap(c.W, c.pairs, False), ba.welch_cap(c.W, c.pairs, True)) for c in cn.CAP_ROWS}
+    assert caps == {"generic_w64_cap": (24, 12), "bluestein_w23_cap": (69, 34), "mixed_w735_runtime_cap": (2, 1), "k1_h256_cap": (0, 0),
+                    "k16_h512_cap": (0, 0)}
+    for c in cn.CAP_ROWS:
+        assert ba.welch_row_bytes(c.W, c.pairs, False) == c.pairs * (c.W - 1) * 8
+        for cross in (False, True):
+            for group in (ba.WELCH_MAX, 2):
+                plan = ba.welch_ranges(c.W, c.pairs, cross, c.frames, group, True)
+                assert plan.workspace_rows <= max(plan.cap, 2), (c.name, cross, group)
+                if plan.cap <= 2 and c.frames == 2:      # the block of two frames in two pieces, the second resumed
+                    assert plan.piece == 1 and plan.resumed and [len(r.pieces) for r in plan.ranges] == [2], (c.name, cross, group)
+                if plan.cap == 0:
+                    assert plan.piece == 1 and plan.row_slots == 1 and plan.per == 1
+    # a row larger than the whole workspace: 16 384 pairs of 2047 bins are 268 MB
+    assert ba.welch_row_bytes(2048, cn.CAP // 2, False) > ba.WORKSPACE_BYTES

@@ -13,6 +13,7 @@ import itertools
 
 import pytest
 
+import bounds_arena as ba
 import cu_counts as cc
 
 N_CU = list(range(1, 41)) + [255, 256]
@@ -131,6 +132,24 @@ def test_the_bank_kinds_reach_a_last_job_without_its_second_frame():
     # 75 frames are 38 jobs, the last of one frame; the sub-range from frame 3 is 72 frames: no such job.  At limits 1 .. 8 the last workgroup
     # runs that job behind others
     assert {limit for name, limit in reached if name == "k1r_h256"} >= {1, 2, 3, 5, 8}
+
+
+def test_the_welch_kinds_ride_every_forward_case():
+    """sgx_psd_batch at group 3 behind the rows of every forward case, sgx_csd_batch wherever the case has an (l, r) pair: the split under
+    test is the rows' own (proved above for every case and limit), and at group 3 every case has a ragged last column or several columns"""
+    forward = [c for c in cc.TABLE if c.kind == "forward"]
+    assert forward
+    for c in forward:
+        r = cc.route_of(c)
+        assert cc.welch_kinds(r) == (("psd_3", "csd_3") if r.channels >= 2 else ("psd_3",)), c.name
+        for limit in cc.LIMITS:
+            for first, n in cc.forward_calls(c, limit):
+                assert n >= 4, (c.name, limit, first, n)          # at least two columns of three frames
+                # one range of whole columns at these sizes: the seams of the ranges are tests/test_gpu_psd.py's and test_gpu_bounds.py's
+                for cross in (False, True)[:len(cc.welch_kinds(r))]:
+                    plan = ba.welch_ranges(r.W, r.pairs, cross, n, 3, True)
+                    assert not plan.carried and not plan.piece and len(plan.ranges) == 1, (c.name, limit, first, n)
+    assert {len(cc.welch_kinds(cc.route_of(c))) for c in forward} == {1, 2}
 
 
 @pytest.mark.parametrize("n_cu", N_CU)

@@ -118,9 +118,22 @@ def test_tables_reach_every_row_and_family():
     assert {c.family for c in HOPS} == set(named) and len(HOPS) == len(named) * 4 * 2
     assert {c.family for c in OUTPUTS} == set(named) - {"mixed_runtime_real"}
     # every family through every kind but the filterbank calls; those on the fused family and on one workspace family with a short hop
-    assert fo.OUTPUT_KINDS[-2:] == list(fo.BANK_KINDS) == ["fbank", "fbank_cross"]
-    assert {(c.family, c.kind) for c in OUTPUTS} == ({(f, k) for f in fo.OUTPUT_FAMILIES for k in fo.OUTPUT_KINDS[:-2]}
-                                                     | {(f, k) for f in ("k1_lr", "k48_lr") for k in fo.BANK_KINDS})
+    # ... and the Welch calls at group 1 on the two 4096-point families: the mono rows (the weighted deal of their launches) and (l, r)
+    assert fo.OUTPUT_KINDS[-4:-2] == list(fo.BANK_KINDS) == ["fbank", "fbank_cross"]
+    assert fo.OUTPUT_KINDS[-2:] == list(fo.WELCH_KINDS) == ["psd_1", "csd_1"]
+    assert {(c.family, c.kind) for c in OUTPUTS} == ({(f, k) for f in fo.OUTPUT_FAMILIES for k in fo.OUTPUT_KINDS[:-4]}
+                                                     | {(f, k) for f in ("k1_lr", "k48_lr") for k in fo.BANK_KINDS}
+                                                     | {("k1r", "psd_1"), ("k1_lr", "csd_1")})
+    welch = {(c.family, c.kind): c for c in OUTPUTS if c.kind in fo.WELCH_KINDS}
+    assert {k: (c.row_bytes, c.rows, c.group, c.R) for k, c in welch.items()} == {
+        ("k1r", "psd_1"): (2047 * 8, 262275, 1, 1024),           # 2^32 / 16376 = 262 272.5 rows, and two
+        ("k1_lr", "csd_1"): (2047 * 16, 131139, 1, 1024)}        # 2^32 / 32752 = 131 136.3 rows, and two
+    for (family, kind), c in welch.items():
+        # hundreds of ranges at the mono rows, the frame passed to the rows launches up to the call's last
+        plan = ba.welch_ranges(c.route.W, 1, kind == "csd_1", c.frames, 1, True)
+        assert len(plan.ranges) == {"psd_1": 43, "csd_1": 43}[kind] and not plan.carried and not plan.piece
+        assert plan.ranges[-1].frames[1] == c.frames and plan.ranges[1].frames[0] == {"psd_1": 6147, "csd_1": 3073}[kind]
+        assert fo.family_route(family).kernel == 2 and fo.family_route(family).channels == (1 if kind == "psd_1" else 2)
     banks = {(c.family, c.kind): c for c in OUTPUTS if c.kind in fo.BANK_KINDS}
     assert {k: (c.row_bytes, c.rows) for k, c in banks.items()} == {
         ("k1_lr", "fbank"): (8192, 524290), ("k48_lr", "fbank"): (8192, 524290),                   # 2^32 / 8 KiB = 524288 rows, and two
@@ -281,6 +294,38 @@ def test_bank_stage_case(case):
     for M in (2047, 2399):                                   # the banks of the batch cases: within the fused size, bins all over the column
         f, c, w = fo.far_bank(M)                             # (bin M - 1, put in by hand, may repeat one of the scattered ones)
         assert len(set(f.tolist())) >= 1023 and int(f.max()) == M - 1 and int(c.sum()) == 1024 <= 16384
+
+
+@pytest.mark.parametrize("case", fo.WELCH_STAGE_CASES, ids=lambda c: c.id)
+def test_welch_stage_case(case):
+    """sgx_psd_mags / sgx_csd_spec: the frame index times the row's elements (the block kernel's `f * elems + e`) and the column index times
+    them (the combine's `j * elems + e`) pass bytes 2^31 and 2^32; the rows are as short as a context takes"""
+    assert case.W == 64 and case.groups == (1, 2)
+    rb = case.row_bytes
+    assert rb == {"psd_mags": 63 * 8, "csd_spec": 63 * 16}[case.entry]
+    F = case.frames
+    assert (1 << 32) + 2 * rb <= F * rb < (1 << 32) + 3 * rb
+    assert 2 * F * rb <= fo.CASE_CAP_BYTES
+    for group in case.groups:
+        cols = case.cols(group)
+        marks_in, marks_out = case.crossed(group)
+        assert marks_in == fo.OUTPUT_MARKS and marks_out == (fo.OUTPUT_MARKS if group == 1 else fo.OUTPUT_MARKS[:1])
+        probes = set(case.probes(group))
+        assert {0, cols - 1} <= probes and max(probes) == cols - 1 and min(probes) == 0
+        for m in marks_out:
+            k = m // rb
+            assert k * rb <= m < (k + 1) * rb and {k - 1, k, k + 1} <= probes and k + 1 <= cols - 1
+        for m in marks_in:       # the column whose frames hold the mark of the input
+            f = m // rb
+            assert f * rb <= m < (f + 1) * rb and f + 1 <= F - 1 and {f // group - 1, f // group, f // group + 1} & probes >= {f // group - 1, f // group}
+        if group == 2:           # frame 2 j + 1 of the column at the output's mark 2^31 lies past the input's 2^32
+            k = marks_out[0] // rb
+            assert (2 * k + 1) * rb > 1 << 32 and F % 2 == 1                       # and the last column is one frame
+        at = 0
+        for a, n in case.pieces(group):
+            assert a == at and n >= 1 and n * group * rb < fo.PIECE_LIMIT
+            at += n
+        assert at == cols and len(case.pieces(group)) >= 3
 
 
 def test_pixel_cases_reach_every_body():

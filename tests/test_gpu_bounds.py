@@ -14,6 +14,11 @@ The filterbank calls (sgx_fbank_batch, sgx_fbank_cross_batch; the stages sgx_fba
 it with one bank per context, fbank_reference.edge_bank at power 2: their baselines equal the stage over the baseline's own rows and, on
 three frames, the header's definition as tests/fbank_reference.py computes it, bit for bit.  sgx_fbank_cross_batch asks for 16 bytes: its
 8-modulo-16 variant asserts the refusal and an untouched arena.
+The Welch calls (sgx_psd_batch, sgx_csd_batch at groups 1, 3 and n + 5; the stages sgx_psd_mags, sgx_csd_spec under D) run through all of
+it as well: their baseline is the header's sum order (tests/psd_reference.py) over the baseline's own rows of the requested sub-range,
+bit for bit, the columns counted from the sub-range's first frame; sgx_csd_batch asks for 16 bytes like the cross sums.  Under E the
+seams of psd_reduce's ranges that bounds_arena.welch_ranges selects: a carried column off kernel 11, a seam on an odd frame of a paired
+context.
 All of it is bit for bit against a clean baseline (the whole stream through a fresh engine on fresh, exact-size tensors), and the
 baseline's rows are held to the float64 truth on three frames at the bound the project holds white noise to.  No skips: a (row, entry
 point) pair is left out only through EXPECTED_UNSUPPORTED, and the library must refuse exactly those.  Run with -m gpu on an MI355X."""
@@ -27,6 +32,7 @@ import bounds_arena as ba
 import edge_signals as es
 import fbank_reference as fr
 import oracle
+import psd_reference as pr
 from conftest import chirpz_bound, mags_error
 from spectrogram_rs_amd import SpectrogramEngine, _lib
 from test_gpu_peak import amax_groups, same
@@ -35,12 +41,15 @@ pytestmark = pytest.mark.gpu
 
 ROWS = [r.name for r in es.ROUTES]
 VARIANTS = ["aligned", "odd"]
-KINDS = ["stft", "f16", "complex", "render", "bands", "peak_1", "peak_3", "peak_n", "peak_n5", "fbank", "fbank_cross"]
+WELCH_KINDS = ["psd_1", "psd_3", "psd_n5", "csd_3", "csd_n5"]   # the groups of the peak kinds: 1, 3, and n + 5 for one short column
+KINDS = ["stft", "f16", "complex", "render", "bands", "peak_1", "peak_3", "peak_n", "peak_n5", "fbank", "fbank_cross"] + WELCH_KINDS
 ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "istft": "f32", "magnitude_in": "f32",
-        "render_mags": "u8", "render_bands": "u8", "fbank": "f32", "fbank_cross": "f32", "fbank_mags": "f32", "fbank_cross_spec": "f32"}
+        "render_mags": "u8", "render_bands": "u8", "fbank": "f32", "fbank_cross": "f32", "fbank_mags": "f32", "fbank_cross_spec": "f32",
+        "psd_1": "f32", "psd_3": "f32", "psd_n5": "f32", "csd_3": "f32", "csd_n5": "f32", "psd_mags": "f32", "csd_spec": "f32"}
 # the only (row, entry point) pairs this file leaves out: the library must answer SGX_ERR_UNSUPPORTED / istft_supported() == 0 for
 # exactly these (test_expected_unsupported), any other refusal fails the test that meets it
-EXPECTED_UNSUPPORTED = {(r.name, "istft") for r in es.ROUTES if r.kernel == 11} | {(r.name, "fbank_cross") for r in es.ROUTES if r.channels == 1}
+EXPECTED_UNSUPPORTED = ({(r.name, "istft") for r in es.ROUTES if r.kernel == 11} | {(r.name, "fbank_cross") for r in es.ROUTES if r.channels == 1}
+                        | {(r.name, k) for r in es.ROUTES if r.channels == 1 for k in WELCH_KINDS if k.startswith("csd")})
 INVERSE_ROWS = [n for n in ROWS if (n, "istft") not in EXPECTED_UNSUPPORTED]
 SERVED = [(n, k) for k in KINDS for n in ROWS if (n, k) not in EXPECTED_UNSUPPORTED]      # (row, kind) of the sweeps over KINDS
 
@@ -86,12 +95,17 @@ def dtype_of(torch, kind):
     return {"f32": torch.float32, "f16": torch.float16, "u8": torch.uint8}[elem_of(kind)]
 
 
+def welch(kind):
+    """"psd" or "csd" of a Welch kind, None of any other"""
+    return kind[:3] if kind in WELCH_KINDS else None
+
+
 def group_of(kind, n):
-    return {"peak_1": 1, "peak_3": 3, "peak_n": n, "peak_n5": n + 5}[kind]
+    return {"1": 1, "3": 3, "n": n, "n5": n + 5}[kind.split("_")[1]]
 
 
 def rows_of(kind, n):
-    return -(-n // group_of(kind, n)) if kind.startswith("peak") else n
+    return -(-n // group_of(kind, n)) if kind.startswith("peak") or welch(kind) else n
 
 
 def bank_of(eng):
@@ -107,6 +121,8 @@ def row_bytes(eng, kind):
         return eng.pairs * ba.N_BANK_FILTERS * (8 if kind == "fbank" else 16)
     if kind in ("stft", "f16", "complex"):
         return eng.pairs * eng.M * {"stft": 8, "f16": 4, "complex": 16}[kind]
+    if welch(kind) or kind in ("psd_mags", "csd_spec"):
+        return eng.pairs * eng.M * (8 if kind.startswith("psd") else 16)
     return eng.pairs * eng.R * (4 if kind == "render" else 8)
 
 
@@ -125,6 +141,8 @@ def run(eng, kind, dev, first, n, out=None):
         return bank_of(eng).batch(dev, first, n, out=out)
     if kind == "fbank_cross":
         return bank_of(eng).cross_batch(dev, first, n, out=out)
+    if welch(kind):
+        return (eng.psd_batch if welch(kind) == "psd" else eng.csd_batch)(dev, group_of(kind, n), first, n, out=out)
     return eng.bands_peak_batch(dev, group_of(kind, n), first, n, out=out)
 
 
@@ -191,7 +209,8 @@ def case(torch, name):
     N = (F - 1) * H + W
     pcm = (oracle.white_noise(N * Cn, seed=0x5EED0900 + ROWS.index(name)) * np.float32(0.25)).reshape(N, Cn)
     dev = to_dev(torch, r, pcm)
-    cs = SimpleNamespace(r=r, eng=eng, F=F, N=N, pcm=pcm, dev=dev, base={}, flat={})
+    cs = SimpleNamespace(r=r, eng=eng, F=F, N=N, pcm=pcm, dev=dev, base={}, flat={}, terms={}, welch={})
+    assert eng.psd_fused == 0 and eng.csd_fused == 0
     fb = bank_of(eng)
     assert (fb.fused, fb.cross_fused) == (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)), (name, fb.fused, fb.cross_fused)
     for kind in ("stft", "f16", "complex", "render", "bands", "fbank", "fbank_cross"):
@@ -269,10 +288,32 @@ def want_peak(cs, kind, first, n):
     return bands if g == 1 else amax_groups(bands, g)
 
 
+def want_welch(torch, cs, kind, first, n):
+    """The Welch kinds' baseline: the header's sum order (tests/psd_reference.py) over the baseline's own stft / complex rows of frames
+    [first, first + n), the columns counted from `first`: flat int32 words on the device.  The summands of a row are formed once and the
+    means of a (kind, first, n) once, on the host; neither is written to afterwards."""
+    which = welch(kind)
+    if which not in cs.terms:
+        if which == "psd":
+            cs.terms[which] = pr.psd_terms(cs.base["stft"].cpu().numpy())
+        else:
+            cs.terms[which] = pr.csd_terms(torch.view_as_real(cs.base["complex"]).cpu().numpy())
+        cs.terms[which].setflags(write=False)
+    key = (kind, first, n)
+    if key not in cs.welch:
+        cs.welch[key] = pr.welch_mean(cs.terms[which][first:first + n], group_of(kind, n)).reshape(-1).view(np.int32)
+        cs.welch[key].setflags(write=False)
+    return torch.tensor(cs.welch[key], device="cuda")     # (a copy: the cached means stay read-only)
+
+
 def check_result(torch, cs, kind, first, n, got_words, what):
     """got_words (flat int32) against the baseline's rows [first, first + n): bit for bit; peak columns with test_gpu_peak.same against
-    amax_groups of the baseline bands"""
-    if kind.startswith("peak"):
+    amax_groups of the baseline bands; the Welch kinds against want_welch"""
+    if welch(kind):
+        want = want_welch(torch, cs, kind, first, n)
+        assert got_words.numel() == want.numel() == rows_of(kind, n) * row_bytes(cs.eng, kind) // 4, what
+        assert torch.equal(got_words, want), what
+    elif kind.startswith("peak"):
         want = want_peak(cs, kind, first, n)
         assert got_words.numel() == want.numel(), what
         assert same(got_words.view(torch.float32), want), what
@@ -288,10 +329,24 @@ def check_arena(arena, prefill, what):
 
 def test_expected_unsupported(torch_cuda):
     torch = torch_cuda
-    assert {k for _, k in EXPECTED_UNSUPPORTED} == {"istft", "fbank_cross"}
-    assert {n for n, k in EXPECTED_UNSUPPORTED if k == "fbank_cross"} == {r.name for r in es.ROUTES if r.channels == 1}
+    assert {k for _, k in EXPECTED_UNSUPPORTED} == {"istft", "fbank_cross", "csd_3", "csd_n5"}
+    mono = {r.name for r in es.ROUTES if r.channels == 1}
+    assert all({n for n, k in EXPECTED_UNSUPPORTED if k == kind} == mono for kind in ("fbank_cross", "csd_3", "csd_n5"))
     for name in ROWS:
         cs = case(torch, name)
+        for kind in ("csd_3", "csd_n5"):
+            if (name, kind) not in EXPECTED_UNSUPPORTED:
+                assert kind in kinds_of(name) and "complex" in cs.base, name
+                continue
+            # a mono context has no (l, r) pair: refused, the count zero, the buffer as it was
+            out = torch.zeros(cs.F * row_bytes(cs.eng, kind) // 4, dtype=torch.float32, device="cuda")
+            got = C.c_size_t(99)
+            rc = cs.eng._lib.sgx_csd_batch(cs.eng._ctx, C.c_void_p(cs.dev.data_ptr()), cs.N, 0, cs.F, group_of(kind, cs.F), C.c_void_p(out.data_ptr()),
+                                           C.byref(got))
+            assert rc == _lib.SGX_ERR_UNSUPPORTED and got.value == 0, (name, kind, rc)
+            assert b"sgx_csd_batch" in cs.eng._lib.sgx_last_error(cs.eng._ctx)
+            torch.cuda.synchronize()
+            assert not bool(out.any()), (name, kind)
         if (name, "fbank_cross") in EXPECTED_UNSUPPORTED:   # a mono context: refused, the count zero, the buffer as it was
             fb = bank_of(cs.eng)
             assert fb.cross_fused == 0
@@ -350,14 +405,18 @@ def test_unstaged_pixel_stage_against_the_oracle(torch_cuda, name):
 
 
 # ---- A: output guards ---------------------------------------------------------------------------------------------------------------
-def refused_for_alignment(torch, cs, arena, first, n, what):
-    """sgx_fbank_cross_batch wants 16 bytes (include/sgx.h): at 8 modulo 16 it answers SGX_ERR_INVALID_ARG and writes nothing"""
+def refused_for_alignment(torch, cs, kind, arena, first, n, what):
+    """sgx_fbank_cross_batch and sgx_csd_batch want 16 bytes (include/sgx.h): at 8 modulo 16 they answer SGX_ERR_INVALID_ARG and write
+    nothing"""
     before = arena.words.clone()
     got = C.c_size_t(99)
     out = arena.payload(torch.float32)
     assert out.data_ptr() % 16 == 8
-    rc = cs.eng._lib.sgx_fbank_cross_batch(bank_of(cs.eng)._h, C.c_void_p(cs.dev_ragged.data_ptr()), cs.dev_ragged.numel() // cs.r.channels, first, n,
-                                           C.c_void_p(out.data_ptr()), C.byref(got))
+    lib, src, samples = cs.eng._lib, C.c_void_p(cs.dev_ragged.data_ptr()), cs.dev_ragged.numel() // cs.r.channels
+    if welch(kind) == "csd":
+        rc = lib.sgx_csd_batch(cs.eng._ctx, src, samples, first, n, group_of(kind, n), C.c_void_p(out.data_ptr()), C.byref(got))
+    else:
+        rc = lib.sgx_fbank_cross_batch(bank_of(cs.eng)._h, src, samples, first, n, C.c_void_p(out.data_ptr()), C.byref(got))
     assert rc == _lib.SGX_ERR_INVALID_ARG and got.value == 0, (what, rc, got.value)
     torch.cuda.synchronize()
     assert arena.guards_intact() and torch.equal(arena.words, before), (what, "a refused call wrote")
@@ -373,8 +432,8 @@ def test_output_guards(torch_cuda, name, kind, variant):
         for second in (False, True):
             prefill = ba.prefill_word(elem_of(kind), second)
             arena = Arena(torch, rows_of(kind, n) * rb, rb, variant == "odd", prefill)
-            if kind == "fbank_cross" and variant == "odd":
-                refused_for_alignment(torch, cs, arena, first, n, (name, kind, variant, first, n))
+            if (kind == "fbank_cross" or welch(kind) == "csd") and variant == "odd":
+                refused_for_alignment(torch, cs, kind, arena, first, n, (name, kind, variant, first, n))
                 continue
             run(cs.eng, kind, cs.dev_ragged, first, n, out=arena.payload(dtype_of(torch, kind)))
             what = (name, kind, variant, first, n, "all ones" if second else "+inf")
@@ -469,14 +528,21 @@ def test_stale_state(torch_cuda, name):
         if cs.istft:
             eng.istft_batch(torch.view_as_real(eng.stft_batch_complex(stream)).contiguous())
     del scratch
-    if "fbank_cross" in kinds:
-        # the workspace between its two row layouts: a cross call (two workspace rows per frame) after a magnitude call of more frames
-        # and before one of fewer, on the overflowing stream and then on the real one
-        a, b, c = F, max(F - 2, 1), max(F - 4, 1)
-        for stream in (hot, cs.dev):
-            got = [run(eng, "fbank", stream, 0, a), run(eng, "fbank_cross", stream, 1, b), run(eng, "fbank", stream, 2, c)]
-        for kind, first, n, t in zip(("fbank", "fbank_cross", "fbank"), (0, 1, 2), (a, min(b, F - 1), min(c, F - 2)), got):
-            check_result(torch, cs, kind, first, n, words(torch, t), (name, kind, first, n, "between the workspace's two row layouts"))
+    # the workspace between its row layouts (fbank: rows; psd: rows and block partials behind them; fbank_cross: double rows; csd: double
+    # rows and double partials), every call of another frame count than its neighbours, on the overflowing stream and then on the real
+    # one: a partial row or a resumed block that kept what the last user left shows in the Welch means.  (A mono row has no cross kinds.)
+    # No group is carried at these rows' 9, 5, 300 and 70 frames (tests/test_bounds_arena.py: test_welch_cases_of_the_gpu_tests), so the
+    # carry row after NaN is left to tests/test_gpu_psd.py's contexts and to part E below.
+    assert F >= 5
+    layouts = [("fbank", 0, F), ("psd_3", 1, F - 1), ("fbank_cross", 1, F - 2), ("csd_3", 0, F - 3), ("psd_n5", 2, max(F - 5, 2)),
+               ("fbank", 2, F - 4)]
+    layouts = [c for c in layouts if c[0] in kinds]
+    assert all(first + n <= F and n >= 1 for _, first, n in layouts)
+    for stream in (hot, cs.dev):
+        got = [run(eng, kind, stream, first, n) for kind, first, n in layouts]
+    for (kind, first, n), t in zip(layouts, got):
+        check_result(torch, cs, kind, first, n, words(torch, t), (name, kind, first, n, "between the workspace's row layouts"))
+    del got
     for kind in kinds:
         out = None
         if kind.startswith("peak"):   # (a stale +inf would survive a max: what the buffer held before must not matter either)
@@ -499,6 +565,11 @@ PIXEL_CONTEXTS = {
 PIXEL_RANGES = np.array([[32.0, 64.0], [100.0, 101.0], [440.0, 880.0], [1000.0, 12000.0], [20.0, 23999.0]], np.float32)
 
 
+def stage_group(cols):
+    """the group of the Welch stages under D: columns of 3 frames, and of 33 (two blocks, the last column short) on the long input"""
+    return 3 if cols < 100 else 33
+
+
 def pixel_call(eng, entry, src, out=None):
     if entry == "render_mags":
         return eng.render_mags(src, out=out)
@@ -508,15 +579,21 @@ def pixel_call(eng, entry, src, out=None):
         return bank_of(eng).apply(src, out=out)
     if entry == "fbank_cross_spec":
         return bank_of(eng).cross_apply(src, out=out)
+    if entry == "psd_mags":
+        return eng.psd_mags(src, stage_group(src.shape[0]), out=out)
+    if entry == "csd_spec":
+        return eng.csd_spec(src, stage_group(src.shape[0]), out=out)
     return eng.magnitude_in(src, PIXEL_RANGES, out=out)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("entry", ["render_mags", "render_bands", "magnitude_in", "fbank_mags", "fbank_cross_spec"])
+@pytest.mark.parametrize("entry", ["render_mags", "render_bands", "magnitude_in", "fbank_mags", "fbank_cross_spec", "psd_mags", "csd_spec"])
 @pytest.mark.parametrize("ctx", sorted(PIXEL_CONTEXTS))
 def test_pixel_stage(torch_cuda, ctx, entry, variant):
     """(the bank entries: edge_bank's filters on bin 0 and on bin M - 1 of every column would pull the neighbouring column's word, or the
-    NaN around the arena's payload, into a sum if a read were one bin off)"""
+    NaN around the arena's payload, into a sum if a read were one bin off; the Welch entries: rows of frames inside the NaN arena, the
+    means of every column against the header's sum order, tests/psd_reference.py -- every context here has one pair, so a column of the
+    input is a frame)"""
     torch = torch_cuda
     key = ("pixel", ctx)
     if key not in _cache:
@@ -524,28 +601,42 @@ def test_pixel_stage(torch_cuda, ctx, entry, variant):
     eng = _cache[key]
     odd = variant == "odd"
     rng = np.random.default_rng([len(ctx), len(entry)])
-    in_row = {"render_bands": eng.R * 2, "fbank_cross_spec": eng.M * 4}.get(entry, eng.M * 2)   # floats per input column
-    out_row = {"magnitude_in": len(PIXEL_RANGES) * 8, "fbank_mags": ba.N_BANK_FILTERS * 8, "fbank_cross_spec": ba.N_BANK_FILTERS * 16}.get(entry, eng.R * 4)   # bytes per output column
+    assert eng.pairs == 1
+    cross = entry in ("fbank_cross_spec", "csd_spec")
+    in_row = {"render_bands": eng.R * 2, "fbank_cross_spec": eng.M * 4, "csd_spec": eng.M * 4}.get(entry, eng.M * 2)   # floats per input column
+    out_row = {"magnitude_in": len(PIXEL_RANGES) * 8, "fbank_mags": ba.N_BANK_FILTERS * 8, "fbank_cross_spec": ba.N_BANK_FILTERS * 16,
+               "psd_mags": eng.M * 8, "csd_spec": eng.M * 16}.get(entry, eng.R * 4)   # bytes per output column
     for cols in (1, 7, 700):   # 700: the persistent workgroups walk several columns each
         # magnitudes from 1e-6 to 1: the whole of the colour ramp
         host = (10.0 ** rng.uniform(-6.0, 0.0, (cols, in_row // 2, 2))).astype(np.float32)
-        if entry == "fbank_cross_spec":
+        if cross:
             host *= rng.choice(np.float32([-1.0, 1.0]), host.shape)
+        out_cols = -(-cols // stage_group(cols)) if entry in ("psd_mags", "csd_spec") else cols
         exact_in = torch.from_numpy(host).cuda()
         want = words(torch, pixel_call(eng, entry, exact_in))
         if entry.startswith("fbank"):   # the clean run itself against the definition (tests/fbank_reference.py), on the first and the last column
             bank, ends = fr.edge_bank(eng.M), [0, cols - 1]
             ref = fr.bank_sums(host[ends], bank, 2) if entry == "fbank_mags" else fr.cross_sums(host[ends].reshape(2, eng.M, 2, 2), bank)
             assert np.array_equal(want.view(cols, -1)[ends].cpu().numpy().view(np.uint32).reshape(-1), ref.view(np.uint32).reshape(-1)), (ctx, entry, cols)
+        if entry in ("psd_mags", "csd_spec"):   # the clean run itself against the definition, every column
+            x = pr.psd_terms(host.reshape(cols, 1, eng.M, 2)) if entry == "psd_mags" else pr.csd_terms(host.reshape(cols, 1, eng.M, 2, 2))
+            mean = pr.welch_mean(x, stage_group(cols))
+            assert mean.shape[0] == out_cols and np.array_equal(want.cpu().numpy().view(np.uint32), mean.reshape(-1).view(np.uint32)), (ctx, entry, cols)
         src = Arena(torch, cols * in_row * 4, in_row * 4, odd, ba.NAN_WORD, guard=ba.NAN_WORD)
         src.payload(torch.float32)[:] = exact_in.view(-1)
         for second in (False, True):
             prefill = ba.prefill_word(ELEM[entry], second)
-            arena = Arena(torch, cols * out_row, out_row, odd, prefill)
+            arena = Arena(torch, out_cols * out_row, out_row, odd, prefill)
             out = arena.payload(torch.uint8 if ELEM[entry] == "u8" else torch.float32)
-            if entry == "fbank_cross_spec" and odd:   # both buffers must be 16-byte aligned (include/sgx.h): refused, nothing written
+            if cross and odd:   # both buffers must be 16-byte aligned (include/sgx.h): refused, nothing written
                 before = arena.words.clone()
-                rc = eng._lib.sgx_fbank_cross_spec(bank_of(eng)._h, C.c_void_p(src.payload().data_ptr()), cols, C.c_void_p(out.data_ptr()))
+                if entry == "csd_spec":
+                    got = C.c_size_t(99)
+                    rc = eng._lib.sgx_csd_spec(eng._ctx, C.c_void_p(src.payload().data_ptr()), cols, stage_group(cols), C.c_void_p(out.data_ptr()),
+                                               C.byref(got))
+                    assert got.value == 0, (ctx, entry, variant, cols)
+                else:
+                    rc = eng._lib.sgx_fbank_cross_spec(bank_of(eng)._h, C.c_void_p(src.payload().data_ptr()), cols, C.c_void_p(out.data_ptr()))
                 torch.cuda.synchronize()
                 assert rc == _lib.SGX_ERR_INVALID_ARG and torch.equal(arena.words, before), (ctx, entry, variant, cols, rc)
                 continue
@@ -675,3 +766,85 @@ def test_seams_peak_fused_route(torch_cuda):
             assert ba.fused_peak_run(n, min(g, n), n_cu) == run, (g, "the run was aligned to the group")
             assert (run % min(g, n) == 0) == (g == run or g == 1), (g, "no column of this group crosses a run's end")
         peak_against_bands(torch, eng, pcm, bands, first, groups)
+
+
+# ---- the Welch kinds: the baseline on every sub-range, and the seams of psd_reduce's ranges the model of bounds_arena selects -----------
+@pytest.mark.parametrize("name", ROWS)
+def test_welch_baseline(torch_cuda, name):
+    """On fresh, exact-size tensors: every Welch kind of every (first, n) of calls_of equals the header's sum order over the baseline's own
+    rows of that sub-range, the columns counted from its first frame, and the stage over those rows"""
+    torch = torch_cuda
+    cs = case(torch, name)
+    spec = torch.view_as_real(cs.base["complex"]).contiguous()
+    for kind in kinds_of(name):
+        if not welch(kind):
+            continue
+        for first, n in calls_of(cs):
+            got = words(torch, run(cs.eng, kind, cs.dev, first, n))
+            check_result(torch, cs, kind, first, n, got, (name, kind, first, n))
+            g = group_of(kind, n)
+            staged = cs.eng.psd_mags(cs.base["stft"][first:first + n], g) if welch(kind) == "psd" else cs.eng.csd_spec(spec[first:first + n], g)
+            assert torch.equal(words(torch, staged), got), (name, kind, first, n, "the stage over the baseline's rows differs")
+
+
+def strided_welch(kind, rows, group, stride):
+    """the header's sum order on every stride-th bin of rows on the device (as tests/test_gpu_psd.py: strided_reference)"""
+    bins = rows[:, :, ::stride].cpu().numpy()
+    return pr.welch_mean(pr.psd_terms(bins) if kind == "psd" else pr.csd_terms(bins), group)
+
+
+def welch_against_rows(torch, eng, kind, pcm, frames, group, stride, what):
+    """a batch call against the stage over the engine's own rows (the caller's rows, no row slots in the workspace: another layout of the
+    same ranges) on the device, and against the definition on a strided subset of the bins"""
+    if kind == "psd":
+        rows = eng.stft_batch(pcm)
+        got, staged = eng.psd_batch(pcm, group), eng.psd_mags(rows, group)
+    else:
+        rows = torch.view_as_real(eng.stft_batch_complex(pcm)).contiguous()
+        got, staged = eng.csd_batch(pcm, group), eng.csd_spec(rows, group)
+    assert rows.shape[0] == frames and got.shape[0] == -(-frames // min(group, frames)), what
+    assert torch.equal(words(torch, got), words(torch, staged)), (what, "batch and stage differ")
+    want = strided_welch(kind, rows, group, stride)
+    assert np.array_equal(got[:, :, ::stride].cpu().numpy().view(np.uint32).reshape(-1), want.view(np.uint32).reshape(-1)), (what, "not the definition's bits")
+    return got
+
+
+@pytest.mark.parametrize("kind", ["psd", "csd"])
+def test_seams_welch_carried_column(torch_cuda, kind):
+    """A column with more blocks than a range holds, carried in the context's float64 row, on a family whose rows do not go through kernel
+    11's scratch: the route of the table that needs the fewest frames for it (W 8192, 8 channels, hop 300: 737 frames, 353 of complex
+    rows) in one column, three more in a second.  The carry row is grown by the first call; the call is then repeated after one on an
+    all-NaN stream left NaN sums in it."""
+    torch = torch_cuda
+    cross = kind == "csd"
+    frames, r = ba.welch_carried_route(es.ROUTES, cross)
+    total = frames + 3                                     # a second, short column behind the carried one: it starts from +0 again
+    plan = ba.welch_ranges(r.W, r.pairs, cross, total, frames, True)
+    assert plan.carried and r.kernel != 11
+    assert [(x.reads_carry, x.writes_carry) for x in plan.ranges] == [(False, True), (True, False), (False, False)]
+    assert plan.ranges[2].frames == (frames, total)
+    eng = engine(r)
+    assert eng.info.stft_kernel == r.kernel and eng.info.mags_bytes_per_frame == ba.mags_bytes_per_frame(r.W, r.pairs)
+    pcm = eng.white_noise(r.W + (total - 1) * r.H, seed=0x5EED090D)
+    what = (r.name, kind, total, frames)
+    got = welch_against_rows(torch, eng, kind, pcm, total, frames, 64, what)
+    nan = torch.full_like(pcm, float("nan"))
+    batch = eng.psd_batch if kind == "psd" else eng.csd_batch
+    assert bool(torch.isnan(batch(nan, ba.WELCH_MAX)).all())
+    assert torch.equal(words(torch, batch(pcm, frames)), words(torch, got)), (what, "after NaN in the carry row")
+    eng.close()
+
+
+def test_seams_welch_odd_frame_of_a_paired_context(torch_cuda):
+    """Two frames of one transform (SGX_FLAG_PAIRED_FRAMES, mono W 2048): at group 1 a range holds 12294 // 2 = 6147 frames, so the second
+    range's rows launch starts on an odd frame, whose partner lies in the range before"""
+    torch = torch_cuda
+    r = es.ROUTE["k1_paired_mono"]
+    group, frames = ba.welch_odd_seam(r.W, r.pairs)
+    plan = ba.welch_ranges(r.W, r.pairs, False, frames, group, True)
+    assert len(plan.ranges) == 2 and plan.ranges[1].frames[0] % 2 == 1 and r.paired
+    eng = engine(r)
+    assert eng.info.stft_kernel == r.kernel and eng.info.mags_bytes_per_frame == ba.mags_bytes_per_frame(r.W, r.pairs)
+    pcm = eng.white_noise(r.W + (frames - 1) * r.H, seed=0x5EED090E)
+    welch_against_rows(torch, eng, "psd", pcm, frames, group, 64, (r.name, group, frames))
+    eng.close()

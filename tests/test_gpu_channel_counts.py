@@ -2,7 +2,8 @@
 table, the streams and the labelling of the cap rows), all through the C ABI.  Per row: the kernel and render_path bits it pins; every
 frame and pair of sgx_stft_batch and sgx_stft_batch_complex against the float64 truth at the project's own white-noise bounds (one
 CHANNEL-RATIO line per case); the half rows, pixels, bands, peak columns, filterbank and cross sums bit for bit against the stage entry
-points on the engine's own rows, fused and (at W 2048) two-kernel; sub-ranges; the inverse against include/sgx.h's definition, split at an
+points on the engine's own rows, fused and (at W 2048) two-kernel, the Welch means also against the header's sum order
+(tests/psd_reference.py) over those rows; sub-ranges; the inverse against include/sgx.h's definition, split at an
 odd sample and into an 8-mod-16 aligned buffer; a stream of identical pairs, whose every pair must give the bytes of pair 0 (the 4096-point
 family: also those of a two-channel context); the 6-channel rows of the persistent kernels at compute-unit limits around their pair count;
 sgx_process_one, the noise generator and sgx_create's refusals at odd and too large counts.
@@ -16,9 +17,11 @@ import time
 import numpy as np
 import pytest
 
+import bounds_arena as ba
 import channel_counts as cn
 import edge_signals as es
 import oracle
+import psd_reference as pr
 from conftest import mags_error
 from test_gpu_bands import two_call
 from test_gpu_bounds import words
@@ -192,6 +195,38 @@ def mel_banks(eng, powers=(2, 1)):
             fb.close()
 
 
+CAP_BINS = 8                # bins per row the host reference of the Welch means takes at the cap rows
+
+
+def check_welch(torch, s, eng, dev, rows, cx, first=0, count=None):
+    """sgx_psd_batch (and, where the case runs complex rows, sgx_csd_batch) over frames [first, first + count) of the stream against the
+    stage over the same frames of the engine's own rows, bit for bit on the device, and both against the header's sum order
+    (tests/psd_reference.py) over those rows: on all bins, at the cap rows on every stride-th.  The groups are those of the peak columns;
+    at the cap one column of all frames and group 2.  No context runs a fused mode: the rows go through the workspace, which at 32 768
+    channels holds fewer rows than a block of 32 and its partial, or none (bounds_arena.welch_ranges: a frame per piece)."""
+    c = s.c
+    assert eng.psd_fused == 0 and eng.csd_fused == 0
+    end = c.frames if count is None else min(c.frames, first + count)
+    n = end - first
+    groups = [ba.WELCH_MAX, 2] if c.cap else peak_groups(n)
+    stride = max(1, eng.M // CAP_BINS) if c.cap else 1
+    kinds = [("psd", rows, eng.psd_batch, eng.psd_mags, pr.psd_terms, 2)]
+    if cx is not None:
+        kinds.append(("csd", torch.view_as_real(cx), eng.csd_batch, eng.csd_spec, pr.csd_terms, 4))
+    for kind, own, batch, stage, terms, comps in kinds:
+        x = terms(own[first:end][:, :, ::stride].cpu().numpy())
+        for group in groups:
+            assert eng.info.mags_bytes_per_frame == ba.mags_bytes_per_frame(c.W, c.pairs)      # (what the model counts the rows by)
+            got = batch(dev, group, first_frame=first, max_frames=count)
+            assert tuple(got.shape) == (-(-n // min(group, n)), c.pairs, eng.M, comps), (c.name, kind, group, first, count)
+            staged = stage(own[first:end].contiguous(), group)
+            assert torch.equal(words(torch, got), words(torch, staged)), (c.name, kind, "batch and stage, group", group, first, count)
+            want = pr.welch_mean(x, group)
+            assert np.array_equal(got[:, :, ::stride].cpu().numpy().view(np.uint32).reshape(-1), want.view(np.uint32).reshape(-1)), \
+                (c.name, kind, "not the definition's bits, group", group, first, count)
+            del got, staged
+
+
 def check_derived(torch, s, eng=None, fused=True):
     """the outputs of `eng` (default the case's own context) against the stage entry points on its own rows"""
     c = s.c
@@ -218,10 +253,12 @@ def check_derived(torch, s, eng=None, fused=True):
         assert tuple(peak.shape) == (-(-c.frames // group), c.pairs, eng.R, 2)
         assert same(peak, amax_groups(bands, group)), (c.name, "peak columns, group", group)
     if not c.complex_and_banks:
+        check_welch(torch, s, eng, dev, rows, None)
         return
     cx = s.cx if own else eng.stft_batch_complex(dev)
     if not own:
         assert torch.equal(words(torch, cx), words(torch, s.cx)), (c.name, "complex rows of the two-kernel context")
+    check_welch(torch, s, eng, dev, rows, cx)
     with mel_banks(eng) as fbs:
         for power, fb in fbs.items():
             assert fb.n_filters == 128
@@ -253,6 +290,7 @@ def check_sub_ranges(torch, s):
         if s.cx is not None:
             part = eng.stft_batch_complex(dev, first_frame=first, max_frames=count)
             assert torch.equal(words(torch, part), words(torch, s.cx[first:end])), (c.name, "complex rows", first, count)
+        check_welch(torch, s, eng, dev, s.rows, s.cx, first, count)     # (the columns counted from the sub-range's own first frame)
 
 
 # ---- 5. the inverse ----------------------------------------------------------------------------------------------------------------------
@@ -291,9 +329,10 @@ def check_identical_pairs(torch, s):
     pcm = cn.identical_stream(c)
     dev = to_dev(torch, pcm)
     def outputs(e, d):
-        outs = {"rows": e.stft_batch(d), "bands": e.bands_batch(d)}
+        outs = {"rows": e.stft_batch(d), "bands": e.bands_batch(d), "Welch means": e.psd_batch(d, 2)}
         if c.complex_and_banks:
             outs["complex rows"] = e.stft_batch_complex(d)
+            outs["Welch cross means"] = e.csd_batch(d, 2)
             with mel_banks(e, powers=(2,)) as fbs:
                 outs["filterbank sums"] = fbs[2].batch(d)
         return outs
@@ -386,6 +425,15 @@ def test_cap_row(torch_cuda, name):
     torch = torch_cuda
     c = cn.CASE[name]
     t0 = time.perf_counter()
+    # the rows the workspace holds of a Welch call (psd, csd): none at W 2048 and W 8192 -- a frame per piece, two rows of workspace --,
+    # fewer than a block of 32 and its partial at W 64 and W 735 -- a block in pieces --, and at W 23 two blocks and one
+    caps = (ba.welch_cap(c.W, c.pairs, False), ba.welch_cap(c.W, c.pairs, True))
+    assert caps == {"k1_h256_cap": (0, 0), "k16_h512_cap": (0, 0), "mixed_w735_runtime_cap": (2, 1), "generic_w64_cap": (24, 12),
+                    "bluestein_w23_cap": (69, 34)}[name]
+    assert caps == (0, 0) or caps[0] < 33 or name == "bluestein_w23_cap"
+    for cross in (False, True):
+        plan = ba.welch_ranges(c.W, c.pairs, cross, c.frames, ba.WELCH_MAX, True)
+        assert plan.workspace_rows <= max(plan.cap, 2) and (plan.piece == 1) == (plan.cap <= 2), (name, plan)
     s = State(torch, c)
     steps = [("build", time.perf_counter() - t0)]
     todo = [("route", lambda: check_route(s)), ("truth", lambda: check_truth(torch, s)), ("derived", lambda: check_derived(torch, s)),

@@ -4,6 +4,9 @@ static -- and nothing else.  One W 2048 mono context at sgx_set_cu_limit(ctx, 1)
 100 (eight columns per pair), 203 frames (a last job without its second frame) and 64, first_frame 0 and 7, float, half and complex
 rows; sgx_set_run_claim forces shares 0/16 and 8/16 with chunks of 1 job, 3 jobs, more than the whole pool, exactly the pool, and a third
 of the pool (fewer chunks than workgroups: one claims nothing).  Every call goes into a NaN-prefilled payload between guard rows.  The
+same launcher writes the rows of every workspace route of such a context, under the same deal: sgx_psd_batch always, and with
+SGX_FLAG_NO_FUSED_RENDER sgx_render_batch, sgx_bands_batch, sgx_bands_peak_batch and sgx_fbank_batch; each of these consumers is held to
+its own bytes behind the static split in the same way (CONSUMERS).  The
 counter's reset: the same call three times back to back, with a call on a second context in between.  At the automatic rule these shapes
 run the static split (sgx_run_claim).  No tolerance is involved.  Run with -m gpu on an MI355X."""
 import ctypes as C
@@ -14,17 +17,21 @@ import pytest
 import bounds_arena as ba
 import oracle
 from spectrogram_rs_amd import SgxError, SpectrogramEngine, _lib
-from test_gpu_bounds import Arena, dtype_of, elem_of, row_bytes, run, words
+from test_gpu_bounds import Arena, bank_of, dtype_of, elem_of, row_bytes, rows_of, run, words
 
 pytestmark = pytest.mark.gpu
 
 W, SR = 2048, 48000.0
 BLOCKS = 4                          # cu limit 1: four workgroups
 SHAPES = [(203, 0), (203, 7), (64, 0), (64, 7)]     # (frames of the call, first_frame)
-KINDS = ["stft", "f16", "complex"]
+ROWS_KINDS = ["stft", "f16", "complex"]
+# the consumers that launch the rows kernel into the workspace: kind -> engine keywords (the default context; one without the fused modes)
+CONSUMERS = {"psd_3": {}, "render": dict(fused_render=False), "bands": dict(fused_render=False), "peak_3": dict(fused_render=False),
+             "fbank": dict(fused_render=False)}
+KINDS = ROWS_KINDS + list(CONSUMERS)
 SHARES = [0, 8]
 NAN_F16 = 0x7E007E00
-PREFILL = {"f32": ba.NAN_WORD, "f16": NAN_F16}
+PREFILL = {"f32": ba.NAN_WORD, "f16": NAN_F16, "u8": ba.BYTE_FILL * 0x01010101}
 
 
 def pool_of(n_frames, share):
@@ -49,11 +56,20 @@ def torch_cuda():
     torch.cuda.empty_cache()
 
 
-def open_engine(hop):
-    eng = SpectrogramEngine(SR, window_samples=W, hop_samples=hop, channels=1, device=0, gradient="viridis")
+def open_engine(hop, kind="stft"):
+    eng = SpectrogramEngine(SR, window_samples=W, hop_samples=hop, channels=1, device=0, gradient="viridis", **CONSUMERS.get(kind, {}))
     assert eng.info.stft_kernel == 2 and eng.info.render_path & 8, "the real-input 4096-point kernel must be the one that runs"
+    assert eng.psd_fused == 0
+    if CONSUMERS.get(kind):     # every consumer of this context takes the rows from the workspace
+        assert eng.info.render_path & 1 == 0 and eng.bands_fused == 0 and eng.bands_peak_fused == 0 and bank_of(eng).fused == 0
     eng.set_cu_limit(1)
     return eng
+
+
+def finite(torch, kind, want):
+    if elem_of(kind) == "u8":
+        return True
+    return not bool(torch.isnan(want.view(torch.float32 if elem_of(kind) == "f32" else torch.float16)).any())
 
 
 def stream(torch, hop, seed):
@@ -62,7 +78,7 @@ def stream(torch, hop, seed):
 
 
 def in_arena(torch, eng, kind, dev, first, n):
-    arena = Arena(torch, n * row_bytes(eng, kind), row_bytes(eng, kind), False, PREFILL[elem_of(kind)])
+    arena = Arena(torch, rows_of(kind, n) * row_bytes(eng, kind), row_bytes(eng, kind), False, PREFILL[elem_of(kind)])
     run(eng, kind, dev, first, n, out=arena.payload(dtype_of(torch, kind)).view(-1))
     torch.cuda.synchronize()
     return arena
@@ -72,13 +88,13 @@ def in_arena(torch, eng, kind, dev, first, n):
 @pytest.mark.parametrize("hop", [256, 100])
 def test_every_split_writes_the_static_split_s_bytes(torch_cuda, hop, kind):
     torch = torch_cuda
-    eng = open_engine(hop)
+    eng = open_engine(hop, kind)
     dev = stream(torch, hop, 0xC1A1 + hop)
     for n, first in SHAPES:
         assert eng.run_claim(n) == (16, 0), "at the automatic rule a launch this short is the static one"
         eng.set_run_claim(16, 0)
         want = words(torch, run(eng, kind, dev, first, n)).clone()
-        assert not bool(torch.isnan(want.view(torch.float32 if kind != "f16" else torch.float16)).any())
+        assert finite(torch, kind, want)
         for share in SHARES:
             for chunk in chunks_of(n, share):
                 eng.set_run_claim(share, chunk)
@@ -96,18 +112,21 @@ def test_every_split_writes_the_static_split_s_bytes(torch_cuda, hop, kind):
 
 @pytest.mark.parametrize("hop", [256, 100])
 def test_the_counter_starts_at_zero_in_every_launch(torch_cuda, hop):
-    """the same call three times back to back on one context, a call of another context in between: every launch claims from chunk 0"""
+    """the same call three times back to back on one context, a call of another context in between: every launch claims from chunk 0.
+    The Welch call between the rows calls launches the same kernel into the workspace: one more memset of the one claim counter, on the
+    same stream, and its means are those behind the static split"""
     torch = torch_cuda
     eng, other = open_engine(hop), open_engine(hop)
     dev = stream(torch, hop, 0xC1A2 + hop)
     n, first = 203, 7
     eng.set_run_claim(16, 0)
-    want = {kind: words(torch, run(eng, kind, dev, first, n)).clone() for kind in KINDS}
+    back_to_back = ROWS_KINDS[:2] + ["psd_3"] + ROWS_KINDS[2:] + ["psd_3"]
+    want = {kind: words(torch, run(eng, kind, dev, first, n)).clone() for kind in back_to_back}
     eng.set_run_claim(8, 3)
     other.set_run_claim(0, 1)
     outs = []
     for rep in range(3):        # enqueued back to back: nothing waits between the launches
-        for kind in KINDS:
+        for kind in back_to_back:
             outs.append((rep, kind, in_arena_nosync(torch, eng, kind, dev, first, n)))
         if rep == 1:
             outs.append((rep, "other", in_arena_nosync(torch, other, "stft", dev, first, n)))
@@ -118,7 +137,7 @@ def test_the_counter_starts_at_zero_in_every_launch(torch_cuda, hop):
 
 
 def in_arena_nosync(torch, eng, kind, dev, first, n):
-    arena = Arena(torch, n * row_bytes(eng, kind), row_bytes(eng, kind), False, PREFILL[elem_of(kind)])
+    arena = Arena(torch, rows_of(kind, n) * row_bytes(eng, kind), row_bytes(eng, kind), False, PREFILL[elem_of(kind)])
     run(eng, kind, dev, first, n, out=arena.payload(dtype_of(torch, kind)).view(-1))
     return arena
 

@@ -1,7 +1,8 @@
 """Every persistent launch at any compute-unit count: bit for bit what it writes at the device's own (tests/cu_counts.py: the case table,
 the job splits restated, the branch each (case, limit) takes; tests/test_cu_counts.py proves on the CPU that no case addresses a row
 outside its buffers).  One context per case runs every limit of cu_counts.LIMITS through sgx_set_cu_limit; every entry point the case
-serves, once over the whole range and once over a sub-range from an odd first_frame, writes into a NaN-prefilled (pixels: 0xA5) payload
+serves (the Welch calls behind the rows of every forward case among them: cu_counts.welch_kinds), once over the whole range and once
+over a sub-range from an odd first_frame, writes into a NaN-prefilled (pixels: 0xA5) payload
 between guards and must leave the bytes of the same call at limit 0, no prefill and both guards intact.  The limit-0 rows are held once
 to the float64 truth at the project's white-noise bound; after the sweep limit 0 is set again and one call repeated.  The contexts of the
 sweep make their first call at limit 0, so their peak partial columns are allocated at full size: test_a_buffer_sized_at_a_low_limit_is_regrown
@@ -22,6 +23,7 @@ import oracle
 from conftest import chirpz_bound, mags_error
 from spectrogram_rs_amd import SpectrogramEngine, _lib
 import fbank_reference as fr
+import psd_reference as pr
 from test_gpu_bounds import Arena, bank_of, dtype_of, elem_of, row_bytes, to_dev, words
 
 pytestmark = pytest.mark.gpu
@@ -103,6 +105,22 @@ def held_to_the_definition(torch, case, eng, kind, dev, F, ref_words):
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (case.name, kind, "the limit-0 sums differ from the definition")
 
 
+def held_to_the_welch_definition(torch, case, eng, kind, dev, F, ref_words):
+    """the limit-0 means of a Welch call at group 3 on the first, the middle and the last column (the ragged one) against the header's sum
+    order over the engine's own rows of those columns (tests/psd_reference.py), bit for bit"""
+    cols = -(-F // 3)
+    comps = 2 if kind == "psd_3" else 4
+    got = ref_words.view(torch.float32).view(cols, eng.pairs, eng.M, comps).cpu().numpy()
+    for j in (0, cols // 2, cols - 1):
+        n = min(3, F - 3 * j)
+        if kind == "psd_3":
+            x = pr.psd_terms(eng.stft_batch(dev, 3 * j, n).cpu().numpy())
+        else:
+            x = pr.csd_terms(torch.view_as_real(eng.stft_batch_complex(dev, 3 * j, n)).cpu().numpy())
+        want = pr.welch_mean(x, 3)
+        assert want.shape[0] == 1 and np.array_equal(got[j].view(np.uint32), want[0].view(np.uint32)), (case.name, kind, j, "the limit-0 means differ from the definition")
+
+
 def run_forward(eng, kind, group, dev, first, n, out=None):
     if kind == "stft":
         return eng.stft_batch(dev, first, n, out=out)
@@ -118,6 +136,10 @@ def run_forward(eng, kind, group, dev, first, n, out=None):
         return bank_of(eng).batch(dev, first, n, out=out)
     if kind == "fbank_cross":
         return bank_of(eng).cross_batch(dev, first, n, out=out)
+    if kind == "psd_3":
+        return eng.psd_batch(dev, group, first, n, out=out)
+    if kind == "csd_3":
+        return eng.csd_batch(dev, group, first, n, out=out)
     return eng.bands_peak_batch(dev, group, first, n, out=out)
 
 
@@ -153,6 +175,9 @@ def forward_case(torch, case, dcu):
     if bank_kinds:
         fb = bank_of(eng)
         assert (fb.fused, fb.cross_fused) == (ba.fbank_fused(r), ba.fbank_fused(r, cross=True)), (case.name, fb.fused, fb.cross_fused)
+    # the Welch calls: on the workspace route everywhere, behind the rows whose split is under test
+    welch_kinds = list(cc.welch_kinds(r))
+    assert eng.psd_fused == 0 and eng.csd_fused == 0
     for limit in cc.LIMITS:
         n_cu = cc.limit_value(limit, dcu)
         eng.set_cu_limit(0 if limit == 0 else n_cu)
@@ -163,8 +188,8 @@ def forward_case(torch, case, dcu):
         predicted = VARIANT == family and cc.more_than_one_job(case, limit, dcu, family)
         differs = False
         for first, n in cc.forward_calls(case, limit):
-            groups = {"peak_3": 3, "peak_run": cc.peak_run_group(r, n, n_cu)}
-            for kind in FORWARD_KINDS + bank_kinds:
+            groups = {"peak_3": 3, "peak_run": cc.peak_run_group(r, n, n_cu), "psd_3": 3, "csd_3": 3}
+            for kind in FORWARD_KINDS + bank_kinds + welch_kinds:
                 group = groups.get(kind, 0)
                 key = (F, kind, group, first)
                 if key not in ref:
@@ -174,6 +199,8 @@ def forward_case(torch, case, dcu):
                         held_to_the_truth(case, r, pcm, ref[key].view(torch.float32).view(n, r.pairs, r.W - 1, 2).cpu().numpy())
                     if kind in bank_kinds and first == 0:
                         held_to_the_definition(torch, case, eng, kind, dev, F, ref[key])
+                    if kind in welch_kinds and first == 0:
+                        held_to_the_welch_definition(torch, case, eng, kind, dev, F, ref[key])
                     eng.set_cu_limit(0 if limit == 0 else n_cu)
                 rb = row_bytes(eng, "bands" if kind.startswith("peak") else kind)
                 rows = -(-n // group) if group else n

@@ -12,7 +12,10 @@ An offset truncated to 32 bits wraps to a lower, valid address of the same buffe
      sgx_magnitude_in and sgx_render_bands, one context per kernel body, the body derived on the device from the launchers' own
      quantities.  The filterbank calls write 1024 single-bin sums per frame past both marks on the fused family and on one workspace
      family, and their stages alone (sgx_fbank_mags, sgx_fbank_cross_spec) on 64-point columns; their probe rows are held to the header's
-     definition (tests/fbank_reference.py) bit for bit.  (Not here: sgx_image_* and sgx_view_* on rings of more than 2^32 bytes.)
+     definition (tests/fbank_reference.py) bit for bit.  The Welch calls at group 1 write a column per frame past both marks on the two
+     4096-point families (43 ranges of the workspace each), and their stages alone (sgx_psd_mags, sgx_csd_spec) read and write rows of 63
+     bins past them at groups 1 and 2; probe rows against the header's sum order (tests/psd_reference.py), the whole by checksum against
+     a torch expression over the same rows.  (Not here: sgx_image_* and sgx_view_* on rings of more than 2^32 bytes.)
 The streams of 1 - 3 lie in NaN arenas where only the samples the call's frames own hold noise.  Results are compared bit for bit with
 a compact replay (the same samples at the same address modulo 16 and the same frame parity in a small fresh tensor); magnitudes and
 complex rows are also held to the float64 truth at the bound the project holds white noise to (conftest.KERNEL_BOUND / chirpz_bound,
@@ -28,6 +31,7 @@ import edge_signals as es
 import far_offsets as fo
 import fbank_reference as fr
 import oracle
+import psd_reference as pr
 from conftest import KERNEL_BOUND, chirpz_bound, mags_error
 from test_gpu_bounds import words
 from test_gpu_complex import complex_error, truth_complex
@@ -120,6 +124,8 @@ def run(eng, kind, pcm, first, n, out=None):
         return far_bank_of(eng).cross_batch(pcm, first, n, out=out)
     if kind.startswith("peak_"):
         return eng.bands_peak_batch(pcm, int(kind[5:]), first, n, out=out)
+    if kind in fo.WELCH_KINDS:
+        return (eng.psd_batch if kind == "psd_1" else eng.csd_batch)(pcm, 1, first, n, out=out)
     f = {"stft": eng.stft_batch, "f16": eng.stft_batch_f16, "complex": eng.stft_batch_complex, "render": eng.render_batch,
          "bands": eng.bands_batch}[kind]
     return f(pcm, first, n, out=out)
@@ -323,7 +329,26 @@ def run_hop_case(g, case, eng, eng_small, rows_eng, stream_i, stream, grad):
 
 
 # ---- part 4: outputs past 2^31 and 2^32 bytes --------------------------------------------------------------------------------------------
-ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "peak_2": "f32", "fbank": "f32", "fbank_cross": "f32"}
+ELEM = {"stft": "f32", "f16": "f16", "complex": "f32", "render": "u8", "bands": "f32", "peak_2": "f32", "fbank": "f32", "fbank_cross": "f32",
+        "psd_1": "f32", "csd_1": "f32"}
+
+
+def welch_terms(torch, entry, rows):
+    """the summands of the Welch calls as a torch expression in float32, one kernel per product, sum and difference (nothing is
+    contracted): psd rows [..., 2] of magnitudes -> m * m; csd rows [..., 4] of (a, b, c, d) -> [..., 4].  The probe rows of every case
+    hold the same bits to tests/psd_reference.py's psd_terms / csd_terms."""
+    if entry in ("psd_mags", "psd_1"):
+        return rows * rows
+    a, b, c, d = rows.unbind(-1)
+    return torch.stack([a * a + b * b, c * c + d * d, a * c + b * d, b * c - a * d], -1)
+
+
+def welch_means_of_two(torch, x):
+    """group 2 as a torch expression: x [2 j or 2 j + 1 frames][...] -> the means of columns of two frames.  The block's chain from +0 is
+    exact for its first add, so a column is (float)((double)(x0 + x1) / 2); an odd last frame is a column of its own, x / 1"""
+    pairs = x[:x.shape[0] // 2 * 2].view(x.shape[0] // 2, 2, *x.shape[1:])
+    out = ((pairs[:, 0] + pairs[:, 1]).double() / 2.0).float()
+    return out if x.shape[0] % 2 == 0 else torch.cat([out, x[-1:] + 0.0])
 
 
 def count_equal(torch, t, word):
@@ -395,6 +420,24 @@ def test_output_marks(gpu, case):
         pieces = (pieces + eng.checksum(piece_buf[:n * rw], base_word=a * rw)) % (1 << 64)
     assert whole == pieces, (case.id, "the checksum of the whole differs from the sum over the pieces")
     del piece_buf
+    if kind in fo.WELCH_KINDS:
+        # group 1 is the summand itself: the whole against rn(m * m) (the four cross terms) of the engine's own rows, piece by piece --
+        # rows written by direct calls, not through the workspace's ranges
+        assert eng.psd_fused == 0 and eng.csd_fused == 0
+        ranges = ba.welch_ranges(W, r.pairs, kind == "csd_1", F, 1, True).ranges
+        assert len(ranges) >= 40 and ranges[-1].frames[1] == F > 1 << 17, (case.id, len(ranges))
+        if kind == "psd_1":   # the rows launch of a full range takes the measured weights and their pool on the whole device
+            n_range = ranges[0].frames[1] - ranges[0].frames[0]
+            assert eng.cu_limit == torch.cuda.get_device_properties(0).multi_processor_count
+            print(f"FAR-WELCH {case.id}: {len(ranges)} ranges of {n_range} frames, weights {eng.run_weights(n_range)}, claim {eng.run_claim(n_range)}")
+        own = 0
+        for a, n in case.pieces():
+            rows_ = eng.stft_batch(pcm, a, n) if kind == "psd_1" else torch.view_as_real(eng.stft_batch_complex(pcm, a, n)).reshape(n, 1, W - 1, 4)
+            x = welch_terms(torch, kind, rows_)
+            del rows_
+            own = (own + eng.checksum(x.view(-1).view(torch.int32), base_word=a * rw)) % (1 << 64)
+            del x
+        assert whole == own, (case.id, "the checksum of the whole differs from that of the summands of the engine's own rows")
     # (b) the probe rows
     sr = eng.info.sample_rate_u32
     grad = builtin_gradient("viridis")
@@ -418,6 +461,13 @@ def test_output_marks(gpu, case):
             ratio = truth.hold(f"{case.id} row {k}", t0, got if kind == "stft" else None, got if kind == "complex" else None)
             worst = max(worst, ratio)
             assert ratio <= 1.0, (case.id, k, ratio, "misses the float64 truth")
+        elif kind in fo.WELCH_KINDS:   # the header's sum order over the engine's own rows of that frame (tests/psd_reference.py), bit for bit
+            if kind == "psd_1":
+                x = pr.psd_terms(eng.stft_batch(pcm, first, n).cpu().numpy())
+            else:
+                x = pr.csd_terms(torch.view_as_real(eng.stft_batch_complex(pcm, first, n)).cpu().numpy())
+            want = pr.welch_mean(x, 1)
+            assert np.array_equal(one[j].cpu().numpy().view(np.uint32), want[j].view(np.uint32)), (case.id, k, "differs from the definition over the engine's rows")
         elif kind == "fbank":   # the header's definition over the engine's own rows of that frame (tests/fbank_reference.py), bit for bit
             want = fr.bank_sums(eng.stft_batch(pcm, first, n)[j].cpu().numpy(), fo.far_bank(eng.M), 2)
             assert np.array_equal(one[j].cpu().numpy().view(np.uint32), want.view(np.uint32)), (case.id, k, "differs from the definition over the engine's rows")
@@ -704,6 +754,75 @@ def test_bank_stage_marks(gpu, case):
             want = fr.cross_sums(host.reshape(1, eng.M, 2, 2), bank) if cross else fr.bank_sums(host.reshape(1, eng.M, 2), bank, 2)
             assert np.array_equal(one.cpu().numpy().view(np.uint32), want.view(np.uint32)), (case.id, k, "differs from the definition")
         del buf, payload, src
+    finally:
+        torch.cuda.synchronize()
+        eng.close()
+
+
+# ---- part 4, the Welch stages alone: sgx_psd_mags, sgx_csd_spec with input and output past 2^32 bytes -------------------------------------
+@pytest.mark.parametrize("case", fo.WELCH_STAGE_CASES, ids=lambda c: c.id)
+def test_welch_stage_marks(gpu, case):
+    """The block kernel reads frame f of element e at `f * elems + e` and the combine writes column j at `j * elems + e`: with rows of 63
+    bins both indices pass bytes 2^31 and 2^32 at frames and columns the case probes.  Group 1: the output crosses the marks the input
+    crosses.  Group 2: the output crosses 2^31 only, and input frame 2 j + 1 of the columns behind it lies past both marks.  The guard, the
+    prefill, the checksum of the whole against that of a torch expression over the same input in pieces, and the probe columns against
+    the header's sum order (tests/psd_reference.py) over the same input rows fetched from the device, bit for bit"""
+    from spectrogram_rs_amd import SpectrogramEngine
+    g, torch = gpu, gpu.torch
+    eng = SpectrogramEngine(es.SR, device=0, window_samples=case.W, hop_samples=case.W // 2, channels=2)
+    try:
+        assert eng.M == case.M and eng.pairs == 1 and eng.psd_fused == 0 and eng.csd_fused == 0
+        cross = case.entry == "csd_spec"
+        comps = 4 if cross else 2
+        F, rw = case.frames, case.row_bytes // 4
+        assert rw == eng.M * comps
+        stage = eng.csd_spec if cross else eng.psd_mags
+        terms = pr.csd_terms if cross else pr.psd_terms
+        # the engine's noise as it is for the complex rows (either sign), its squares plus 1e-7 as magnitudes
+        src = eng.white_noise(F * rw, seed=fo.NOISE_SEED, channels=1)
+        if not cross:
+            src.mul_(src).add_(1e-7)
+        rows = src.view(F, 1, eng.M, 2, 2) if cross else src.view(F, 1, eng.M, 2)
+        before = eng.checksum(src)
+        prefill, guard = ba.as_i32(ba.prefill_word("f32", False)), ba.as_i32(ba.GUARD_WORD)
+        for group in case.groups:
+            cols = case.cols(group)
+            marks_in, marks_out = case.crossed(group)
+            assert marks_in == fo.OUTPUT_MARKS and marks_out == fo.OUTPUT_MARKS[:3 - group], (case.id, group)
+            total = cols * rw
+            buf = torch.full((total + ba.guard_bytes(case.row_bytes) // 4,), prefill, dtype=torch.int32, device="cuda")
+            buf[total:] = guard
+            payload = buf[:total]
+            got = stage(rows, group, out=payload.view(torch.float32))
+            assert got.data_ptr() == payload.data_ptr()
+            # (a)
+            assert bool((buf[total:] == guard).all()), (case.id, group, "the guard was written")
+            left = count_equal(torch, payload, prefill)
+            assert left == 0, (case.id, group, left, "words still hold the prefill")
+            assert eng.checksum(src) == before, (case.id, group, "the input was written")
+            # (c) the whole against the torch expression over the same input, in pieces below 2^31 bytes of input and of output
+            whole, expr = eng.checksum(payload), 0
+            for a, n in case.pieces(group):
+                f0, f1 = a * group, min((a + n) * group, F)
+                x = welch_terms(torch, case.entry, src[f0 * rw:f1 * rw].view(f1 - f0, eng.M, comps))
+                if group == 2:
+                    x = welch_means_of_two(torch, x)
+                assert x.shape[0] == n and x.numel() * 4 < fo.PIECE_LIMIT
+                expr = (expr + eng.checksum(x.view(-1).view(torch.int32), base_word=a * rw)) % (1 << 64)
+                del x
+            assert whole == expr, (case.id, group, "the checksum of the whole differs from that of the torch expression over the input")
+            # (b) the columns that hold a mark of the output or whose frames hold a mark of the input, their neighbours, the first, the last
+            for k in case.probes(group):
+                f0, f1 = k * group, min((k + 1) * group, F)
+                host = rows[f0:f1].cpu().numpy()
+                want = pr.welch_mean(terms(host), group)
+                assert want.shape[0] == 1
+                assert np.array_equal(payload[k * rw:(k + 1) * rw].cpu().numpy().view(np.uint32), want.reshape(-1).view(np.uint32)), \
+                    (case.id, group, k, "differs from the definition over the same rows")
+                one = stage(rows[f0:f1].clone(), group)
+                assert torch.equal(words(torch, one), payload[k * rw:(k + 1) * rw]), (case.id, group, k, "differs from a call of that column alone")
+            del buf, payload, got
+        del src, rows
     finally:
         torch.cuda.synchronize()
         eng.close()

@@ -298,7 +298,7 @@ def test_ranges_shorter_than_the_call_at_w19200(kind):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_rows_too_long_for_a_block_at_w32768_ch64(kind):
-    """W 32768 with 64 channels: 22 rows (11 complex rows) fit the workspace -- fewer than a block of 32 frames and its partial row.  The
+    """W 32768 with 64 channels: 24 rows (12 complex rows) fit the workspace -- fewer than a block of 32 frames and its partial row.  The
     batch call takes a block's rows a few frames at a time and continues the block's chain; the bits stay the definition's"""
     import torch
 

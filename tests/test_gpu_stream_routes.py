@@ -7,8 +7,8 @@ like one launched on the context's stream.  Here
      has run, the outputs are prefilled, and the context's own buffers hold another seed's state.  A kernel, copy or memset placed on
      another stream runs before its input exists.  The host must have enqueued everything before the stream wakes (nothing in the steady
      state of an entry point waits on the host), and every output is bit for bit what the same calls give on the NULL stream;
-  2  so do sgx_view_write_rows / sgx_view_draw, sgx_image_write_columns / sgx_image_read, sgx_render_mags on one context per kernel body
-     and sgx_magnitude_in on both of its instantiations;
+  2  so do sgx_view_write_rows / sgx_view_draw, sgx_image_write_columns / sgx_image_read, sgx_render_mags on one context per kernel body,
+     sgx_magnitude_in on both of its instantiations, and a Welch call whose one column is carried and whose blocks are pieced;
   3  a context that the wrapper rebinds from a busy stream to another (SpectrogramEngine binds to torch's current stream before every
      call) has its later work ordered behind its earlier work, on the device; rebinding to the same stream costs no wait.
 Nothing here has a tolerance.  Run with -m gpu on an MI355X."""
@@ -108,7 +108,11 @@ class RouteCalls:
             "render_bands": buffer(torch, (F * P, R, 4), u8, pix), "checksum_add": torch.zeros(1, dtype=torch.int64, device="cuda"),
             "fbank": buffer(torch, (F, P, fb.n_filters, 2), f32, flt), "fbank_mags": buffer(torch, (F * P, fb.n_filters, 2), f32, flt),
             "fbank_cross_spec": buffer(torch, (F * P, fb.n_filters, 4), f32, flt),
+            "psd_3": buffer(torch, (cols, P, M, 2), f32, flt), "psd_mags": buffer(torch, (cols, P, M, 2), f32, flt),
+            "csd_spec": buffer(torch, (cols, P, M, 4), f32, flt),
         }
+        if "csd_3" in entries:
+            self.out["csd_3"] = buffer(torch, (cols, P, M, 4), f32, flt)
         if "fbank_cross" in entries:
             self.out["fbank_cross"] = buffer(torch, (F, P, fb.n_filters, 4), f32, flt)
         if "istft" in entries:
@@ -141,6 +145,12 @@ class RouteCalls:
                 assert got.value == F, (r.name, entry)
             elif entry in ("fbank_mags", "fbank_cross_spec"):
                 ck(getattr(lib, sc.SYMBOL[entry])(self.fb._h, ptr(o[sc.READS[entry]]), F * e.pairs, ptr(o[entry])))
+            elif entry in ("psd_3", "csd_3"):
+                ck(getattr(lib, sc.SYMBOL[entry])(ctx, ptr(self.pcm), n, 0, F, sc.PEAK_GROUP, ptr(o[entry]), C.byref(got)))
+                assert got.value == o[entry].shape[0], (r.name, entry)
+            elif entry in ("psd_mags", "csd_spec"):
+                ck(getattr(lib, sc.SYMBOL[entry])(ctx, ptr(o[sc.READS[entry]]), F, sc.PEAK_GROUP, ptr(o[entry]), C.byref(got)))
+                assert got.value == o[entry].shape[0], (r.name, entry)
             else:
                 assert entry == "checksum_add"
                 ck(lib.sgx_checksum_add(ctx, ptr(o["stft"]), o["stft"].numel() * 4, 0, ptr(o[entry])))
@@ -158,6 +168,7 @@ def open_route(r, **extra):
             assert eng.bands_fused == r.bands_fused, (r.name, eng.bands_fused)
         assert eng.bands_peak_fused == sc.peak_fused(r), (r.name, eng.bands_peak_fused)
         assert eng.istft_supported() == int(sc.istft_served(r)), r.name
+        assert eng.psd_fused == eng.csd_fused == sc.psd_fused(r) == 0, r.name
     except BaseException:
         eng.close()
         raise
@@ -286,6 +297,59 @@ def test_image_on_a_held_stream(gpu, case):
         for run in runs:
             run.img.close()
         eng.close()
+
+
+@pytest.mark.parametrize("case", sc.WELCH_CASES, ids=lambda c: c.name)
+def test_welch_carried_and_pieced_on_a_held_stream(gpu, case):
+    """One column whose float64 sums wait in the context's carry row between ranges, every block's rows taken a few frames at a time (the
+    later pieces resume the block's partial): several rows launches with kernel 11's passes, block launches and a combine per range, all
+    behind the sleep.  The workspace is warmed by a call that carries nothing, so the carry row is grown on the held stream by the call
+    under test; the reference runs on the NULL stream afterwards, on a fresh context."""
+    from spectrogram_rs_amd import SpectrogramEngine
+    torch = gpu.torch
+    plan = ba.welch_ranges(case.W, case.channels // 2, case.cross, case.frames, case.group, True)
+    assert plan.carried and plan.piece and plan.resumed and len(plan.ranges) >= 2
+    short = ba.welch_ranges(case.W, case.channels // 2, case.cross, case.frames, 1, True)
+    assert not short.carried and short.workspace_rows >= plan.workspace_rows      # the warm-up grows the whole workspace, and no carry row
+    kw = dict(window_samples=case.W, hop_samples=case.H, channels=case.channels, large_transforms=True)
+    n = (case.frames - 1) * case.H + case.W
+    fn = "sgx_csd_batch" if case.cross else "sgx_psd_batch"
+
+    def run(eng, pcm, out, seed, group):
+        got = C.c_size_t(0)
+        eng._check(eng._lib.sgx_synth_white_noise(eng._ctx, ptr(pcm), 0, n, case.channels, seed))
+        eng._check(getattr(eng._lib, fn)(eng._ctx, ptr(pcm), n, 0, case.frames, group, ptr(out), C.byref(got)))
+        return got.value
+
+    engines = []
+    try:
+        eng = SpectrogramEngine(es.SR, device=0, **kw)
+        engines.append(eng)
+        assert eng.info.stft_kernel == 11 and eng.info.mags_bytes_per_frame == ba.mags_bytes_per_frame(case.W, eng.pairs)
+        comps = 4 if case.cross else 2
+        assert eng._lib.sgx_set_stream(eng._ctx, None) == 0
+        pcm = buffer(torch, (n * case.channels,), torch.float32, None)
+        scratch = buffer(torch, (case.frames, eng.pairs, eng.M, comps), torch.float32, None)
+        assert run(eng, pcm, scratch, sc.SEED_A, 1) == case.frames                 # the workspace and kernel 11's scratch: another seed's state
+        del scratch
+        torch.cuda.synchronize()
+        pcm.fill_(NAN)
+        held = buffer(torch, (1, eng.pairs, eng.M, comps), torch.float32, -1.0)
+        cols = []
+        hold(gpu, eng, lambda S: cols.append(run(eng, pcm, held, sc.SEED_B, case.group)), case.name)
+        assert cols == [1]
+        ref = SpectrogramEngine(es.SR, device=0, **kw)
+        engines.append(ref)
+        want = buffer(torch, (1, eng.pairs, eng.M, comps), torch.float32, None)
+        pcm2 = buffer(torch, (n * case.channels,), torch.float32, None)
+        assert run(ref, pcm2, want, sc.SEED_B, case.group) == 1
+        torch.cuda.synchronize()
+        assert same_bytes(torch, pcm, pcm2) and bool(torch.isfinite(want).all())
+        assert same_bytes(torch, held, want), (case.name, "differs from the NULL stream's")
+    finally:
+        torch.cuda.synchronize()
+        for e in engines:
+            e.close()
 
 
 def lds_cap(torch):

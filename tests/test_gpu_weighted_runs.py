@@ -5,7 +5,10 @@ rows.  At sgx_set_cu_limit(ctx, 1) -- four workgroups, slot = block -- 203 frame
 and 7 and 64 frames at 7; at a limit of 2, 97 frames (49 jobs in 7 workgroups: a last slot one short) and 203.  Forced weights
 (88, 80, 48, 40), (253, 1, 1, 1) and (1, 1, 1, 253) -- the extreme ones leave some workgroups an empty static run, and where the static
 share is under one job per unit of weight all of them -- under the splits (15, 1), (15, 3) and (16, 0): no pool, an exact partition.  Every
-call goes into a NaN-prefilled payload between guard rows.  The same call three times back to back still holds.  No tolerance is involved.
+call goes into a NaN-prefilled payload between guard rows.  The same call three times back to back still holds.  The consumers that launch
+the rows kernel into the workspace (tests/test_gpu_claimed_runs.py: CONSUMERS) are held to their own bytes behind the equal static split
+in the same way, and on the whole device one sgx_psd_batch call whose range is long enough for the automatic, measured weights equals
+the stage over rows of the equal static split.  No tolerance is involved.
 Run with -m gpu on an MI355X."""
 import ctypes as C
 
@@ -15,18 +18,19 @@ import pytest
 import bounds_arena as ba
 import oracle
 from spectrogram_rs_amd import SgxError, SpectrogramEngine, _lib
-from test_gpu_bounds import Arena, dtype_of, elem_of, row_bytes, run, words
+from test_gpu_bounds import Arena, bank_of, dtype_of, elem_of, row_bytes, rows_of, run, words
+from test_gpu_claimed_runs import CONSUMERS, ROWS_KINDS, finite
 
 pytestmark = pytest.mark.gpu
 
 W, SR = 2048, 48000.0
 SHAPES = [(1, 203, 0), (1, 203, 7), (1, 64, 7), (2, 97, 0), (2, 203, 0)]     # (cu limit, frames of the call, first_frame)
-KINDS = ["stft", "f16", "complex"]
+KINDS = ROWS_KINDS + list(CONSUMERS)
 WEIGHTS = [(88, 80, 48, 40), (253, 1, 1, 1), (1, 1, 1, 253)]
 SPLITS = [(15, 1), (15, 3), (16, 0)]
 EQUAL = (64, 64, 64, 64)
 NAN_F16 = 0x7E007E00
-PREFILL = {"f32": ba.NAN_WORD, "f16": NAN_F16}
+PREFILL = {"f32": ba.NAN_WORD, "f16": NAN_F16, "u8": ba.BYTE_FILL * 0x01010101}
 
 
 @pytest.fixture(scope="module")
@@ -38,10 +42,13 @@ def torch_cuda():
     torch.cuda.empty_cache()
 
 
-def open_engine(hop, channels=1):
-    eng = SpectrogramEngine(SR, window_samples=W, hop_samples=hop, channels=channels, device=0, gradient="viridis")
+def open_engine(hop, channels=1, kind="stft"):
+    eng = SpectrogramEngine(SR, window_samples=W, hop_samples=hop, channels=channels, device=0, gradient="viridis", **CONSUMERS.get(kind, {}))
     if channels == 1:
         assert eng.info.stft_kernel == 2 and eng.info.render_path & 8, "the real-input 4096-point kernel must be the one that runs"
+    assert eng.psd_fused == 0
+    if CONSUMERS.get(kind):     # every consumer of this context takes the rows from the workspace
+        assert eng.info.render_path & 1 == 0 and eng.bands_fused == 0 and eng.bands_peak_fused == 0 and bank_of(eng).fused == 0
     return eng
 
 
@@ -51,7 +58,7 @@ def stream(torch, hop, seed):
 
 
 def in_arena(torch, eng, kind, dev, first, n, sync=True):
-    arena = Arena(torch, n * row_bytes(eng, kind), row_bytes(eng, kind), False, PREFILL[elem_of(kind)])
+    arena = Arena(torch, rows_of(kind, n) * row_bytes(eng, kind), row_bytes(eng, kind), False, PREFILL[elem_of(kind)])
     run(eng, kind, dev, first, n, out=arena.payload(dtype_of(torch, kind)).view(-1))
     if sync:
         torch.cuda.synchronize()
@@ -62,7 +69,7 @@ def equal_static(torch, eng, kind, dev, first, n):
     eng.set_run_weights(EQUAL)
     eng.set_run_claim(16, 0)
     want = words(torch, run(eng, kind, dev, first, n)).clone()
-    assert not bool(torch.isnan(want.view(torch.float32 if kind != "f16" else torch.float16)).any())
+    assert finite(torch, kind, want)
     return want
 
 
@@ -70,7 +77,7 @@ def equal_static(torch, eng, kind, dev, first, n):
 @pytest.mark.parametrize("hop", [256, 100])
 def test_every_weighted_deal_writes_the_equal_static_split_s_bytes(torch_cuda, hop, kind):
     torch = torch_cuda
-    eng = open_engine(hop)
+    eng = open_engine(hop, kind=kind)
     dev = stream(torch, hop, 0x51A7 + hop)
     for limit, n, first in SHAPES:
         eng.set_cu_limit(limit)
@@ -100,18 +107,50 @@ def test_the_same_weighted_call_three_times_back_to_back(torch_cuda, hop):
     dev = stream(torch, hop, 0x51A8 + hop)
     eng.set_cu_limit(2)
     n, first = 203, 7
-    want = {kind: equal_static(torch, eng, kind, dev, first, n) for kind in KINDS}
+    back_to_back = ROWS_KINDS[:2] + ["psd_3"] + ROWS_KINDS[2:] + ["psd_3"]      # (the Welch call: the same kernel into the workspace, the same counter)
+    want = {kind: equal_static(torch, eng, kind, dev, first, n) for kind in back_to_back}
     outs = []
     for w, split in (((88, 80, 48, 40), (15, 3)), ((253, 1, 1, 1), (16, 0)), ((1, 1, 1, 253), (15, 1))):
         eng.set_run_weights(w)
         eng.set_run_claim(*split)
         for rep in range(3):        # enqueued back to back: nothing waits between the launches
-            for kind in KINDS:
+            for kind in back_to_back:
                 outs.append((w, split, rep, kind, in_arena(torch, eng, kind, dev, first, n, sync=False)))
     torch.cuda.synchronize()
     for w, split, rep, kind, arena in outs:
         assert arena.guards_intact(), (hop, w, split, rep, kind)
         assert torch.equal(arena.payload(), want[kind]), (hop, w, split, rep, kind, "differs from the equal static split")
+
+
+def test_a_welch_range_under_the_automatic_measured_weights(torch_cuda):
+    """The whole device, nothing forced: a mono W 2048, hop 256 context and a call of 2 * (3 * 4 * n_cu) - 3 frames -- 12 n_cu - 1 frame
+    pairs, three to a workgroup and four workgroups on every compute unit, the last pair of one frame.  At group 5 the call is one range
+    (bounds_arena.welch_ranges), so the rows launch into the workspace is one of that many frames and takes the measured slot weights,
+    which ride in the LUT and seed words of the kernel's arguments.  Its means equal the stage over rows of the equal static split."""
+    torch = torch_cuda
+    eng = open_engine(256)
+    n_cu = eng.cu_limit
+    assert n_cu == torch.cuda.get_device_properties(0).multi_processor_count
+    n, group = 2 * (3 * 4 * n_cu) - 3, 5
+    plan = ba.welch_ranges(W, 1, False, n, group, True)
+    assert len(plan.ranges) == 1 and plan.ranges[0].pieces == ((0, n, False),), "one rows launch of all the frames"
+    auto = eng.run_weights(n)
+    assert auto != EQUAL and auto == eng.run_weights(1_000_000), "the measured weights engage for a rows call of the range's size"
+    # (a few pairs more than four per compute unit would not do: 4 n_cu + 2 pairs run two to a workgroup in 2 n_cu + 1 workgroups,
+    # fewer than three per compute unit, which is the equal deal)
+    assert eng.run_weights(2 * 4 * n_cu + 3) == EQUAL
+    dev = eng.white_noise((n - 1) * 256 + W, seed=0x51A9)
+    got = eng.psd_batch(dev, group)
+    eng.set_run_claim(16, 0)
+    eng.set_run_weights(EQUAL)
+    assert eng.run_weights(n) == EQUAL and eng.run_claim(n) == (16, 0)
+    rows = eng.stft_batch(dev)
+    want = eng.psd_mags(rows, group)
+    assert got.shape == want.shape == (-(-n // group), 1, eng.M, 2)
+    assert torch.equal(words(torch, got), words(torch, want)), "the means behind the weighted deal differ from the stage over the equal static split's rows"
+    # and the forced equal static split behind the same call
+    assert torch.equal(words(torch, eng.psd_batch(dev, group)), words(torch, want))
+    eng.close()
 
 
 def test_the_automatic_weights_and_the_setter_s_arguments(torch_cuda):

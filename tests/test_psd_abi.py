@@ -41,8 +41,22 @@ def test_header_declares_the_six_calls():
                   "35 * 2^-24", "group = 0: SGX_ERR_INVALID_ARG", "SIZE_MAX", "number of COLUMNS",
                   "(A * S1 / W)^2", "p * W^2 / (2 * S1^2)", "p * W^2 / (2 * fs * S2)", "No logarithm, no dB",
                   "[n_out][pairs][M][2]", "[n_out][pairs][M][4]", "16-byte aligned", "SGX_ERR_UNSUPPORTED", "(v, v)",
-                  "[n_frames][pairs][M][2][2]", "nothing waits on the host", "192 MiB workspace", "one float64 row [pairs][M][4]"):
+                  "[n_frames][pairs][M][2][2]", "nothing waits on the host", "192 MiB workspace", "one float64 row [pairs][M][4]",
+                  "tests/test_gpu_psd.py", "tests/test_gpu_bounds.py", "test_gpu_stream_routes.py", "test_gpu_far_offsets.py",
+                  "test_gpu_channel_counts.py", "test_gpu_cu_counts.py"):
         assert words in flat, words
+
+
+def test_header_says_the_workspace_routes_take_the_rows_deal():
+    h = _read("include", "sgx.h")
+    flat = re.sub(r"\s*\n \*\s*", " ", h)
+    claim = flat[flat.index("Diagnostic: how the rows calls"):flat.index("SGX_API int sgx_set_run_claim")]
+    weights = flat[flat.index("Diagnostic: the weights of those calls"):flat.index("SGX_API int sgx_set_run_weights")]
+    for words in ("The rows launches of the workspace routes take the same deal", "sgx_psd_batch always", "SGX_FLAG_NO_FUSED_RENDER",
+                  "tests/test_gpu_claimed_runs.py", "holds those consumers to it"):
+        assert words in claim, words
+    for words in ("the rows launches of the workspace routes take the same deal", "the automatic one included", "tests/test_gpu_weighted_runs.py"):
+        assert words in weights, words
 
 
 def test_library_exports_the_six_calls():

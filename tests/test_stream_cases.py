@@ -3,6 +3,7 @@ edge_signals.ROUTES is in it, with every entry point the row's route serves, no 
 wrong stream is taken by some case; the stand-alone cases name every kernel body of the pixel stage."""
 import collections
 
+import bounds_arena as ba
 import edge_signals as es
 import far_offsets as fo
 import stream_cases as sc
@@ -17,13 +18,16 @@ def test_every_row_of_routes_is_in_the_table():
 
 def test_every_entry_point_the_route_serves_is_listed():
     rows = sc.by_row()
-    always = (set(sc.BATCH) | set(sc.STAGE)) - {"fbank_cross"}
-    assert {"fbank", "fbank_mags", "fbank_cross_spec"} <= always
+    always = (set(sc.BATCH) | set(sc.STAGE)) - {"fbank_cross", "csd_3"}
+    assert {"fbank", "fbank_mags", "fbank_cross_spec", "psd_3", "psd_mags", "csd_spec"} <= always
     for r in es.ROUTES:
         listed = set(rows[r.name])
         assert always <= listed, (r.name, always - listed)
         # the cross sums from PCM: every context with an (l, r) pair (the stage serves the mono rows as well)
         assert ("fbank_cross" in listed) == (r.channels >= 2), r.name
+        # the Welch cross means from PCM likewise (sgx_csd_spec serves the mono rows)
+        assert ("csd_3" in listed) == (r.channels >= 2), r.name
+        assert sc.psd_fused(r) == 0
         # the inverse: every length an in-LDS kernel serves, i.e. every row but kernel 11's
         assert ("istft" in listed) == (r.kernel != 11), r.name
         assert listed == set(sc.entries_served(r))
@@ -36,7 +40,10 @@ def test_every_entry_point_the_route_serves_is_listed():
     banks = {n for n in exported if n.startswith("sgx_fbank_")} - {"sgx_fbank_create", "sgx_fbank_destroy", "sgx_fbank_filters", "sgx_fbank_fused",
                                                                       "sgx_fbank_cross_fused"}
     assert banks == {"sgx_fbank_batch", "sgx_fbank_mags", "sgx_fbank_cross_batch", "sgx_fbank_cross_spec"}
-    assert enqueue_only | banks | {"sgx_magnitude_in", "sgx_checksum_add"} == set(sc.SYMBOL.values())
+    welch = {n for n in exported if n.startswith(("sgx_psd_", "sgx_csd_"))} - {"sgx_psd_fused", "sgx_csd_fused"}
+    assert welch == {"sgx_psd_batch", "sgx_csd_batch", "sgx_psd_mags", "sgx_csd_spec"}
+    assert enqueue_only | banks | welch | {"sgx_magnitude_in", "sgx_checksum_add"} == set(sc.SYMBOL.values())
+    assert sc.READS["psd_mags"] == "stft" and sc.READS["csd_spec"] == "complex"
     assert set(sc.READS) == {"istft"} | set(sc.STAGE) and set(sc.READS.values()) <= set(sc.BATCH)
     assert sc.HOST_WAITS == {}
 
@@ -44,9 +51,9 @@ def test_every_entry_point_the_route_serves_is_listed():
 def test_no_case_is_listed_twice():
     count = collections.Counter((c.row, c.entry) for c in sc.CASES)
     assert max(count.values()) == 1
-    assert len(sc.CASES) == (len(es.ROUTES) * (len(sc.ENTRIES) - 2) + sum(1 for r in es.ROUTES if r.kernel != 11)
-                             + sum(1 for r in es.ROUTES if r.channels >= 2))
-    for cases in (sc.VIEW_CASES, sc.IMAGE_CASES, sc.PIXEL_CASES):
+    assert len(sc.CASES) == (len(es.ROUTES) * (len(sc.ENTRIES) - 3) + sum(1 for r in es.ROUTES if r.kernel != 11)
+                             + 2 * sum(1 for r in es.ROUTES if r.channels >= 2))
+    for cases in (sc.VIEW_CASES, sc.IMAGE_CASES, sc.PIXEL_CASES, sc.WELCH_CASES):
         names = [c.name for c in cases]
         assert len(names) == len(set(names))
     assert len({n for n, _, _ in sc.REBIND_CASES}) == len(sc.REBIND_CASES)
@@ -95,6 +102,21 @@ def test_every_helper_pass_is_taken_by_some_case():
     assert sc.helpers(es.ROUTE["k16_mono_h512"], "fbank", False, False) == {"k16_plane", "workspace", "workspace_fbank"}
     assert sc.helpers(es.ROUTE["bluestein_w23"], "fbank_cross", False, False) == {"ladder", "workspace", "workspace_fbank_cross"}
     assert sc.helpers(es.ROUTE["k1r_h256"], "fbank_mags", True, True) == set()
+    # the Welch calls: never fused -- the rows into the workspace behind the rows' own helpers on EVERY row, the 4096-point kernels
+    # included, then block partials and the combine; the stages are those two kernels alone
+    welch = {"workspace_psd_blocks", "workspace_psd_combine"}
+    for h in welch:
+        assert {e for _, e in taken[h]} == {"psd_3", "csd_3", "psd_mags", "csd_spec"}
+        assert {row for row, e in taken[h] if e == "psd_3"} == {r.name for r in es.ROUTES}
+        assert {row for row, e in taken[h] if e == "csd_3"} == {r.name for r in es.ROUTES if r.channels >= 2}
+    for r in es.ROUTES:
+        for fused in (False, True):
+            assert sc.helpers(r, "psd_3", fused, fused) == sc.rows_helpers(r) | {"workspace"} | welch, r.name
+            assert sc.helpers(r, "psd_mags", fused, fused) == sc.helpers(r, "csd_spec", fused, fused) == welch, r.name
+    assert sc.helpers(es.ROUTE["k1_ch8"], "csd_3", True, True) == {"deinterleave", "workspace"} | welch
+    assert sc.helpers(es.ROUTE["k16_mono_h512"], "psd_3", False, False) == {"k16_plane", "workspace"} | welch
+    assert sc.helpers(es.ROUTE["bluestein_w23"], "csd_3", False, False) == {"ladder", "workspace"} | welch
+    assert sc.helpers(es.ROUTE["large_w6001_chunks"], "psd_3", False, False) == {"large_passes", "workspace"} | welch
     # one run of a persistent workgroup of the fused peak kernel is one frame here (23 frames on 4 n_cu workgroups): every column of three
     # frames crosses runs, so the combine pass writes every column
     assert sc.FRAMES < 4 * 64
@@ -108,6 +130,16 @@ def test_the_families_are_the_routes_own():
                                                  "generic": 6, "large": 8}
     # the same families far_offsets names one row each of
     assert {sc.family(fo.family_route(f)) for f in fo.FAMILIES} == set(fam.values())
+
+
+def test_the_welch_case_is_carried_and_pieced():
+    assert [c.cross for c in sc.WELCH_CASES] == [False, True]
+    for c in sc.WELCH_CASES:
+        assert (c.W, c.channels, c.frames, c.group) == (32768, 64, 36, ba.WELCH_MAX)      # tests/test_gpu_psd.py's context
+        plan = ba.welch_ranges(c.W, c.channels // 2, c.cross, c.frames, c.group, True)
+        assert plan.carried and plan.piece and plan.resumed
+        assert [(r.reads_carry, r.writes_carry) for r in plan.ranges] == [(False, True), (True, False)]
+        assert sum(len(r.pieces) for r in plan.ranges) >= 3                              # rows launches, each with kernel 11's passes
 
 
 def test_the_stand_alone_cases_cover_the_pixel_stage():
