@@ -51,6 +51,11 @@ extern "C" {
                         n_out: *mut usize) -> c_int;   // the stage alone, from complex rows
     pub fn sgx_psd_fused(ctx: *const SgxCtx) -> c_int;
     pub fn sgx_csd_fused(ctx: *const SgxCtx) -> c_int;
+    // the K strongest spectral maxima per frame, pair and side: (bin, m[bin - 1], m[bin], m[bin + 1]) each, strongest first
+    pub fn sgx_maxima_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                            k: u32, floor: f32, d_max: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][2][K][4]
+    pub fn sgx_maxima_mags(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, k: u32, floor: f32,
+                           d_max: *mut f32) -> c_int;   // the stage alone, from magnitude rows
     pub fn sgx_render_bands(ctx: *mut SgxCtx, d_bands: *const f32, n_columns: usize, d_rgba: *mut u8) -> c_int;   // color_for over band columns
     // filterbanks: weighted sums of bin magnitudes or powers over sparse filters (mel, bark, third octaves ...)
     pub fn sgx_fbank_create(ctx: *mut SgxCtx, n_filters: u32, h_first: *const u32, h_count: *const u32, h_weights: *const f32,

@@ -13,7 +13,7 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
  *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -382,6 +382,36 @@ SGX_API int sgx_psd_mags(sgx_ctx *ctx, const float *d_mags, size_t n_frames, siz
 SGX_API int sgx_csd_spec(sgx_ctx *ctx, const float *d_spec, size_t n_frames, size_t group, float *d_csd, size_t *n_out);
 SGX_API int sgx_psd_fused(const sgx_ctx *ctx);
 SGX_API int sgx_csd_fused(const sgx_ctx *ctx);
+/* ---- The K strongest spectral maxima per frame: where a row's peaks are and how strong ----------------------------------------------
+ * What a tuner, a partial tracker, a sinusoidal model, a landmark fingerprint or a pitch tracker reads off a spectrum (the reference has
+ * none: it draws every bin).  No row reaches the caller: 32 * K bytes per frame and side do.
+ *
+ * Take one frame, pair and side (0 = l, 1 = r).  The row is m[j], j = 0 .. M - 1, exactly the float32 values that sgx_stft_batch stores;
+ * element j is bin k = j + 1.  The order below is part of the definition.
+ *   Candidate.  An interior j (1 <= j <= M - 2) is a candidate when all three hold: m[j] > m[j-1], m[j] >= m[j+1] and m[j] >= floor.  A
+ *     plateau yields its leftmost bin only.  Bins 1 and W - 1 are never candidates: each has a neighbour that is not stored.  Where
+ *     M < 3 there are none.
+ *   Order.  Candidates are ordered by descending m[j], ties by ascending j; the first K are the result.  The output is therefore a pure
+ *     function of the row, bit for bit: independent of route, launch geometry, compute-unit limit, run claim, run weights, stream, chunk
+ *     seams and any split of a call (tests/test_gpu_maxima.py; numpy restates it with two masks and a lexsort: tests/maxima_reference.py).
+ *   Record.  Each of the K results is four floats, ((float)k, m[j-1], m[j], m[j+1]).  The library applies no interpolation, logarithm
+ *     or division: parabolic, log-parabolic or Gaussian refinement of frequency and level is the caller's, from the three values.  Slots
+ *     beyond the number of candidates hold (0, 0, 0, 0); k = 0 is never a stored bin.  All K slots are always written.
+ *   Arguments.  K from 1 to 64: K = 0 or K > 64 is SGX_ERR_INVALID_ARG.  floor is finite and >= 0, else SGX_ERR_INVALID_ARG.  The output
+ *     for non-finite or negative row values (the stage call only) is unspecified.
+ * Scaling as the rows': a stationary sinusoid of amplitude A at a bin centre has the centre value A * S1 / W, S1 = sum of sgx_window.
+ *
+ * sgx_maxima_batch: d_max [n_out][pairs][2][K][4] float, 16-byte aligned (else SGX_ERR_INVALID_ARG, nothing written).  A mono stream
+ *   holds the same records on both sides (with SGX_FLAG_PAIRED_FRAMES each side holds what its rows hold).  first_frame, max_frames and
+ *   *n_out as sgx_stft_batch: too few samples is *n_out = 0, not an error; a null buffer is SGX_ERR_INVALID_ARG; n_out may be NULL.
+ * sgx_maxima_mags: the stage alone over rows already on the device, d_mags [n_columns][pairs][M][2] as sgx_stft_batch writes them, into
+ *   d_max [n_columns][pairs][2][K][4].  Every W the library accepts, SGX_FLAG_LARGE_TRANSFORM lengths included.  n_columns == 0: SGX_OK.
+ * Stream-ordered and asynchronous; nothing waits on the host (a grown workspace may, as elsewhere); every kernel of a call goes onto the
+ * context's stream.  Device memory beyond the caller's buffers is the 192 MiB workspace only: the rows of a chunk of frames by their own
+ * route, then one selection kernel over them (a wave per row).  There is no fused mode and no flag. */
+SGX_API int sgx_maxima_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                             uint32_t k, float floor, float *d_max, size_t *n_out);
+SGX_API int sgx_maxima_mags(sgx_ctx *ctx, const float *d_mags, size_t n_columns, uint32_t k, float floor, float *d_max);
 /* ---- filterbanks: weighted sums of bin magnitudes or powers over overlapping filters ---------------------------------------------
  * What a mel, bark or ERB front end, a third-octave analyser, a chroma vector or an A-weighted level is (the reference has none: every
  * reduction there is magnitude_in, an unweighted mean).

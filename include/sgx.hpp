@@ -225,6 +225,42 @@ public:
     int psd_fused() const { return sgx_psd_fused(ctx_); }
     int csd_fused() const { return sgx_csd_fused(ctx_); }
 
+    // where the peaks of every frame are and how strong: per frame and side (0 = l, 1 = r) the k strongest local maxima of the row,
+    // strongest first, each {bin, m[bin - 1], m[bin], m[bin + 1]}; slots beyond the candidates are {0, 0, 0, 0} (sgx_maxima_batch;
+    // include/sgx.h states the candidates and their order; refinement of frequency and level from the three values is the caller's)
+    using Maximum = std::array<float, 4>;
+    std::vector<std::array<std::vector<Maximum>, 2>> maxima_stream(const StereoMagnitude *lr, std::size_t n, uint32_t k, float floor = 0.0f)
+    {
+        if (k < 1 || k > 64) throw Error(SGX_ERR_INVALID_ARG, "maxima_stream: k must be 1 .. 64");
+        const std::size_t frames = sgx_num_frames(ctx_, n);
+        std::vector<std::array<std::vector<Maximum>, 2>> out(frames);
+        if (!frames) return out;
+        reserve(n * 2 * sizeof(float), frames * 2 * k * 4 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        int rc = sgx_maxima_batch(ctx_, d_in_, n, 0, frames, k, floor, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(frames * 2 * k * 4);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < frames; ++f)
+            for (std::size_t s = 0; s < 2; ++s) {
+                out[f][s].resize(k);
+                for (std::size_t r = 0; r < k; ++r) {
+                    const float *b = &flat[((f * 2 + s) * k + r) * 4];
+                    out[f][s][r] = {b[0], b[1], b[2], b[3]};
+                }
+            }
+        return out;
+    }
+    // the stage alone over rows already on the device (DEVICE pointers; stream-ordered, not waited for)
+    // (sgx_maxima_mags: [n_columns][pairs][M][2] -> [n_columns][pairs][2][k][4], d_max 16-byte aligned)
+    void maxima_mags(const float *d_mags, std::size_t n_columns, uint32_t k, float floor, float *d_max)
+    {
+        const int rc = sgx_maxima_mags(ctx_, d_mags, n_columns, k, floor, d_max);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+    }
+
     // the complex (L, R) spectra behind process_stream's magnitudes for every complete frame of `lr`: frames x (W-1) bins of
     // {L, R} (sgx_stft_batch_complex)
     std::vector<std::vector<std::array<std::complex<float>, 2>>> process_stream_complex(const StereoMagnitude *lr, std::size_t n)

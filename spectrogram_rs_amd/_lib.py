@@ -117,6 +117,8 @@ SIGNATURES = [
     ("sgx_csd_spec", C.c_int, [_ctx, _vp, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_psd_fused", C.c_int, [_ctx]),
     ("sgx_csd_fused", C.c_int, [_ctx]),
+    ("sgx_maxima_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, C.c_uint32, C.c_float, _vp, C.POINTER(_sz)]),
+    ("sgx_maxima_mags", C.c_int, [_ctx, _vp, _sz, C.c_uint32, C.c_float, _vp]),
     ("sgx_render_bands", C.c_int, [_ctx, _vp, _sz, _vp]),
     ("sgx_fbank_create", C.c_int, [_ctx, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     ("sgx_fbank_destroy", None, [_vp]),

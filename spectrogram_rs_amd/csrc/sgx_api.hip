@@ -7,6 +7,7 @@
 
 #include "sgx_fbank.hpp"
 #include "sgx_gradients.inc"
+#include "sgx_maxima.hpp"
 #include "sgx_psd.hpp"
 #include "sgx_internal.hpp"
 
@@ -488,6 +489,15 @@ int psd_stage(sgx_ctx *c, const char *who, bool cross, const float *d_rows, size
     const int rc = psd_reduce(c, who, cross, n_frames, group, false, [&](size_t f, size_t) { return d_rows + f * row_floats; }, d_out);
     if (rc != SGX_OK) return rc;
     if (n_out) *n_out = (size_t)sgx::psd::geometry(n_frames, group).columns();
+    return SGX_OK;
+}
+
+// sgx_maxima_batch and sgx_maxima_mags: what both calls refuse before anything is enqueued
+int check_maxima(sgx_ctx *c, const char *who, uint32_t k, float floor, const float *d_max)
+{
+    if (k < 1 || k > sgx::maxima::kMaxK) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": k must be 1 .. 64");
+    if (!(floor >= 0.0f) || std::isinf(floor)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": floor must be finite and >= 0");
+    if ((uintptr_t)d_max & 15u) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": d_max must be 16-byte aligned");
     return SGX_OK;
 }
 
@@ -1155,6 +1165,44 @@ int sgx_psd_mags(sgx_ctx *c, const float *d_mags, size_t n_frames, size_t group,
 int sgx_csd_spec(sgx_ctx *c, const float *d_spec, size_t n_frames, size_t group, float *d_csd, size_t *n_out)
 {
     return psd_stage(c, "sgx_csd_spec", true, d_spec, n_frames, group, d_csd, n_out);
+}
+
+// ---- the K strongest spectral maxima of every row (sgx_maxima.hpp): the rows through the workspace, the selection kernel over them ------
+
+int sgx_maxima_mags(sgx_ctx *c, const float *d_mags, size_t n_columns, uint32_t k, float floor, float *d_max)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    const int rc = check_maxima(c, "sgx_maxima_mags", k, floor, d_max);
+    if (rc != SGX_OK) return rc;
+    if (n_columns == 0) return SGX_OK;
+    if (!d_mags || !d_max) return fail(c, SGX_ERR_INVALID_ARG, "sgx_maxima_mags: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = sgx::maxima::launch_maxima(c, d_mags, n_columns * c->pairs, k, floor, d_max);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_maxima_mags: kernel launch");
+    return SGX_OK;
+}
+
+int sgx_maxima_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, uint32_t k, float floor,
+                     float *d_max, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (c) {
+        const int bad = check_maxima(c, "sgx_maxima_batch", k, floor, d_max);
+        if (bad != SGX_OK) return bad;
+    }
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_maxima_batch", n_samples, first_frame, max_frames, d_pcm, d_max, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    // two kernels: the rows of a chunk of frames in the bounded workspace, by the rows' own route, then the selection kernel over them
+    rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+        hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_maxima_batch: stft launch");
+        e = sgx::maxima::launch_maxima(c, c->d_ws_mags.get(), m * c->pairs, k, floor, d_max + done * (size_t)c->pairs * 2 * k * 4);
+        return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_maxima_batch: selection launch");
+    });
+    if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = n;
+    return SGX_OK;
 }
 
 int sgx_render_bands(sgx_ctx *c, const float *d_bands, size_t n_columns, uint8_t *d_rgba)

@@ -401,6 +401,41 @@ class SpectrogramEngine:
         """1 when csd_batch runs one kernel from PCM to block partials, 0 on the workspace route"""
         return self._check(self._lib.sgx_csd_fused(self._ctx))
 
+    # ---- spectral maxima --------------------------------------------------------------------
+    def maxima_batch(self, pcm, k: int, floor: float = 0.0, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [frames][pairs][2][k][4] float32: per frame, pair and side the k strongest local maxima of stft_batch's row, strongest
+        first (ties: the lower bin), each as (bin, m[bin - 1], m[bin], m[bin + 1]); slots beyond the candidates are zero.  A candidate
+        is > its left neighbour, >= its right one and >= floor (include/sgx.h).  Refinement of frequency and level is the caller's."""
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        k = int(k)
+        out = self._out(out, (n, self.pairs, 2, k, 4), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_maxima_batch(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n, C.c_uint32(k),
+                                                   C.c_float(floor), C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return out
+
+    def maxima_mags(self, mags, k: int, floor: float = 0.0, out=None):
+        """The stage of maxima_batch alone: float32 [columns][pairs][M][2] rows, as stft_batch writes them -> [columns][pairs][2][k][4]"""
+        import torch
+
+        row_floats = self.pairs * self.M * 2
+        assert mags.dtype == torch.float32 and mags.numel() % row_floats == 0, "expected whole float32 rows of this context"
+        n = mags.numel() // row_floats
+        k = int(k)
+        out = self._out(out, (n, self.pairs, 2, k, 4), torch.float32)
+        if n:
+            self._check(self._lib.sgx_maxima_mags(self._ctx, self._dev_f32(mags), n, C.c_uint32(k), C.c_float(floor),
+                                                  C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- filterbanks ------------------------------------------------------------------------
     def filterbank(self, first, count, weights, power: int = 2) -> "FilterBank":
         """A bank of sparse filters over the M stored bins (include/sgx.h states the definition): filter f weighs the bins
