@@ -56,6 +56,13 @@ extern "C" {
                             k: u32, floor: f32, d_max: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][2][K][4]
     pub fn sgx_maxima_mags(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, k: u32, floor: f32,
                            d_max: *mut f32) -> c_int;   // the stage alone, from magnitude rows
+    // per-bin order statistics over groups of frames: the word of rank floor(q * (n - 1) + 0.5) of every column, bin and side, NaN last
+    pub fn sgx_quantile_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                              group: usize, q: *const f64, n_q: u32, d_out: *mut f32,
+                              n_out: *mut usize) -> c_int;   // PCM -> [columns][n_q][pairs][M][2]
+    pub fn sgx_quantile_mags(ctx: *mut SgxCtx, d_mags: *const f32, n_frames: usize, group: usize, q: *const f64, n_q: u32,
+                             d_out: *mut f32, n_out: *mut usize) -> c_int;   // the stage alone, from magnitude rows; any group
+    pub fn sgx_quantile_max_group(ctx: *const SgxCtx) -> usize;   // the longest column sgx_quantile_batch takes
     pub fn sgx_render_bands(ctx: *mut SgxCtx, d_bands: *const f32, n_columns: usize, d_rgba: *mut u8) -> c_int;   // color_for over band columns
     // filterbanks: weighted sums of bin magnitudes or powers over sparse filters (mel, bark, third octaves ...)
     pub fn sgx_fbank_create(ctx: *mut SgxCtx, n_filters: u32, h_first: *const u32, h_count: *const u32, h_weights: *const f32,

@@ -13,7 +13,7 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_quantile_batch, sgx_quantile_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
  *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -412,6 +412,49 @@ SGX_API int sgx_csd_fused(const sgx_ctx *ctx);
 SGX_API int sgx_maxima_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
                              uint32_t k, float floor, float *d_max, size_t *n_out);
 SGX_API int sgx_maxima_mags(sgx_ctx *ctx, const float *d_mags, size_t n_columns, uint32_t k, float floor, float *d_max);
+/* ---- Per-bin order statistics over groups of frames: percentile spectra, the median spectrum, the per-bin minimum ---------------------
+ * The level exceeded 90 %, 50 % and 10 % of the time per bin (L90, L50, L10), the median a spectral gate or a noise estimator uses
+ * because one click does not move it, the minimum of minimum-statistics noise tracking.  None of them follows from a mean or a maximum.
+ * No row reaches the caller: n_q rows per column do.
+ *
+ * Frames, columns, group, first_frame, max_frames and *n_out exactly as sgx_psd_batch: F frames of the call exist; column j covers frames
+ * first_frame + [j * group, min((j + 1) * group, F)) and holds n_j of them, the last column may be short; group = 0 is
+ * SGX_ERR_INVALID_ARG; *n_out is the number of columns.
+ * Take one column, pair, stored bin and side.  The sample is v[t], t = 0 .. n_j - 1: exactly the float32 words sgx_stft_batch stores for
+ * those frames.
+ *   Order.  Words are ordered by the key key(u) = u ^ (u >> 31 ? 0xffffffff : 0x80000000) of their bit pattern u, compared as unsigned
+ *     integers.  The resulting total order is -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  On the engine's own rows (>= +0, or NaN
+ *     for non-finite PCM) this is the numeric order with NaN last, i.e. np.sort.
+ *   Rank.  q[i] in [0, 1] for i = 0 .. n_q - 1, n_q from 1 to 16; the values may be in any order and may repeat.  The rank is
+ *     k_i = (size_t)floor(q[i] * (double)(n_j - 1) + 0.5): one double product, one add, one floor.  That is nearest rank with a half going
+ *     up: n_j = 2 and q = 0.5 gives k = 1.  q = 0 is the column's minimum and q = 1 its maximum.  n_q = 0, n_q > 16, or any q that is NaN
+ *     or outside [0, 1] is SGX_ERR_INVALID_ARG: nothing is written or enqueued.
+ *   Result.  The word of rank k_i in that order, bits unchanged.  There is no interpolation between ranks: a caller who wants it asks for
+ *     both neighbours.  The output is therefore a pure function of the rows, bit for bit: independent of route, launch geometry,
+ *     compute-unit limit, run claim, run weights, stream, chunk seams and any split of a call at a column boundary
+ *     (tests/test_gpu_quantile.py; numpy restates it with a sort along the frame axis: tests/quantile_reference.py).
+ *
+ * q is a host array, read before the call returns.  d_out is [n_out][n_q][pairs][M][2] float (no alignment beyond float's): every
+ * (column, q) is one row in sgx_stft_batch's layout, so sgx_render_mags, sgx_maxima_mags, sgx_fbank_mags and sgx_magnitude_in take a
+ * percentile row as they take any other row.  A mono stream holds what its rows hold: (v, v), or with SGX_FLAG_PAIRED_FRAMES each side
+ * its own.  Too few samples is *n_out = 0, not an error; a null buffer or a null q is SGX_ERR_INVALID_ARG; n_out may be NULL.
+ * sgx_quantile_batch: the rows of a range of whole columns go by their own route into the 192 MiB workspace, then the selection kernel
+ *   runs over the range and writes straight into d_out.  A quantile does not decompose, so a column is not carried across ranges: a call
+ *   with min(group, F) > sgx_quantile_max_group(ctx) is SGX_ERR_UNSUPPORTED, sgx_last_error names the cap, nothing is written or
+ *   enqueued.  Device memory beyond the caller's buffers is the workspace alone, whatever F is.
+ * sgx_quantile_max_group: that cap, 192 MiB / the bytes of one frame's rows ([pairs][M][2] floats), at least 1: 12 294 frames at W 2048
+ *   with 1 or 2 channels.
+ * sgx_quantile_mags: the stage alone over rows already on the device, d_mags [n_frames][pairs][M][2] as sgx_stft_batch writes them.  Any
+ *   group up to SIZE_MAX (one column), every W the library accepts, no workspace: also the way out for a caller whose column exceeds the
+ *   cap.  n_frames == 0: *n_out = 0 and SGX_OK.
+ * Stream-ordered and asynchronous; nothing waits on the host (a grown workspace may, as elsewhere); every kernel of a call goes onto the
+ * context's stream.  A column of at most 512 frames is selected in LDS, a longer one where its rows lie (32 passes over them).  There is
+ * no fused mode and no flag. */
+SGX_API int sgx_quantile_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                               size_t group, const double *q, uint32_t n_q, float *d_out, size_t *n_out);
+SGX_API int sgx_quantile_mags(sgx_ctx *ctx, const float *d_mags, size_t n_frames, size_t group,
+                              const double *q, uint32_t n_q, float *d_out, size_t *n_out);
+SGX_API size_t sgx_quantile_max_group(const sgx_ctx *ctx);
 /* ---- filterbanks: weighted sums of bin magnitudes or powers over overlapping filters ---------------------------------------------
  * What a mel, bark or ERB front end, a third-octave analyser, a chroma vector or an A-weighted level is (the reference has none: every
  * reduction there is magnitude_in, an unweighted mean).

@@ -261,6 +261,43 @@ public:
         if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
     }
 
+    // per-bin order statistics over groups of `group` frames: columns x q.size() rows of (W-1) bins of {l, r}, each the word of rank
+    // floor(q * (n - 1) + 0.5) among the column's n frames, NaN last (sgx_quantile_batch; include/sgx.h states order and rank; a column
+    // longer than quantile_max_group() is refused)
+    std::vector<std::vector<Output>> quantile_stream(const StereoMagnitude *lr, std::size_t n, std::size_t group, const std::vector<double> &q)
+    {
+        if (group == 0) throw Error(SGX_ERR_INVALID_ARG, "quantile_stream: group is 0");
+        if (q.empty() || q.size() > 16) throw Error(SGX_ERR_INVALID_ARG, "quantile_stream: 1 .. 16 quantiles");
+        const std::size_t frames = sgx_num_frames(ctx_, n), m = num_output_frequencies(), cols = frames ? (frames - 1) / group + 1 : 0;
+        std::vector<std::vector<Output>> out(cols, std::vector<Output>(q.size(), Output(m)));
+        if (!cols) return out;
+        reserve(n * 2 * sizeof(float), cols * q.size() * m * 2 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        int rc = sgx_quantile_batch(ctx_, d_in_, n, 0, frames, group, q.data(), (uint32_t)q.size(), d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(cols * q.size() * m * 2);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < cols; ++f)
+            for (std::size_t i = 0; i < q.size(); ++i)
+                for (std::size_t j = 0; j < m; ++j) {
+                    const float *b = &flat[((f * q.size() + i) * m + j) * 2];
+                    out[f][i][j] = {b[0], b[1]};
+                }
+        return out;
+    }
+    // the stage alone over rows already on the device (DEVICE pointers; stream-ordered, not waited for); any group
+    // (sgx_quantile_mags: [n_frames][pairs][M][2] -> [columns][n_q][pairs][M][2]); answers the number of columns
+    std::size_t quantile_mags(const float *d_mags, std::size_t n_frames, std::size_t group, const std::vector<double> &q, float *d_out)
+    {
+        std::size_t got = 0;
+        const int rc = sgx_quantile_mags(ctx_, d_mags, n_frames, group, q.data(), (uint32_t)q.size(), d_out, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        return got;
+    }
+    std::size_t quantile_max_group() const { return sgx_quantile_max_group(ctx_); }
+
     // the complex (L, R) spectra behind process_stream's magnitudes for every complete frame of `lr`: frames x (W-1) bins of
     // {L, R} (sgx_stft_batch_complex)
     std::vector<std::vector<std::array<std::complex<float>, 2>>> process_stream_complex(const StereoMagnitude *lr, std::size_t n)

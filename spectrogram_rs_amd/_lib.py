@@ -119,6 +119,9 @@ SIGNATURES = [
     ("sgx_csd_fused", C.c_int, [_ctx]),
     ("sgx_maxima_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, C.c_uint32, C.c_float, _vp, C.POINTER(_sz)]),
     ("sgx_maxima_mags", C.c_int, [_ctx, _vp, _sz, C.c_uint32, C.c_float, _vp]),
+    ("sgx_quantile_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, C.POINTER(C.c_double), C.c_uint32, _vp, C.POINTER(_sz)]),
+    ("sgx_quantile_mags", C.c_int, [_ctx, _vp, _sz, _sz, C.POINTER(C.c_double), C.c_uint32, _vp, C.POINTER(_sz)]),
+    ("sgx_quantile_max_group", _sz, [_ctx]),
     ("sgx_render_bands", C.c_int, [_ctx, _vp, _sz, _vp]),
     ("sgx_fbank_create", C.c_int, [_ctx, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     ("sgx_fbank_destroy", None, [_vp]),

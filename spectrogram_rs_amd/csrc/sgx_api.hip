@@ -9,6 +9,7 @@
 #include "sgx_gradients.inc"
 #include "sgx_maxima.hpp"
 #include "sgx_psd.hpp"
+#include "sgx_quantile.hpp"
 #include "sgx_internal.hpp"
 
 namespace {
@@ -499,6 +500,24 @@ int check_maxima(sgx_ctx *c, const char *who, uint32_t k, float floor, const flo
     if (!(floor >= 0.0f) || std::isinf(floor)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": floor must be finite and >= 0");
     if ((uintptr_t)d_max & 15u) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": d_max must be 16-byte aligned");
     return SGX_OK;
+}
+
+// sgx_quantile_batch and sgx_quantile_mags: what both calls refuse before anything is enqueued
+int check_quantile(sgx_ctx *c, const char *who, size_t group, const double *q, uint32_t n_q)
+{
+    if (group == 0) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": group is 0");
+    if (n_q < 1 || n_q > sgx::quantile::kMaxQ) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": n_q must be 1 .. 16");
+    if (!q) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": q is null");
+    for (uint32_t i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": every q must lie in [0, 1]");
+    return SGX_OK;
+}
+
+// the frames of rows the workspace holds, at least 1: the longest column sgx_quantile_batch selects
+size_t quantile_cap(const sgx_ctx *c)
+{
+    const size_t cap = kWorkspaceBytes / mags_bytes_per_frame(c);
+    return cap < 1 ? 1 : cap;
 }
 
 }  // namespace
@@ -1202,6 +1221,58 @@ int sgx_maxima_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fi
     });
     if (rc != SGX_OK) return rc;
     if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+// ---- per-bin order statistics over groups of frames (sgx_quantile.hpp): the rows of whole columns through the workspace, the selection ----
+
+size_t sgx_quantile_max_group(const sgx_ctx *c) { return c ? quantile_cap(c) : 0; }
+
+int sgx_quantile_mags(sgx_ctx *c, const float *d_mags, size_t n_frames, size_t group, const double *q, uint32_t n_q, float *d_out, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!c) return SGX_ERR_INVALID_ARG;
+    const int rc = check_quantile(c, "sgx_quantile_mags", group, q, n_q);
+    if (rc != SGX_OK) return rc;
+    if (n_frames == 0) return SGX_OK;
+    if (!d_mags || !d_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_quantile_mags: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const size_t g = group < n_frames ? group : n_frames;
+    const hipError_t e = sgx::quantile::launch_quantile(c, d_mags, n_frames, g, q, n_q, d_out);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_quantile_mags: kernel launch");
+    if (n_out) *n_out = (n_frames - 1) / g + 1;
+    return SGX_OK;
+}
+
+int sgx_quantile_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, size_t group, const double *q,
+                       uint32_t n_q, float *d_out, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (c) {
+        const int bad = check_quantile(c, "sgx_quantile_batch", group, q, n_q);
+        if (bad != SGX_OK) return bad;
+    }
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_quantile_batch", n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    // a quantile does not decompose: a column is selected from rows that lie in the workspace together, or not at all
+    const size_t cap = quantile_cap(c), g = group < n ? group : n;
+    if (g > cap)
+        return fail(c, SGX_ERR_UNSUPPORTED, "sgx_quantile_batch: a column of " + std::to_string(g) + " frames exceeds the cap of " + std::to_string(cap) +
+                                                " frames (sgx_quantile_max_group); sgx_quantile_mags takes any group over rows the caller holds");
+    // ranges of whole columns: their rows by the rows' own route into the workspace, then the selection kernel over them into d_out
+    const size_t range = cap / g * g, row_floats = mags_bytes_per_frame(c) / sizeof(float);
+    rc = ensure_workspace(c, range < n ? range : n);
+    for (size_t f = 0; rc == SGX_OK && f < n; f += range) {
+        const size_t m = n - f < range ? n - f : range;
+        hipError_t e = rows_to_workspace(c, d_pcm, first_frame + f, m, total);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_quantile_batch: stft launch");
+        // (m < g: the call's short last column alone in the last range)
+        e = sgx::quantile::launch_quantile(c, c->d_ws_mags.get(), m, g < m ? g : m, q, n_q, d_out + f / g * n_q * row_floats);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_quantile_batch: selection launch");
+    }
+    if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = (n - 1) / g + 1;
     return SGX_OK;
 }
 

@@ -436,6 +436,59 @@ class SpectrogramEngine:
                                                   C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- per-bin order statistics over groups of frames ---------------------------------------
+    @staticmethod
+    def _quantiles(q):
+        q = [float(x) for x in ([q] if isinstance(q, (int, float)) else q)]
+        return (C.c_double * len(q))(*q), len(q)
+
+    def quantile_batch(self, pcm, group: int, q, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [ceil(frames / group)][n_q][pairs][M][2] float32: per bin and side the order statistics of stft_batch's rows over
+        groups of `group` consecutive frames (the last group may be shorter).  q: one value or up to 16 in [0, 1]; the result is the
+        word of rank floor(q * (n - 1) + 0.5) among a column's n words, bits unchanged, NaN last (include/sgx.h states the order).
+        A column longer than quantile_max_group is refused: quantile_mags over stored rows takes any group."""
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        group = int(group)
+        h_q, n_q = self._quantiles(q)
+        cols = -(-n // group) if group > 0 else 0
+        out = self._out(out, (cols, n_q, self.pairs, self.M, 2), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_quantile_batch(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n, min(group, 2 ** 64 - 1),
+                                                     h_q, C.c_uint32(n_q), C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == cols
+        return out
+
+    def quantile_mags(self, mags, group: int, q, out=None):
+        """The stage of quantile_batch alone: float32 [frames][pairs][M][2] rows, as stft_batch writes them -> [columns][n_q][pairs][M][2].
+        Any group (one column at most), no workspace."""
+        import torch
+
+        row_floats = self.pairs * self.M * 2
+        assert mags.dtype == torch.float32 and mags.numel() % row_floats == 0, "expected whole float32 rows of this context"
+        n = mags.numel() // row_floats
+        group = int(group)
+        h_q, n_q = self._quantiles(q)
+        cols = -(-n // group) if group > 0 else 0
+        out = self._out(out, (cols, n_q, self.pairs, self.M, 2), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_quantile_mags(self._ctx, self._dev_f32(mags), n, min(group, 2 ** 64 - 1), h_q, C.c_uint32(n_q),
+                                                    C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == cols
+        return out
+
+    @property
+    def quantile_max_group(self) -> int:
+        """The longest column quantile_batch selects: the frames of rows the 192 MiB workspace holds, at least 1"""
+        return int(self._lib.sgx_quantile_max_group(self._ctx))
+
     # ---- filterbanks ------------------------------------------------------------------------
     def filterbank(self, first, count, weights, power: int = 2) -> "FilterBank":
         """A bank of sparse filters over the M stored bins (include/sgx.h states the definition): filter f weighs the bins
