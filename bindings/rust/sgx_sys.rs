@@ -78,6 +78,11 @@ extern "C" {
                                  d_out: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][n_filters][4]
     pub fn sgx_fbank_cross_spec(fbank: *mut SgxFbank, d_spec: *const f32, n_columns: usize, d_out: *mut f32) -> c_int;   // the stage alone, from complex rows
     pub fn sgx_fbank_cross_fused(fbank: *const SgxFbank) -> c_int;
+    // the flux of a bank: per band (rise_l, rise_r, fall_l, fall_r) of every bin against the same bin `lag` frames earlier
+    pub fn sgx_flux_batch(fbank: *mut SgxFbank, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                                lag: u32, d_out: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][n_filters][4]
+    pub fn sgx_flux_mags(fbank: *mut SgxFbank, d_mags: *const f32, n_frames: usize, lag: u32, d_out: *mut f32) -> c_int;   // the stage alone, from frames of rows
+    pub fn sgx_flux_max_lag(fbank: *const SgxFbank) -> u32;   // the largest lag sgx_flux_batch takes
     pub fn sgx_mel_weights(sample_rate: f64, window_samples: u32, n_mels: u32, f_min: f64, f_max: f64, scale: u32, norm: u32,
                            h_first: *mut u32, h_count: *mut u32, h_weights: *mut f32, n_weights: *mut usize) -> c_int;   // host only
     pub fn sgx_set_gradient(ctx: *mut SgxCtx, h_rgb: *const u8, n: u32, stereo: c_int) -> c_int;

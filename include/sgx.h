@@ -13,7 +13,7 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_quantile_batch, sgx_quantile_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_flux_batch, sgx_flux_mags, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_quantile_batch, sgx_quantile_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
  *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -548,6 +548,56 @@ SGX_API int sgx_fbank_cross_spec(void *fbank, const float *d_spec, size_t n_colu
  * One kernel: W = 2048 with 2 or 2k channels (any hop), without SGX_FLAG_NO_FUSED_RENDER or SGX_FLAG_FORCE_GENERIC, for banks within
  * the size sgx_fbank_fused states.  Same bits either way. */
 SGX_API int sgx_fbank_cross_fused(const void *fbank);
+
+/* The flux of a bank: per band how much of the spectrum rose and how much fell against an earlier frame -- what an onset detector, a beat
+ * tracker, a transient / steady-state splitter or a scene-change trigger reads off a spectrogram.  It is the one reduction here that
+ * compares a frame with another one, and a caller cannot get it from sgx_fbank_batch: the rectification happens per bin, before the
+ * band sum, so a rising partial and a falling one in the same band do not cancel.
+ * Take a bank and a lag from 1 to 64.  Frame t is the absolute frame index of the hop loop (sgx_flux_batch) or the row index in
+ * d_mags (sgx_flux_mags).  Per frame, pair, side and stored bin j
+ *
+ *     x_t[j]  = m (power 1) or rn(m * m) (power 2)      m exactly the float32 that sgx_stft_batch stores: the x of sgx_fbank_batch
+ *     d[j]    = rn(x_t[j] - x_{t - lag}[j])              one float32 subtract, never contracted with the square
+ *     rise[j] = d < 0 ? +0 : d
+ *     fall[j] = d > 0 ? +0 : rn(+0 - d)
+ *
+ * Equal words give (+0, +0), never -0; a NaN in either row gives NaN in both.  Per filter f the record is four sums,
+ *
+ *     out[f] = (rise_l, rise_r, fall_l, fall_r),    each sum_{i < count[f]} w[f][i] * e[first[f] + i]
+ *
+ * in the order defined above for sgx_fbank_batch (the 64 chains from +0, then the tree by halving); count == 0 gives four +0.0f.  A frame
+ * with t < lag has no predecessor: its record is (+0, +0, +0, +0) for every filter, as the onset functions of librosa and madmom leave
+ * their first frames.  The output is a pure function of the two rows and the bank, bit for bit: independent of route, launch geometry,
+ * compute-unit limit, run claim, run weights, stream, range seams and any split of a call (tests/test_gpu_fbank_flux.py; numpy
+ * restates it: tests/flux_reference.py).
+ * On finite rows rise - fall telescopes (it is the difference of two sgx_fbank_batch columns up to rounding), rise + fall is the weighted
+ * L1 distance of the two rows, and rise of a one-filter all-ones bank is the classic full-band spectral flux.
+ * What is not here: no logarithm or compression before the difference (the device's logarithm is not reproducible on the host:
+ * log-flux is a later call), no normalisation, no peak picking.  For infinite row values the arithmetic is IEEE's, but the payload of a
+ * resulting NaN is unspecified.  There is no fused mode, no flag and no query for one.
+ * The three calls take a bank (the first argument is an sgx_fbank handle) and are named sgx_flux_*, as sgx_maxima_* and
+ * sgx_quantile_* carry their own prefix: the names sgx_fbank_* of the library's tables are the bank's own sums and its handle.
+ *
+ * sgx_flux_batch: PCM to the records of every frame of the hop loop.
+ *   d_out [n_out][pairs][n_filters][4] float, 16-byte aligned (else SGX_ERR_INVALID_ARG, nothing written).  A mono stream holds (v, v),
+ *   so rise_l = rise_r; with SGX_FLAG_PAIRED_FRAMES each side is differenced against its own side.
+ * first_frame / max_frames / *n_out as sgx_fbank_batch: too few samples is *n_out = 0, not an error; a null buffer is
+ * SGX_ERR_INVALID_ARG; n_out may be NULL.  The call reads frame first_frame - lag out of the PCM itself: a call with first_frame >= lag
+ * has no zero records, and any split of a call concatenates to the whole call.  lag == 0 or lag > 64 is SGX_ERR_INVALID_ARG, nothing
+ * written or enqueued.  Stream-ordered and asynchronous; nothing waits on the host; every kernel goes onto the context's stream.
+ * Device memory beyond the caller's buffers is the 192 MiB workspace alone: every range of the call puts the rows of its frames and of
+ * the min(lag, first frame of the range) frames before them into it by the rows' own route, then one stage kernel writes the range's
+ * records.  The head rows of a range are recomputed, not carried.
+ * sgx_flux_max_lag: min(64, floor(192 MiB / bytes of one frame's rows) - 1), 0 where fewer than two frames' rows fit, 0 for a
+ * null bank.  It is 64 on every in-LDS length and 23 at W = 2^20 with two channels.  sgx_flux_batch with lag above it is
+ * SGX_ERR_UNSUPPORTED: sgx_last_error names the cap and points to sgx_flux_mags; nothing is written or enqueued.
+ * sgx_flux_mags: the stage alone over rows already on the device, d_mags [n_frames][pairs][M][2] as sgx_stft_batch writes them
+ * (frames, not flattened columns: the predecessor of (t, pair p) is (t - lag, pair p)) -> d_out [n_frames][pairs][n_filters][4].  Any
+ * lag from 1 to 64 at every W the library accepts; n_frames == 0 is SGX_OK. */
+SGX_API int sgx_flux_batch(void *fbank, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                                 uint32_t lag, float *d_out, size_t *n_out);
+SGX_API int sgx_flux_mags(void *fbank, const float *d_mags, size_t n_frames, uint32_t lag, float *d_out);
+SGX_API uint32_t sgx_flux_max_lag(const void *fbank);
 
 /* The triangular mel bank as sgx_fbank_create takes it.  Host only: no context, no device.
  * Over the TRUE bin frequencies f_k = k * sample_rate / (2W), k = 1 .. W - 1 (stored element j = k - 1) -- deliberately not the axis of

@@ -573,6 +573,23 @@ public:
         const int rc = sgx_fbank_cross_spec(bank_, d_spec, n_columns, d_out);
         if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
     }
+    // The flux (sgx_flux_*): per band (rise_l, rise_r, fall_l, fall_r) of every bin against the same bin `lag` frames earlier.
+    std::uint32_t flux_max_lag() const { return sgx_flux_max_lag(bank_); }
+    // device to device: PCM -> [frames][pairs][filters][4]; returns the frames written
+    std::size_t flux_batch(const float *d_pcm, std::size_t n_samples, float *d_out, std::uint32_t lag = 1, std::size_t first_frame = 0,
+                           std::size_t max_frames = (std::size_t)-1)
+    {
+        std::size_t got = 0;
+        const int rc = sgx_flux_batch(bank_, d_pcm, n_samples, first_frame, max_frames, lag, d_out, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
+        return got;
+    }
+    // the stage alone: [frames][pairs][M][2] rows -> [frames][pairs][filters][4]
+    void flux_apply(const float *d_mags, std::size_t n_frames, float *d_out, std::uint32_t lag = 1)
+    {
+        const int rc = sgx_flux_mags(bank_, d_mags, n_frames, lag, d_out);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(transform_.ctx()));
+    }
     sgx_fbank *raw() const { return bank_; }
 
 private:

@@ -132,6 +132,9 @@ SIGNATURES = [
     ("sgx_fbank_cross_batch", C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, C.POINTER(_sz)]),
     ("sgx_fbank_cross_spec", C.c_int, [_vp, _vp, _sz, _vp]),
     ("sgx_fbank_cross_fused", C.c_int, [_vp]),
+    ("sgx_flux_batch", C.c_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _vp, C.POINTER(_sz)]),
+    ("sgx_flux_mags", C.c_int, [_vp, _vp, _sz, C.c_uint32, _vp]),
+    ("sgx_flux_max_lag", C.c_uint32, [_vp]),
     ("sgx_mel_weights", C.c_int, [C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
                                   C.POINTER(_sz)]),
     ("sgx_spectrum_levels", C.c_int, [_ctx, _vp, C.c_uint32, _vp]),

@@ -1075,6 +1075,66 @@ int sgx_fbank_cross_batch(void *bank, const float *d_pcm, size_t n_samples, size
     return SGX_OK;
 }
 
+// ---- the flux of a bank: per band the sums of every bin's rise and fall against the same bin `lag` frames earlier (sgx_fbank.hpp) -------
+static_assert(sgx::flux::kWorkspaceBytes == kWorkspaceBytes, "flux_host.hpp counts rows of the one workspace");
+
+uint32_t sgx_flux_max_lag(const void *bank)
+{
+    const sgx_fbank *fb = static_cast<const sgx_fbank *>(bank);
+    return fb && fb->ctx ? sgx::flux::max_lag(mags_bytes_per_frame(fb->ctx)) : 0u;
+}
+
+int sgx_flux_mags(void *bank, const float *d_mags, size_t n_frames, uint32_t lag, float *d_out)
+{
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    sgx_ctx *c = fb->ctx;
+    if (lag == 0 || lag > sgx::flux::kMaxLag) return fail(c, SGX_ERR_INVALID_ARG, "sgx_flux_mags: lag must be 1 .. 64");
+    if (n_frames == 0) return SGX_OK;
+    if (!d_mags || !d_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_flux_mags: null buffer");
+    if ((uintptr_t)d_out & 15u) return fail(c, SGX_ERR_INVALID_ARG, "sgx_flux_mags: d_out must be 16-byte aligned");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = sgx::launch_fbank_flux_stage(c, fb, d_mags, 0, n_frames, lag, d_out);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_flux_mags: kernel launch");
+    return SGX_OK;
+}
+
+int sgx_flux_batch(void *bank, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, uint32_t lag, float *d_out,
+                         size_t *n_out)
+{
+    namespace flux = sgx::flux;
+    sgx_fbank *fb = static_cast<sgx_fbank *>(bank);
+    if (n_out) *n_out = 0;
+    if (!fb || !fb->ctx) return SGX_ERR_INVALID_ARG;
+    sgx_ctx *c = fb->ctx;
+    if (lag == 0 || lag > flux::kMaxLag) return fail(c, SGX_ERR_INVALID_ARG, "sgx_flux_batch: lag must be 1 .. 64");
+    // a frame and its predecessor lie in the workspace together, or the call does not run
+    const size_t cap = flux::row_cap(mags_bytes_per_frame(c));
+    if (lag > flux::max_lag(mags_bytes_per_frame(c)))
+        return fail(c, SGX_ERR_UNSUPPORTED, "sgx_flux_batch: lag " + std::to_string(lag) + " exceeds the cap of " +
+                                                std::to_string(flux::max_lag(mags_bytes_per_frame(c))) +
+                                                " frames (sgx_flux_max_lag); sgx_flux_mags takes any lag over rows the caller holds");
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_flux_batch", n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    if ((uintptr_t)d_out & 15u) return fail(c, SGX_ERR_INVALID_ARG, "sgx_flux_batch: d_out must be 16-byte aligned");
+    // ranges: the rows of a range's frames and of the `back` frames before them by the rows' own route into the workspace (the head is
+    // recomputed, not carried: a row is a pure function of its frame index), then the stage kernel over the frames behind the head
+    rc = ensure_workspace(c, flux::rows_needed(first_frame, n, lag, cap));
+    if (rc != SGX_OK) return rc;
+    const size_t end = first_frame + n;
+    for (size_t a = first_frame; a < end;) {
+        const flux::Range r = flux::range_at(a, end, lag, cap);
+        hipError_t e = rows_to_workspace(c, d_pcm, r.a - r.back, r.back + r.m, total);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_flux_batch: stft launch");
+        e = sgx::launch_fbank_flux_stage(c, fb, c->d_ws_mags.get(), r.back, r.m, lag, d_out + (a - first_frame) * (size_t)c->pairs * fb->n_filters * 4);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_flux_batch: filter launch");
+        a += r.m;
+    }
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
 int sgx_bands_peak_fused(const sgx_ctx *c)
 {
     if (!c) return SGX_ERR_INVALID_ARG;

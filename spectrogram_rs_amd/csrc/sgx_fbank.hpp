@@ -1,7 +1,8 @@
 // sgx_fbank.hpp -- the filter pass of the filterbank calls (include/sgx.h: sgx_fbank_batch, sgx_fbank_mags): one body for the stage kernel
 // (sgx_fbank.hip) and for the fused modes of the two 4096-point kernels (stft4096_wg.hip, stft4096_real.hip), so that a bank's output
 // is the same bits on every route.  The cross pass (sgx_fbank_cross_batch, sgx_fbank_cross_spec) is the same order over the four
-// products of a bin's (L, R) pair, one trip over the bank for all four.
+// products of a bin's (L, R) pair, one trip over the bank for all four.  The flux pass (sgx_flux_batch, sgx_flux_mags) is the
+// cross pass over another four elements: the rise and the fall of a bin's (l, r) pair against the same bin of an earlier frame.
 //
 // A wave per filter.  Lane l takes the filter's elements i = l, l + 64, l + 128, ... in ascending order into one fused-multiply-add
 // chain from +0; the 64 partial sums then meet in a halving tree (a[l] + a[l + 32], then + 16, 8, 4, 2, 1).  That order is the
@@ -10,6 +11,7 @@
 #pragma once
 
 #include "fbank_host.hpp"
+#include "flux_host.hpp"
 #include "sgx_internal.hpp"
 
 // A bank: its tables on the device.  It belongs to its context (sgx_destroy detaches the banks still alive: their calls then answer
@@ -30,6 +32,10 @@ hipError_t launch_fbank_stage(const sgx_ctx *c, const sgx_fbank *fb, const float
 bool wg4096_can_fuse_fbank(const sgx_ctx *c, const sgx_fbank *fb);   // stft4096_wg.hip
 hipError_t launch_fbank_cross_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_spec, size_t n_columns, float *d_out);   // sgx_fbank.hip
 bool wg4096_can_fuse_fbank_cross(const sgx_ctx *c, const sgx_fbank *fb);   // stft4096_wg.hip
+// The flux records of n_frames frames: d_rows holds skip + n_frames frames' rows [pairs][M][2], the records are those of the frames behind
+// the first `skip`; row r of d_rows has its predecessor at r - lag, and none where r < lag (skip <= lag: the head of a range, or 0)
+hipError_t launch_fbank_flux_stage(const sgx_ctx *c, const sgx_fbank *fb, const float *d_rows, size_t skip, size_t n_frames, uint32_t lag,
+                                   float *d_out);   // sgx_fbank.hip
 void detach_fbanks(sgx_ctx *c);   // sgx_fbank.hip
 
 #ifdef __HIPCC__
@@ -235,6 +241,37 @@ __device__ __forceinline__ void cross_filter_pass(const Col &col, const Filter *
         }
     }
 }
+
+// ---- the flux pass: per band the sums of a bin's rise and fall against the same bin `lag` frames earlier (include/sgx.h: sgx_flux_batch) --
+
+// Rise and fall of one bin's (l, r) pair, as the header defines them: x = m or rn(m * m), d = rn(x_t - x_{t - lag}) -- one subtract, never
+// contracted with the square -- then rise = d < 0 ? +0 : d and fall = d > 0 ? +0 : rn(+0 - d).  Equal words give +0 in both, a NaN
+// gives NaN in both (neither comparison holds).
+__device__ __forceinline__ float flux_element(float cur, float prev, bool square)
+{
+#pragma clang fp contract(off)
+    if (square) {
+        cur = __fmul_rn(cur, cur);
+        prev = __fmul_rn(prev, prev);
+    }
+    return __fsub_rn(cur, prev);
+}
+__device__ __forceinline__ void flux_terms(float2 cur, float2 prev, bool square, float2 &rise, float2 &fall)
+{
+    const float dl = flux_element(cur.x, prev.x, square), dr = flux_element(cur.y, prev.y, square);
+    rise.x = dl < 0.0f ? 0.0f : dl;
+    rise.y = dr < 0.0f ? 0.0f : dr;
+    fall.x = dl > 0.0f ? 0.0f : __fsub_rn(0.0f, dl);
+    fall.y = dr > 0.0f ? 0.0f : __fsub_rn(0.0f, dr);
+}
+
+// The element source of a column no LDS holds: both rows where they lie, rise and fall formed at every read -- the same bits, flux_terms
+// is a pure function of the two rows' words.  (A staged column goes through CrossColumns: (rise_l, rise_r) and (fall_l, fall_r).)
+struct FluxRows {
+    const float2 *cur, *prev;   // [M] (l, r) magnitudes of frame t and of frame t - lag
+    bool square;
+    __device__ __forceinline__ void operator()(uint32_t j, float2 &rise, float2 &fall) const { flux_terms(cur[j], prev[j], square, rise, fall); }
+};
 
 }  // namespace fbank
 #endif

@@ -835,6 +835,44 @@ class FilterBank:
             e._check(self._lib.sgx_fbank_cross_spec(self._h, e._dev_f32(spec), n, C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- the flux: per band the rise and the fall of every bin against the same bin `lag` frames earlier (include/sgx.h: sgx_flux_batch) ----
+    @property
+    def flux_max_lag(self) -> int:
+        """the largest lag flux_batch() takes: 64 unless a frame's rows are so long that the workspace holds fewer than 65 of them
+        (flux_apply() takes 1 .. 64 at any length)"""
+        return int(self._lib.sgx_flux_max_lag(self._h))
+
+    def flux_batch(self, pcm, lag: int = 1, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [frames][pairs][n_filters][4] float32: per band (rise_l, rise_r, fall_l, fall_r), the weighted sums of the half-wave
+        rectified differences of the bank's elements against frame t - lag, rectified per bin before the band sum.  Frames t < lag
+        (absolute) are zero.  rise is the spectral flux an onset detector reads; rise - fall telescopes, rise + fall is the L1 distance."""
+        import torch
+
+        e = self.engine
+        n_samples = pcm.numel() // e.channels
+        total = e.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        out = e._out(out, (n, e.pairs, self.n_filters, 4), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            e._check(self._lib.sgx_flux_batch(self._h, e._dev_f32(pcm), n_samples, first_frame, n, int(lag), C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return out
+
+    def flux_apply(self, mags, lag: int = 1, out=None):
+        """[frames][pairs][M][2] float32 rows (stft_batch's) -> [frames][pairs][n_filters][4] float32; frame t is differenced against
+        frame t - lag of the same pair, frames t < lag are zero"""
+        import torch
+
+        e = self.engine
+        n = mags.numel() // (e.pairs * e.M * 2)
+        out = e._out(out, (n, e.pairs, self.n_filters, 4), torch.float32)
+        if n:
+            e._check(self._lib.sgx_flux_mags(self._h, e._dev_f32(mags), n, int(lag), C.c_void_p(out.data_ptr())))
+        return out
+
 
 class ImageRing:
     """sgx_image: the width x rows RGBA Pixbuf of simple_spectrogram.rs:89-94 on the device, written one pixel column per frame at
