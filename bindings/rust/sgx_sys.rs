@@ -56,6 +56,12 @@ extern "C" {
                             k: u32, floor: f32, d_max: *mut f32, n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][2][K][4]
     pub fn sgx_maxima_mags(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, k: u32, floor: f32,
                            d_max: *mut f32) -> c_int;   // the stage alone, from magnitude rows
+    // the cumulative spectrum per frame, pair and side: per share p, (bin, c[bin - 1], c[bin], total) where the running sum reaches p * total
+    pub fn sgx_rolloff_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
+                             power: u32, h_p: *const f32, n_p: u32, d_out: *mut f32,
+                             n_out: *mut usize) -> c_int;   // PCM -> [frames][pairs][2][n_p][4]
+    pub fn sgx_rolloff_mags(ctx: *mut SgxCtx, d_mags: *const f32, n_columns: usize, power: u32, h_p: *const f32, n_p: u32,
+                            d_out: *mut f32) -> c_int;   // the stage alone, from magnitude rows
     // per-bin order statistics over groups of frames: the word of rank floor(q * (n - 1) + 0.5) of every column, bin and side, NaN last
     pub fn sgx_quantile_batch(ctx: *mut SgxCtx, d_pcm: *const f32, n_samples: usize, first_frame: usize, max_frames: usize,
                               group: usize, q: *const f64, n_q: u32, d_out: *mut f32,

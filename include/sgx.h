@@ -13,7 +13,7 @@
  *     All `h_*` pointers are host pointers.  The caller owns every I/O buffer.
  *   - Work is enqueued on the context's stream (sgx_set_stream; default: the NULL stream) and is
  *     asynchronous; sgx_sync() waits for it.  The batch calls (sgx_stft_batch*, sgx_render_*, sgx_bands_*batch, sgx_magnitude_in,
- *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_flux_batch, sgx_flux_mags, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_quantile_batch, sgx_quantile_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
+ *     sgx_fbank_batch, sgx_fbank_mags, sgx_fbank_cross_batch, sgx_fbank_cross_spec, sgx_flux_batch, sgx_flux_mags, sgx_psd_batch, sgx_csd_batch, sgx_psd_mags, sgx_csd_spec, sgx_maxima_batch, sgx_maxima_mags, sgx_rolloff_batch, sgx_rolloff_mags, sgx_quantile_batch, sgx_quantile_mags, sgx_image_write_columns / _read, sgx_view_write_rows / _draw, sgx_synth_white_noise,
  *     sgx_checksum_add) only enqueue;
  *     the calls that hand host data back or free host slots (sgx_process_one, sgx_live_tick*, sgx_spectrum_levels,
  *     sgx_checksum) and the calls that replace tables (sgx_set_gradient*, sgx_set_builtin_*) wait for the context's OWN
@@ -412,6 +412,51 @@ SGX_API int sgx_csd_fused(const sgx_ctx *ctx);
 SGX_API int sgx_maxima_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
                              uint32_t k, float floor, float *d_max, size_t *n_out);
 SGX_API int sgx_maxima_mags(sgx_ctx *ctx, const float *d_mags, size_t n_columns, uint32_t k, float floor, float *d_max);
+/* ---- The cumulative spectrum per frame: where the running sum of a row crosses a share of its total ------------------------------------
+ * Spectral roll-off (the 85 % / 95 % point), the spectral median (50 %), occupied bandwidth (the 0.5 % and 99.5 % points of ITU-R
+ * SM.328), the 5 % / 95 % energy edges an auto-ranging display sets its axis by (the reference has none: it draws every bin).  No row
+ * reaches the caller: 16 * n_p bytes per frame and side do.
+ *
+ * Take one frame, pair and side (0 = l, 1 = r).  The row is m[j], j = 0 .. M - 1, exactly the float32 words that sgx_stft_batch stores;
+ * element j is bin k = j + 1.  rn() is one round-to-nearest-even float32 operation.  The order below is part of the definition.
+ *   Summand.  x[j] = m[j] (power 1) or rn(m[j] * m[j]) (power 2: the x of a power-2 filterbank, never contracted into the add that
+ *     follows).  Any other power is SGX_ERR_INVALID_ARG.
+ *   Segments.  The row is cut into segments of S = 32 consecutive elements counted from element 0; the last may be short.  Within segment
+ *     b the partial is one chain of float32 adds from +0 in ascending order: s[b][i] = rn(s[b][i-1] + x[32 b + i]).
+ *   Offsets.  o[0] = +0 and o[b+1] = rn(o[b] + s[b][last i of b]): one chain of float32 adds over the segment totals in ascending order.
+ *   Cumulative value.  c[j] = rn(o[b] + s[b][i]) for j = 32 b + i.  The total is T = c[M-1], not a separately formed sum.  For x >= 0, c
+ *     never decreases:
+ *       rn is monotone, so within a segment s[b][i] = rn(s[b][i-1] + x) >= s[b][i-1] and hence c[32 b + i] >= c[32 b + i - 1];
+ *       the last c of segment b is rn(o[b] + s[b][last]), the very operation that forms o[b+1], so it EQUALS o[b+1];
+ *       the first c of segment b + 1 is rn(o[b+1] + s[b+1][0]) >= o[b+1].
+ *   S = 32 is fixed here.  It does not depend on the device, the route, the launch geometry or M.  In numpy: pad the row to a multiple of
+ *     32 with +0 and reshape to [.., 32]; np.cumsum(axis=-1, dtype=float32); np.cumsum of the last column, shifted by one; one add
+ *     (tests/rolloff_reference.py).
+ *   Threshold.  p[i], i = 0 .. n_p - 1, n_p from 1 to 8, each a float32 in (0, 1], in any order and possibly repeated.  thr = rn(p[i] *
+ *     T): one float32 product.  n_p = 0, n_p > 8, or any p that is NaN or outside (0, 1] is SGX_ERR_INVALID_ARG: nothing is written or
+ *     enqueued.  h_p is a host array, read before the call returns.
+ *   Result.  j* is the smallest j with c[j] >= thr; it exists whenever T > 0, because rn(p * T) <= T = c[M-1].  The record is four
+ *     floats, ((float)(j* + 1), c[j* - 1], c[j*], T), with +0 in place of c[-1].  If !(T > 0) -- an all-zero row, or a NaN anywhere in
+ *     it -- the record is (0, 0, 0, T); k = 0 is never a stored bin, as in sgx_maxima_*.  Every record is always written.  Rows with
+ *     negative values (the stage call only) are unspecified; infinities follow IEEE arithmetic.
+ *   The output is therefore a pure function of the row, bit for bit: independent of route, launch geometry, compute-unit limit, run claim,
+ *     run weights, stream, chunk seams and any split of a call (tests/test_gpu_rolloff.py).
+ * There is no interpolation and no conversion to Hz: k * sample_rate / (2 W) is the caller's, as is the fraction
+ * (thr - c[j* - 1]) / (c[j*] - c[j* - 1]).  Scaling as the rows'.
+ *
+ * sgx_rolloff_batch: d_out [n_out][pairs][2][n_p][4] float, 16-byte aligned (else SGX_ERR_INVALID_ARG, nothing written).  A mono stream
+ *   holds the same records on both sides (with SGX_FLAG_PAIRED_FRAMES each side holds what its rows hold).  first_frame, max_frames and
+ *   *n_out as sgx_maxima_batch: too few samples is *n_out = 0, not an error; a null buffer or a null h_p is SGX_ERR_INVALID_ARG; n_out
+ *   may be NULL.
+ * sgx_rolloff_mags: the stage alone over rows already on the device, d_mags [n_columns][pairs][M][2] as sgx_stft_batch writes them, into
+ *   d_out [n_columns][pairs][2][n_p][4].  Every W the library accepts, SGX_FLAG_LARGE_TRANSFORM lengths included.  n_columns == 0: SGX_OK.
+ * Stream-ordered and asynchronous; nothing waits on the host (a grown workspace may, as elsewhere); every kernel of a call goes onto the
+ * context's stream.  Device memory beyond the caller's buffers is the 192 MiB workspace only: the rows of a chunk of frames by their own
+ * route, then one kernel over them (a wave per row).  There is no fused mode, no flag and no query for one. */
+SGX_API int sgx_rolloff_batch(sgx_ctx *ctx, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames,
+                              uint32_t power, const float *h_p, uint32_t n_p, float *d_out, size_t *n_out);
+SGX_API int sgx_rolloff_mags(sgx_ctx *ctx, const float *d_mags, size_t n_columns, uint32_t power,
+                             const float *h_p, uint32_t n_p, float *d_out);
 /* ---- Per-bin order statistics over groups of frames: percentile spectra, the median spectrum, the per-bin minimum ---------------------
  * The level exceeded 90 %, 50 % and 10 % of the time per bin (L90, L50, L10), the median a spectral gate or a noise estimator uses
  * because one click does not move it, the minimum of minimum-statistics noise tracking.  None of them follows from a mean or a maximum.

@@ -261,6 +261,43 @@ public:
         if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
     }
 
+    // where the running sum of every frame's row crosses shares of its total: per frame, side (0 = l, 1 = r) and share p[i] the record
+    // {bin, c[bin - 1], c[bin], T}, c the cumulative value of include/sgx.h (segments of 32, power 1: magnitudes, 2: their squares), bin
+    // the first with c >= rn(p * T); {0, 0, 0, T} where !(T > 0) (sgx_rolloff_batch; interpolation and Hz are the caller's)
+    using Crossing = std::array<float, 4>;
+    std::vector<std::array<std::vector<Crossing>, 2>> rolloff_stream(const StereoMagnitude *lr, std::size_t n, uint32_t power,
+                                                                     const std::vector<float> &p)
+    {
+        if (p.empty() || p.size() > 8) throw Error(SGX_ERR_INVALID_ARG, "rolloff_stream: 1 .. 8 shares");
+        const std::size_t frames = sgx_num_frames(ctx_, n), n_p = p.size();
+        std::vector<std::array<std::vector<Crossing>, 2>> out(frames);
+        if (!frames) return out;
+        reserve(n * 2 * sizeof(float), frames * 2 * n_p * 4 * sizeof(float));
+        check_hip(hipMemcpy(d_in_, lr, n * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::size_t got = 0;
+        int rc = sgx_rolloff_batch(ctx_, d_in_, n, 0, frames, power, p.data(), (uint32_t)n_p, d_out_, &got);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        if ((rc = sgx_sync(ctx_)) != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+        std::vector<float> flat(frames * 2 * n_p * 4);
+        check_hip(hipMemcpy(flat.data(), d_out_, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (std::size_t f = 0; f < frames; ++f)
+            for (std::size_t s = 0; s < 2; ++s) {
+                out[f][s].resize(n_p);
+                for (std::size_t r = 0; r < n_p; ++r) {
+                    const float *b = &flat[((f * 2 + s) * n_p + r) * 4];
+                    out[f][s][r] = {b[0], b[1], b[2], b[3]};
+                }
+            }
+        return out;
+    }
+    // the stage alone over rows already on the device (DEVICE pointers; stream-ordered, not waited for)
+    // (sgx_rolloff_mags: [n_columns][pairs][M][2] -> [n_columns][pairs][2][n_p][4], d_out 16-byte aligned; h_p a HOST array)
+    void rolloff_mags(const float *d_mags, std::size_t n_columns, uint32_t power, const float *h_p, uint32_t n_p, float *d_out)
+    {
+        const int rc = sgx_rolloff_mags(ctx_, d_mags, n_columns, power, h_p, n_p, d_out);
+        if (rc != SGX_OK) throw Error(rc, sgx_last_error(ctx_));
+    }
+
     // per-bin order statistics over groups of `group` frames: columns x q.size() rows of (W-1) bins of {l, r}, each the word of rank
     // floor(q * (n - 1) + 0.5) among the column's n frames, NaN last (sgx_quantile_batch; include/sgx.h states order and rank; a column
     // longer than quantile_max_group() is refused)

@@ -119,6 +119,8 @@ SIGNATURES = [
     ("sgx_csd_fused", C.c_int, [_ctx]),
     ("sgx_maxima_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, C.c_uint32, C.c_float, _vp, C.POINTER(_sz)]),
     ("sgx_maxima_mags", C.c_int, [_ctx, _vp, _sz, C.c_uint32, C.c_float, _vp]),
+    ("sgx_rolloff_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, _vp, C.POINTER(_sz)]),
+    ("sgx_rolloff_mags", C.c_int, [_ctx, _vp, _sz, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, _vp]),
     ("sgx_quantile_batch", C.c_int, [_ctx, _vp, _sz, _sz, _sz, _sz, C.POINTER(C.c_double), C.c_uint32, _vp, C.POINTER(_sz)]),
     ("sgx_quantile_mags", C.c_int, [_ctx, _vp, _sz, _sz, C.POINTER(C.c_double), C.c_uint32, _vp, C.POINTER(_sz)]),
     ("sgx_quantile_max_group", _sz, [_ctx]),

@@ -10,6 +10,7 @@
 #include "sgx_maxima.hpp"
 #include "sgx_psd.hpp"
 #include "sgx_quantile.hpp"
+#include "sgx_rolloff.hpp"
 #include "sgx_internal.hpp"
 
 namespace {
@@ -499,6 +500,21 @@ int check_maxima(sgx_ctx *c, const char *who, uint32_t k, float floor, const flo
     if (k < 1 || k > sgx::maxima::kMaxK) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": k must be 1 .. 64");
     if (!(floor >= 0.0f) || std::isinf(floor)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": floor must be finite and >= 0");
     if ((uintptr_t)d_max & 15u) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": d_max must be 16-byte aligned");
+    return SGX_OK;
+}
+
+// sgx_rolloff_batch and sgx_rolloff_mags: what both calls refuse before anything is enqueued; the shares, read from the host array
+int check_rolloff(sgx_ctx *c, const char *who, uint32_t power, const float *h_p, uint32_t n_p, const float *d_out, sgx::rolloff::Shares &shares)
+{
+    if (power != 1 && power != 2) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": power must be 1 or 2");
+    if (n_p < 1 || n_p > sgx::rolloff::kMaxShares) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": n_p must be 1 .. 8");
+    if (!h_p) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": h_p is null");
+    shares = sgx::rolloff::Shares{};
+    for (uint32_t i = 0; i < n_p; ++i) {
+        if (!(h_p[i] > 0.0f && h_p[i] <= 1.0f)) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": every p must lie in (0, 1]");
+        shares.p[i] = h_p[i];
+    }
+    if ((uintptr_t)d_out & 15u) return fail(c, SGX_ERR_INVALID_ARG, std::string(who) + ": d_out must be 16-byte aligned");
     return SGX_OK;
 }
 
@@ -1278,6 +1294,46 @@ int sgx_maxima_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t fi
         if (e != hipSuccess) return fail_hip(c, e, "sgx_maxima_batch: stft launch");
         e = sgx::maxima::launch_maxima(c, c->d_ws_mags.get(), m * c->pairs, k, floor, d_max + done * (size_t)c->pairs * 2 * k * 4);
         return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_maxima_batch: selection launch");
+    });
+    if (rc != SGX_OK) return rc;
+    if (n_out) *n_out = n;
+    return SGX_OK;
+}
+
+// ---- where a row's cumulative sum crosses shares of its total (sgx_rolloff.hpp): the rows through the workspace, the kernel over them ----
+
+int sgx_rolloff_mags(sgx_ctx *c, const float *d_mags, size_t n_columns, uint32_t power, const float *h_p, uint32_t n_p, float *d_out)
+{
+    if (!c) return SGX_ERR_INVALID_ARG;
+    sgx::rolloff::Shares shares;
+    const int rc = check_rolloff(c, "sgx_rolloff_mags", power, h_p, n_p, d_out, shares);
+    if (rc != SGX_OK) return rc;
+    if (n_columns == 0) return SGX_OK;
+    if (!d_mags || !d_out) return fail(c, SGX_ERR_INVALID_ARG, "sgx_rolloff_mags: null buffer");
+    SGX_HIP(c, hipSetDevice(c->device));
+    const hipError_t e = sgx::rolloff::launch_rolloff(c, d_mags, n_columns * c->pairs, power, shares, n_p, d_out);
+    if (e != hipSuccess) return fail_hip(c, e, "sgx_rolloff_mags: kernel launch");
+    return SGX_OK;
+}
+
+int sgx_rolloff_batch(sgx_ctx *c, const float *d_pcm, size_t n_samples, size_t first_frame, size_t max_frames, uint32_t power,
+                      const float *h_p, uint32_t n_p, float *d_out, size_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    sgx::rolloff::Shares shares;
+    if (c) {
+        const int bad = check_rolloff(c, "sgx_rolloff_batch", power, h_p, n_p, d_out, shares);
+        if (bad != SGX_OK) return bad;
+    }
+    size_t total, n;
+    int rc = begin_batch(c, "sgx_rolloff_batch", n_samples, first_frame, max_frames, d_pcm, d_out, n_out, total, n);
+    if (rc != SGX_OK || n == 0) return rc;
+    // two kernels: the rows of a chunk of frames in the bounded workspace, by the rows' own route, then the cumulative kernel over them
+    rc = in_workspace_chunks(c, n, [&](size_t done, size_t m) {
+        hipError_t e = rows_to_workspace(c, d_pcm, first_frame + done, m, total);
+        if (e != hipSuccess) return fail_hip(c, e, "sgx_rolloff_batch: stft launch");
+        e = sgx::rolloff::launch_rolloff(c, c->d_ws_mags.get(), m * c->pairs, power, shares, n_p, d_out + done * (size_t)c->pairs * 2 * n_p * 4);
+        return e == hipSuccess ? (int)SGX_OK : fail_hip(c, e, "sgx_rolloff_batch: cumulative launch");
     });
     if (rc != SGX_OK) return rc;
     if (n_out) *n_out = n;

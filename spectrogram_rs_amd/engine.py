@@ -436,6 +436,47 @@ class SpectrogramEngine:
                                                   C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- the cumulative spectrum per frame ------------------------------------------------------
+    @staticmethod
+    def _shares(p):
+        p = [float(x) for x in ([p] if isinstance(p, (int, float)) else p)]
+        return (C.c_float * len(p))(*p), len(p)
+
+    def rolloff_batch(self, pcm, power: int, p, first_frame: int = 0, max_frames: Optional[int] = None, out=None):
+        """PCM -> [frames][pairs][2][n_p][4] float32: per frame, pair, side and share p[i] in (0, 1] the record (bin, c[bin - 1], c[bin], T):
+        the first bin at which the cumulative value c of stft_batch's row (power 1) or of its squares (power 2) reaches rn(p[i] * T), T the
+        row's total; (0, 0, 0, T) where T is not > 0.  include/sgx.h fixes the sum order (segments of 32).  Interpolation and Hz are the
+        caller's."""
+        import torch
+
+        n_samples = pcm.numel() // self.channels
+        total = self.num_frames(n_samples)
+        n = max(total - first_frame, 0)
+        if max_frames is not None:
+            n = min(n, max_frames)
+        h_p, n_p = self._shares(p)
+        out = self._out(out, (n, self.pairs, 2, n_p, 4), torch.float32)
+        got = C.c_size_t(0)
+        if n:
+            self._check(self._lib.sgx_rolloff_batch(self._ctx, self._dev_f32(pcm), n_samples, first_frame, n, C.c_uint32(int(power)), h_p,
+                                                    C.c_uint32(n_p), C.c_void_p(out.data_ptr()), C.byref(got)))
+            assert got.value == n
+        return out
+
+    def rolloff_mags(self, mags, power: int, p, out=None):
+        """The stage of rolloff_batch alone: float32 [columns][pairs][M][2] rows, as stft_batch writes them -> [columns][pairs][2][n_p][4]"""
+        import torch
+
+        row_floats = self.pairs * self.M * 2
+        assert mags.dtype == torch.float32 and mags.numel() % row_floats == 0, "expected whole float32 rows of this context"
+        n = mags.numel() // row_floats
+        h_p, n_p = self._shares(p)
+        out = self._out(out, (n, self.pairs, 2, n_p, 4), torch.float32)
+        if n:
+            self._check(self._lib.sgx_rolloff_mags(self._ctx, self._dev_f32(mags), n, C.c_uint32(int(power)), h_p, C.c_uint32(n_p),
+                                                   C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- per-bin order statistics over groups of frames ---------------------------------------
     @staticmethod
     def _quantiles(q):
